@@ -8,16 +8,21 @@ seq=4096, causal, fp16 in / fp32 accumulate.  A *step* is one forward pass
 and sharded across ranks by batch index with no collective on the data path
 (SURVEY.md §8(e)), so scaling is "strong".
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 
 Rank 0 prints ONE JSON line.  `value` = total TFLOPS of the whole job
 (reference FLOP convention 4*B*H*S^2*D/2 for causal, flash_attention.cu:938-939)
 over the max-over-ranks wall time of K steps.  `roofline.achieved` comes from
-HIP events around every launch on the launch stream; `roofline.traffic` from
-two rocprofv3 --pmc passes this run starts itself (FETCH_SIZE, WRITE_SIZE).
-`cpu_baseline` times the CPU oracle (a restatement of the reference's
-cpu_attention) on config 0 (S=512) on this host (rank 0, N=1 only).
+HIP events around every launch on the launch stream.
+
+A plain run sets up, warms up, times the K steps and prints the line.
+--dump-outputs DIR also writes what the last timed step computed (a fixed
+sample of the output rows, float32) as DIR/out.npy.  --full adds the legs that
+take runs of their own (rank 0, N=1 only): the per-config `sweep`,
+`roofline.traffic` from two rocprofv3 --pmc passes this run starts itself
+(FETCH_SIZE, WRITE_SIZE), and `cpu_baseline`, which times the CPU oracle (a
+restatement of the reference's cpu_attention) on config 0 (S=512) on this host.
 """
 from __future__ import annotations
 
@@ -50,6 +55,8 @@ SWEEP = [
 MFMA_FLOP_PER_CLK_PER_CU = 4096  # fp16 dense, gfx950 (16x16x32: 16384 FLOP / 16 clk / SIMD x 4)
 CLOCK_HZ = 2.4e9                 # MI355X max engine clock (MI355X_MICROARCH.md)
 HBM_PEAK_GBS = 8000.0
+DUMP_ROWS = 65536                # output rows --dump-outputs samples (32 MiB as float32)
+DUMP_SEED = 20240
 
 
 def shard_range(total: int, world: int, rank: int):
@@ -111,6 +118,30 @@ def _time_reference_loop(torch, fa, q, k, v, o, causal, iters=100, warm=20, runs
         b.synchronize()
         res.append(a.elapsed_time(b) / iters)
     return res
+
+
+def sample_rows(total_rows: int, n: int = DUMP_ROWS, seed: int = DUMP_SEED):
+    """Sorted indices of the output rows --dump-outputs keeps: all of them when
+    there are at most `n`, else `n` distinct rows drawn by a host generator
+    with a fixed seed (the same rows in every run and every build)."""
+    import numpy as np
+
+    if total_rows <= n:
+        return np.arange(total_rows, dtype=np.int64)
+    idx = np.random.default_rng(seed).choice(total_rows, size=n, replace=False)
+    return np.sort(idx).astype(np.int64)
+
+
+def dump_outputs(torch, out, directory, name):
+    """Write the sampled rows of `out` ([B,H,S,D] on the device) to
+    directory/name.npy as float32 [rows, D]."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    rows = out.view(-1, out.shape[-1])
+    idx = torch.from_numpy(sample_rows(rows.shape[0])).to(out.device)
+    np.save(os.path.join(directory, name + ".npy"),
+            rows.index_select(0, idx).float().cpu().numpy())
 
 
 # --------------------------------------------------------------------------
@@ -307,17 +338,27 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--no-sweep", action="store_true", help="skip the per-config sweep")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output (a fixed row sample, float32) "
+                         "to DIR/out.npy (DIR/out_rank<r>.npy per rank at N > 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the per-config sweep, the CPU baselines and the live "
+                         "rocprofv3 HBM-traffic passes (N=1 only)")
+    ap.add_argument("--no-sweep", action="store_true",
+                    help="with --full: skip the per-config sweep")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baselines")
     ap.add_argument("--cpu-seconds", type=float, default=5.0,
                     help="time budget of the torch-eager CPU baseline")
     ap.add_argument("--no-pmc", action="store_true",
-                    help="skip the live rocprofv3 HBM-traffic passes")
+                    help="with --full: skip the live rocprofv3 HBM-traffic passes")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.pmc_child:
         _pmc_child()
         return
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
 
@@ -374,6 +415,9 @@ def main():
         dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)
     wall_max = float(elapsed.item())
 
+    if args.dump_outputs:
+        dump_outputs(torch, o, args.dump_outputs, "out" if world == 1 else f"out_rank{rank}")
+
     total_flops = attention_flops(B, H, S, HEAD_DIM, causal) * args.steps
     value = total_flops / wall_max / 1e12
     ms_per_step = wall_max * 1e3 / args.steps
@@ -390,7 +434,7 @@ def main():
         return
 
     sweep = {}
-    if world == 1 and not args.no_sweep:
+    if args.full and world == 1 and not args.no_sweep:
         del q, k, v, o
         torch.cuda.empty_cache()
         for name, b, h, s, c in SWEEP:
@@ -406,7 +450,7 @@ def main():
 
     cpu = None
     cpu_torch = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline_oracle()
         except Exception as e:  # oracle not built: report, never fall back
@@ -419,8 +463,8 @@ def main():
     kernel_name = kernel_symbol(cfg_name)
     traffic, provenance = None, "not measured at world > 1 (per-rank shard launches)"
     if world == 1:
-        live_err = "skipped (--no-pmc)"
-        if not args.no_pmc:
+        live_err = "skipped (--no-pmc)" if args.full else "skipped (not --full)"
+        if args.full and not args.no_pmc:
             try:
                 traffic, live_err = measure_traffic_live(kernel_name)
             except Exception as e:

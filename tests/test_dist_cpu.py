@@ -41,6 +41,23 @@ def test_flop_and_byte_conventions():
     assert abs(bench.mfma_peak_tflops(256) - 2516.58) < 0.1
 
 
+def test_dump_outputs_sample(tmp_path):
+    # --dump-outputs: the same sorted, distinct rows every time, within 64 MB as float32
+    total = 64 * 32 * 4096
+    idx = bench.sample_rows(total)
+    assert idx.shape == (bench.DUMP_ROWS,) and idx.dtype == np.int64
+    assert np.all(np.diff(idx) > 0) and 0 <= idx[0] and idx[-1] < total
+    assert np.array_equal(idx, bench.sample_rows(total))
+    assert bench.DUMP_ROWS * bench.HEAD_DIM * 4 <= 64 * 2 ** 20
+    assert np.array_equal(bench.sample_rows(7), np.arange(7))
+    # a small output is written whole, as float32 [rows, D]
+    o = (torch.arange(2 * 3 * 5 * 8, dtype=torch.float32) / 64).half().view(2, 3, 5, 8)
+    bench.dump_outputs(torch, o, str(tmp_path / "d"), "out")
+    got = np.load(tmp_path / "d" / "out.npy")
+    assert got.dtype == np.float32 and got.shape == (30, 8)
+    assert np.array_equal(got, o.float().view(30, 8).numpy())
+
+
 def _worker(rank, world, port, result_q):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
