@@ -1,0 +1,212 @@
+// fa_decode.hip -- host side of the decode-attention entries of
+// include/fa_mi355x.h (fa_decode_f16 / fa_decode_bf16, the split plan and the
+// workspace size).  The kernel is csrc/fa_decode_kernel.hpp.  It is not a tile
+// config: fa_config_info() does not list it.
+#include <hip/hip_runtime.h>
+
+#include <math.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <atomic>
+#include <mutex>
+
+#include "fa_decode_kernel.hpp"
+#include "fa_mi355x.h"
+
+namespace fa {
+
+// CUs of the current device (cached per device id; 256 if the query fails)
+static int decode_num_cus() {
+  static std::atomic<int> cache[64];  // 0: not asked yet (entries may run on several host threads)
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+  int n = cache[dev].load(std::memory_order_relaxed);
+  if (!n) {
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+      n = 256;
+    cache[dev].store(n, std::memory_order_relaxed);
+  }
+  return n;
+}
+
+// Workspace layout, shared with the causal split tier (fa_fwd.hip): arrival
+// counters in the FIXED first 64 KB, then the per-row log2-sum-exp, then the
+// fp32 partial O slabs.
+constexpr unsigned long long kDecodeCtrBytes = 65536;
+// most pieces a cache is cut into: the last arriver reads every piece's slab
+// (64 pieces x 16 rows x 512 B = 512 KB for one 16-row unit)
+constexpr int kDecodeMaxSplits = 64;
+// the plan fills the CUs kDecodeFill times over (decode section)
+constexpr int kDecodeFill = 1;
+
+struct DecodeGeom {
+  bool ok = false;
+  int group = 0, rows = 0, nb = 0, rw = 0, rgroups = 0;
+  long long units = 0;  // (batch, kv head, row group)
+};
+
+static DecodeGeom decode_geom(int batch, int heads_q, int heads_kv, int seqlen_q) {
+  DecodeGeom ge;
+  if (batch <= 0 || heads_q <= 0 || heads_kv <= 0 || seqlen_q < 1 || seqlen_q > 16 ||
+      heads_q % heads_kv != 0)
+    return ge;
+  ge.group = heads_q / heads_kv;
+  ge.rows = ge.group * seqlen_q;
+  ge.nb = ge.rows <= 16 ? 1 : (ge.rows <= 32 ? 2 : 4);
+  ge.rw = 16 * ge.nb;
+  ge.rgroups = (ge.rows + ge.rw - 1) / ge.rw;
+  ge.units = (long long)batch * heads_kv * ge.rgroups;
+  ge.ok = true;
+  return ge;
+}
+
+// 1 when the units already fill the CUs; otherwise enough pieces to fill them
+// kDecodeFill times, pieces no shorter than one round of the four waves (256
+// keys), at most kDecodeMaxSplits
+static int decode_plan(const DecodeGeom& ge, int kv_capacity) {
+  if (!ge.ok || kv_capacity <= 0) return 1;
+  const long long cus = decode_num_cus();
+  if (ge.units >= cus) return 1;
+  const long long want = (cus * kDecodeFill + ge.units - 1) / ge.units;
+  const long long longest = std::max(1, kv_capacity / 256);
+  return (int)std::min(std::min(want, longest), (long long)kDecodeMaxSplits);
+}
+
+static unsigned long long decode_lse_bytes(const DecodeGeom& ge, int ns) {
+  const unsigned long long n = (unsigned long long)ge.units * ns * ge.rw * 4;
+  return (n + 255) / 256 * 256;
+}
+static unsigned long long decode_ws_total(const DecodeGeom& ge, int head_dim, int ns) {
+  if (ns <= 1) return 0;
+  return kDecodeCtrBytes + decode_lse_bytes(ge, ns) +
+         (unsigned long long)ge.units * ns * ge.rw * head_dim * 4;
+}
+
+template <class T, int HDIM, int NB>
+static int decode_launch_inst(const DecodeParams& p, unsigned grid, hipStream_t stream) {
+  constexpr int kLds = decode_lds_bytes<HDIM, NB>();
+  static std::once_flag flags[64];
+  static hipError_t errs[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return FA_ERR_HIP;
+  std::call_once(flags[dev], [dev] {
+    errs[dev] = hipFuncSetAttribute((const void*)fa_decode_kernel<T, HDIM, NB>,
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
+  });
+  if (errs[dev] != hipSuccess) return FA_ERR_HIP;
+  hipLaunchKernelGGL((fa_decode_kernel<T, HDIM, NB>), dim3(grid), dim3(256), kLds, stream, p);
+  return hipGetLastError() == hipSuccess ? FA_OK : FA_ERR_LAUNCH;
+}
+
+template <class T, int HDIM>
+static int decode_launch_nb(int nb, const DecodeParams& p, unsigned grid, hipStream_t stream) {
+  switch (nb) {
+    case 1: return decode_launch_inst<T, HDIM, 1>(p, grid, stream);
+    case 2: return decode_launch_inst<T, HDIM, 2>(p, grid, stream);
+    default: return decode_launch_inst<T, HDIM, 4>(p, grid, stream);
+  }
+}
+
+static int decode_entry(int dtype, const void* q, const void* k, const void* v, void* o, float* lse,
+                        int batch, int heads_q, int heads_kv, int seqlen_q, int kv_capacity,
+                        int head_dim, const int* kv_lens, int causal, int num_splits, void* ws,
+                        unsigned long long ws_bytes, void* hip_stream) {
+  if (batch < 0 || heads_q < 0 || heads_kv < 0 || kv_capacity < 0 || head_dim < 0 || num_splits < 0)
+    return FA_ERR_BAD_SHAPE;
+  if (head_dim != 128 && head_dim != 64) return FA_ERR_UNSUPPORTED_HEAD_DIM;
+  if (seqlen_q < 1 || seqlen_q > 16) return FA_ERR_BAD_SHAPE;
+  if (batch == 0 || heads_q == 0) return FA_OK;
+  if (heads_kv == 0 || heads_q % heads_kv != 0) return FA_ERR_BAD_SHAPE;
+  if ((long long)batch * heads_q * seqlen_q > 0x7fffffffLL) return FA_ERR_BAD_SHAPE;
+  // a head's cache rows are addressed through one buffer resource whose byte
+  // range (cap * 2 * head_dim) is a 32-bit int
+  if ((long long)kv_capacity * 2 * head_dim > 0x7fffffffLL) return FA_ERR_BAD_SHAPE;
+  if (!kv_lens && causal && kv_capacity < seqlen_q && kv_capacity > 0) return FA_ERR_BAD_SHAPE;
+  hipStream_t stream = (hipStream_t)hip_stream;
+  const size_t nrow = (size_t)batch * heads_q * seqlen_q;
+  if (kv_capacity == 0) {
+    // rows but no keys: O = 0, LSE = -inf; nothing else runs
+    if (!o) return FA_ERR_NULL_POINTER;
+    if (hipMemsetAsync(o, 0, nrow * head_dim * 2, stream) != hipSuccess) return FA_ERR_HIP;
+    if (lse && hipMemsetD32Async((hipDeviceptr_t)lse, (int)0xff800000u, nrow, stream) != hipSuccess)
+      return FA_ERR_HIP;
+    return FA_OK;
+  }
+  if (!q || !k || !v || !o) return FA_ERR_NULL_POINTER;
+  const DecodeGeom ge = decode_geom(batch, heads_q, heads_kv, seqlen_q);
+  if (num_splits > kDecodeMaxSplits) return FA_ERR_BAD_CONFIG;
+  const int ns = num_splits > 0 ? num_splits : decode_plan(ge, kv_capacity);
+  if (ge.units * ns > 0x7fffffffLL) return FA_ERR_BAD_SHAPE;
+  if (ns > 1) {
+    // one arrival counter per unit in the 64-KB region (the plan splits only
+    // when units are fewer than CUs; a forced split of more units is refused)
+    if (ge.units > (long long)(kDecodeCtrBytes / 4)) return FA_ERR_BAD_CONFIG;
+    // the slabs take 16-B sc1 stores / loads: a 16-byte aligned workspace
+    if (!ws || ws_bytes < decode_ws_total(ge, head_dim, ns) || (reinterpret_cast<uintptr_t>(ws) & 15) != 0)
+      return FA_ERR_WORKSPACE;
+  }
+  DecodeParams p = {};
+  p.q = q;
+  p.k = k;
+  p.v = v;
+  p.o = o;
+  p.lse = lse;
+  p.kv_lens = kv_lens;
+  p.hq = heads_q;
+  p.hkv = heads_kv;
+  p.sq = seqlen_q;
+  p.cap = kv_capacity;
+  p.group = ge.group;
+  p.rows = ge.rows;
+  p.rgroups = ge.rgroups;
+  p.num_splits = ns;
+  p.causal = causal ? 1 : 0;
+  p.c = 1.4426950408889634f / sqrtf((float)head_dim);
+  if (ns > 1) {
+    char* w = static_cast<char*>(ws);
+    p.ws_ctr = reinterpret_cast<unsigned*>(w);
+    p.ws_lse = reinterpret_cast<float*>(w + kDecodeCtrBytes);
+    p.ws_o = reinterpret_cast<float*>(w + kDecodeCtrBytes + decode_lse_bytes(ge, ns));
+  }
+  const unsigned grid = (unsigned)(ge.units * ns);
+  if (dtype == FA_DTYPE_BF16)
+    return head_dim == 128 ? decode_launch_nb<__bf16, 128>(ge.nb, p, grid, stream)
+                           : decode_launch_nb<__bf16, 64>(ge.nb, p, grid, stream);
+  return head_dim == 128 ? decode_launch_nb<f16, 128>(ge.nb, p, grid, stream)
+                         : decode_launch_nb<f16, 64>(ge.nb, p, grid, stream);
+}
+
+}  // namespace fa
+
+using namespace fa;
+
+extern "C" int fa_decode_f16(const void* q, const void* k, const void* v, void* o, float* lse,
+                             int batch, int heads_q, int heads_kv, int seqlen_q, int kv_capacity,
+                             int head_dim, const int* kv_lens, int causal, int num_splits,
+                             void* workspace, unsigned long long ws_bytes, void* hip_stream) {
+  return decode_entry(FA_DTYPE_F16, q, k, v, o, lse, batch, heads_q, heads_kv, seqlen_q, kv_capacity,
+                      head_dim, kv_lens, causal, num_splits, workspace, ws_bytes, hip_stream);
+}
+
+extern "C" int fa_decode_bf16(const void* q, const void* k, const void* v, void* o, float* lse,
+                              int batch, int heads_q, int heads_kv, int seqlen_q, int kv_capacity,
+                              int head_dim, const int* kv_lens, int causal, int num_splits,
+                              void* workspace, unsigned long long ws_bytes, void* hip_stream) {
+  return decode_entry(FA_DTYPE_BF16, q, k, v, o, lse, batch, heads_q, heads_kv, seqlen_q, kv_capacity,
+                      head_dim, kv_lens, causal, num_splits, workspace, ws_bytes, hip_stream);
+}
+
+extern "C" int fa_decode_num_splits(int batch, int heads_q, int heads_kv, int seqlen_q,
+                                    int kv_capacity, int head_dim) {
+  if (head_dim != 128 && head_dim != 64) return 1;
+  return decode_plan(decode_geom(batch, heads_q, heads_kv, seqlen_q), kv_capacity);
+}
+
+extern "C" unsigned long long fa_decode_ws_bytes(int batch, int heads_q, int heads_kv, int seqlen_q,
+                                                 int kv_capacity, int head_dim, int num_splits) {
+  if (head_dim != 128 && head_dim != 64) return 0;
+  const DecodeGeom ge = decode_geom(batch, heads_q, heads_kv, seqlen_q);
+  if (!ge.ok || kv_capacity <= 0 || num_splits < 0 || num_splits > kDecodeMaxSplits) return 0;
+  return decode_ws_total(ge, head_dim, num_splits > 0 ? num_splits : decode_plan(ge, kv_capacity));
+}

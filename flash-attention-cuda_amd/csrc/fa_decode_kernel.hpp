@@ -1,0 +1,420 @@
+// Decode attention over a K/V cache for gfx950: a few query tokens (1..16)
+// per head against a long cache whose length differs per batch element, with
+// grouped K/V heads (GQA / MQA) and the key range split across workgroups and
+// merged in the same launch.
+//
+//   O[b,hq,t,:] = softmax(Q[b,hq,t,:] . K[b,hkv,0:len_b,:]^T / sqrt(D) [+ mask]) V[b,hkv,0:len_b,:]
+//   hkv = hq / (Hq / Hkv);  causal (bottom-right): token t sees keys <= len_b - Sq + t
+//
+// Decomposition.  The G*Sq query rows that share one K/V head are contiguous
+// in a [B][Hq][Sq][D] tensor (row r = (hq - hkv*G)*Sq + t), so they form the
+// query dimension of the MFMAs in NB = 1, 2 or 4 blocks of 16 rows; more than
+// 64 rows become several row groups.  A workgroup = (batch, kv head, row
+// group, key piece), four waves.  The batch element's own 64-key tiles
+// (from kv_lens[b], not from the capacity) are cut into num_splits pieces;
+// wave w of a piece streams tiles w, w+4, ... with no workgroup barrier in
+// the loop and keeps its own (m, l, O) in the exp2 domain.  The four partials
+// are merged once through LDS; with num_splits > 1 each piece then hands its
+// normalised partial to the last-arriving piece through the workspace (the
+// causal split tier's hand-off, fa_w4_kernel.hpp).
+//
+// Operand movement (the operand is streamed once, so LDS is used only where a
+// transpose needs it):
+//   K: straight from HBM into the A-operand registers of S^T = K . Q^T, one
+//      buffer_load_dwordx4 per lane per 16-key x 32-dim fragment, the next
+//      tile's 16 fragments issued right after the current tile's QK^T.
+//   V: register-staged into a wave-private 16-KB LDS image (image A of
+//      fa_fwd_kernel.hpp) and read back with ds_read_b64_tr_b16 as the A
+//      operand of O^T = V^T . P^T.  The next tile's V loads are issued right
+//      after the image is written, so they fly during PV, the next QK^T and
+//      softmax.  The image is wave-private: no barrier, the wave's own LDS
+//      order suffices.
+// All loads are plain builtins, so hipcc counts vmcnt itself and each wave
+// keeps one K or V tile (16 KB at head_dim 128) in flight at any time.
+// The K/V descriptors' range is len_b rows: rows past the length read as
+// zeros whatever the capacity padding holds (P = 0 and a finite V).
+#pragma once
+
+#include "fa_fwd_kernel.hpp"
+
+namespace fa {
+
+struct DecodeParams {
+  const void* q;
+  const void* k;
+  const void* v;
+  void* o;
+  float* lse;          // [B][Hq][Sq] natural-log LSE, or nullptr
+  const int* kv_lens;  // device int32[B], or nullptr (= cap)
+  int hq, hkv, sq, cap;
+  int group;           // hq / hkv
+  int rows;            // group * sq: query rows per K/V head
+  int rgroups;         // row groups (16 * NB rows each) per K/V head
+  int num_splits;
+  int causal;
+  float c;             // log2(e) / sqrt(D)
+  unsigned* ws_ctr;    // [unit] arrival counters (the workspace's first 64 KB)
+  float* ws_lse;       // [unit][piece][16 NB] log2-sum-exp
+  float* ws_o;         // [unit][piece][16 NB][D] normalised partial O
+};
+
+constexpr int kDecodeVBytes = 4 * 64 * 256;  // four wave-private V images
+template <int HDIM, int NB>
+constexpr int decode_lds_bytes() {
+  // in-CU merge region (reuses the images): four waves' O and (m, l); it
+  // also covers the Q image of the 64-row head_dim-128 variant (16 KB)
+  constexpr int merge = 4 * NB * (HDIM / 16) * 1024 + 4 * NB * 64 * 8;
+  return merge > kDecodeVBytes ? merge : kDecodeVBytes;
+}
+
+// The last-arriving piece's merge of a unit's NS partials, in piece order:
+//   O = sum_s 2^(lse_s - M) O_s / sum_s 2^(lse_s - M),  M = max_s lse_s.
+// Thread = one 16-B chunk (4 fp32) of one row; every slab load is sc1.
+template <class T, int HDIM, int NB>
+__device__ __forceinline__ void decode_merge_pieces(const DecodeParams& p, size_t unit, int ns,
+                                                    __amdgpu_buffer_rsrc_t ro, float* lse_out,
+                                                    int row0, int tid) {
+  constexpr int kSc1 = 16, RW = 16 * NB, CH = HDIM / 4;
+  typedef typename Elem<T>::x4 tx4;
+  const __amdgpu_buffer_rsrc_t rs =
+      make_rsrc(p.ws_o + unit * (size_t)ns * RW * HDIM, ns * RW * HDIM * 4);
+  const __amdgpu_buffer_rsrc_t rls = make_rsrc(p.ws_lse + unit * (size_t)ns * RW, ns * RW * 4);
+  for (int idx = tid; idx < RW * CH; idx += 256) {
+    const int row = idx / CH, ch = idx - row * CH;
+    float M = ninf();
+#pragma unroll 4
+    for (int s = 0; s < ns; ++s)
+      M = fmaxf(M, __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
+                                                 rls, (s * RW + row) * 4, 0, kSc1)));
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    float den = 0.f;
+#pragma unroll 4
+    for (int s = 0; s < ns; ++s) {
+      const float l = __builtin_bit_cast(
+          float, __builtin_amdgcn_raw_buffer_load_b32(rls, (s * RW + row) * 4, 0, kSc1));
+      const f32x4 x = __builtin_bit_cast(
+          f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, ((s * RW + row) * HDIM + 4 * ch) * 4, 0,
+                                                       kSc1));
+      const float w = M == ninf() ? 0.f : __builtin_amdgcn_exp2f(l - M);
+      den += w;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[j] = __builtin_fmaf(w, x[j], acc[j]);
+    }
+    const float inv = den > 0.f ? 1.0f / den : 0.f;
+    tx4 out;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) out[j] = (T)(acc[j] * inv);
+    buf_store8(ro, row * (2 * HDIM) + 8 * ch, __builtin_bit_cast(f16x4, out));
+    if (lse_out && ch == 0 && row0 + row < p.rows)
+      lse_out[row] = den > 0.f ? (M + __builtin_log2f(den)) * 0.6931471805599453f : ninf();
+  }
+}
+
+template <class T, int HDIM, int NB>
+__global__ __launch_bounds__(256, 1) void fa_decode_kernel(DecodeParams p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int ROW = 2 * HDIM;      // bytes per Q/K/V/O row
+  constexpr int NTQ = HDIM / 32;     // 32-wide k-steps of QK^T
+  constexpr int NE = HDIM / 16;      // 16-wide d-blocks of O
+  constexpr int RW = 16 * NB;        // query rows per workgroup
+  constexpr int RPW = 512 / HDIM;    // V rows one load instruction of a wave covers
+  constexpr int NPASS = 64 / RPW;    // V load instructions per tile
+  constexpr int EW = NE / 4;         // d-blocks each wave finishes in the in-CU merge
+  // the next tile's K is issued right after QK^T; with 64 rows at head_dim 128
+  // the scores and the next K do not fit the register file together (scratch),
+  // so there it is issued once the scores are dead (P built)
+  constexpr bool kEarlyK = !(NB == 4 && HDIM == 128);
+  constexpr bool kQLds = NB == 4 && HDIM == 128;
+  typedef typename Elem<T>::x8 tx8;
+  typedef typename Elem<T>::x4 tx4;
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r16 = lane & 15, g = lane >> 4;
+  const int sg = ((g & 1) << 1) | (g >> 1);
+
+  // workgroup -> (batch, kv head, row group, piece)
+  const int ns = p.num_splits;
+  const unsigned unit = blockIdx.x / (unsigned)ns;
+  const int piece = (int)(blockIdx.x - unit * (unsigned)ns);
+  const int rg = (int)(unit % (unsigned)p.rgroups);
+  const unsigned bhk = unit / (unsigned)p.rgroups;  // b * Hkv + hkv
+  const int b = (int)(bhk / (unsigned)p.hkv), hk = (int)(bhk - (unsigned)b * p.hkv);
+  int len = p.kv_lens ? p.kv_lens[b] : p.cap;
+  len = __builtin_amdgcn_readfirstlane(min(max(len, 0), p.cap));
+  const int ntiles = (len + 63) >> 6;
+  const int t0 = (int)((long long)ntiles * piece / ns);
+  const int t1 = (int)((long long)ntiles * (piece + 1) / ns);
+
+  const int row0 = rg * RW;  // first row of this group among the kv head's rows
+  const size_t qrow = ((size_t)b * p.hq + (size_t)hk * p.group) * p.sq;  // [B*Hq*Sq] row of r = 0
+  const int nrows = max(0, min(RW, p.rows - row0));
+  const char* qb = static_cast<const char*>(p.q) + (qrow + row0) * ROW;
+  char* ob = static_cast<char*>(p.o) + (qrow + row0) * ROW;
+  const size_t kvoff = (size_t)bhk * (size_t)p.cap * ROW;
+  const __amdgpu_buffer_rsrc_t rq = make_rsrc(qb, nrows * ROW);
+  const __amdgpu_buffer_rsrc_t ro = make_rsrc(ob, nrows * ROW);
+  const __amdgpu_buffer_rsrc_t rk = make_rsrc(static_cast<const char*>(p.k) + kvoff, len * ROW);
+  const __amdgpu_buffer_rsrc_t rv = make_rsrc(static_cast<const char*>(p.v) + kvoff, len * ROW);
+
+  // Q fragments (B operand): qf[nb][t] = Q[16 nb + r16][32 t + 8 g .. +7]; rows
+  // past the group's last read as zeros.  Held in registers, except with 64
+  // rows at head_dim 128 (kQLds: the register file cannot hold them beside
+  // the O accumulator and both prefetches): there wave nb parks block nb's
+  // fragments lane-linearly behind the V images and every wave re-reads them
+  // per tile.
+  tx8 qf[kQLds ? 1 : NB][NTQ];
+  char* qimg = smem + kDecodeVBytes;
+  if constexpr (kQLds) {
+#pragma unroll
+    for (int t = 0; t < NTQ; ++t)
+      *reinterpret_cast<u32x4*>(qimg + ((wave * NTQ + t) * 64 + lane) * 16) = __builtin_bit_cast(
+          u32x4, buf_load16(rq, (16 * wave + r16) * ROW + (4 * t + g) * 16));
+    __syncthreads();
+  } else {
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+      for (int t = 0; t < NTQ; ++t)
+        qf[nb][t] = __builtin_bit_cast(tx8, buf_load16(rq, (16 * nb + r16) * ROW + (4 * t + g) * 16));
+  }
+  auto qfrag = [&](int nb, int t) -> tx8 {
+    if constexpr (kQLds)
+      return *reinterpret_cast<const tx8*>(qimg + ((nb * NTQ + t) * 64 + lane) * 16);
+    else
+      return qf[nb][t];
+  };
+
+  // first key a row does not see
+  int lim[NB];
+#pragma unroll
+  for (int nb = 0; nb < NB; ++nb) {
+    const int r = row0 + 16 * nb + r16;
+    lim[nb] = p.causal ? len - p.sq + 1 + r % p.sq : len;
+  }
+  const int mask_from = p.causal ? len - p.sq + 1 : len;  // tiles ending past it need the mask
+
+  // K: A-operand row r16 of 16-key block cb is key 16 cb + sigma(r16), so the
+  // S^T accumulator of lane (g, r16) holds keys 16 cb + 4 sg + i (the order
+  // the transposed V reads deliver)
+  const unsigned krow = 4 * ((((r16 >> 2) & 1) << 1) | (r16 >> 3)) + (r16 & 3);
+  const unsigned kvo = krow * ROW + g * 16;
+  // V staging (conflict-free writes into image A) and transposed reads
+  const int vrl = HDIM == 128 ? 2 * ((lane >> 5) & 1) + ((lane >> 2) & 1)
+                              : 2 * ((lane >> 4) & 3) + ((lane >> 2) & 1);
+  const int vch = HDIM == 128 ? 4 * ((lane >> 3) & 3) + (lane & 3) : 4 * ((lane >> 3) & 1) + (lane & 3);
+  const unsigned vvo = vrl * ROW + vch * 16;
+  char* vimg = smem + 16384 * wave;
+  int vaddr[2];
+  {
+    const int qq = r16 >> 2, pp = r16 & 3;
+#pragma unroll
+    for (int ep = 0; ep < 2; ++ep)
+      vaddr[ep] = 2048 * (sg >> 1) + 64 * (4 * (sg & 1) + qq) + 16 * ((2 * ep + (pp >> 1)) ^ sg) +
+                  8 * (pp & 1);
+  }
+
+  f32x4 acc[NB][NE], lacc[NB];
+  float m[NB];
+#pragma unroll
+  for (int nb = 0; nb < NB; ++nb) {
+#pragma unroll
+    for (int e = 0; e < NE; ++e) acc[nb][e] = f32x4{};
+    lacc[nb] = f32x4{};
+    m[nb] = ninf();
+  }
+
+  tx8 kf[4][NTQ];
+  u32x4 vr[NPASS];
+  // tile `tl`'s loads; a tile past the piece is addressed past the
+  // descriptor's range (row len): zeros, no memory traffic, no branch
+  auto load_k = [&](int tl) {
+    const unsigned base = (unsigned)min(64 * tl, len) * ROW + kvo;
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+      for (int t = 0; t < NTQ; ++t)
+        kf[cb][t] = __builtin_bit_cast(tx8, buf_load16(rk, (int)(base + 16 * cb * ROW + 64 * t)));
+  };
+  auto load_v = [&](int tl) {
+    const unsigned base = (unsigned)min(64 * tl, len) * ROW + vvo;
+#pragma unroll
+    for (int ps = 0; ps < NPASS; ++ps)
+      vr[ps] = __builtin_amdgcn_raw_buffer_load_b128(rv, (int)(base + ps * RPW * ROW), 0, 0);
+  };
+
+  int tile = t0 + wave;
+  const int tend = tile < t1 ? t1 : tile;  // a wave with no tile loads nothing
+  load_k(tile < tend ? tile : ntiles);
+  load_v(tile < tend ? tile : ntiles);
+  for (; tile < tend; tile += 4) {
+    const int nxt = tile + 4 < tend ? tile + 4 : ntiles;
+    // S^T = K . Q^T, then the online softmax in the exp2 domain, P rounded to
+    // T in the PV operand layout.  kEarlyK: every block's scores first, so the
+    // next K can be issued before the softmax; else block by block (16 score
+    // registers live at a time)
+    const int kv0 = 64 * tile;
+    const bool need_mask = kv0 + 64 > mask_from;
+    f32x4 s[NB][4];
+    tx8 pf[NB][2];
+    auto qk = [&](int nb) {
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+        for (int t = 0; t < NTQ; ++t)
+          s[nb][cb] = Elem<T>::mfma(kf[cb][t], qfrag(nb, t), t == 0 ? f32x4{} : s[nb][cb]);
+    };
+    auto softmax = [&](int nb) {
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb) s[nb][cb] *= p.c;
+      if (need_mask) {
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+            s[nb][cb][i] = kv0 + 16 * cb + 4 * sg + i < lim[nb] ? s[nb][cb][i] : ninf();
+      }
+      float mx = s[nb][0][0];
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+        for (int i = (cb == 0 ? 1 : 0); i < 4; ++i) mx = fmaxf(mx, s[nb][cb][i]);
+      mx = max_xor32(max_xor16(mx));
+      const float mnew = fmaxf(m[nb], mx);
+      const float msafe = mnew == ninf() ? 0.f : mnew;  // a row that has seen no key yet
+      const float alpha = __builtin_amdgcn_exp2f(m[nb] - msafe);
+      m[nb] = mnew;
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          pf[nb][cb >> 1][4 * (cb & 1) + i] = (T)__builtin_amdgcn_exp2f(s[nb][cb][i] - msafe);
+#pragma unroll
+      for (int e = 0; e < NE; ++e) acc[nb][e] *= alpha;
+      lacc[nb] *= alpha;
+    };
+    if constexpr (kEarlyK) {
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) qk(nb);
+      load_k(nxt);
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) softmax(nb);
+    } else {
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) {
+        qk(nb);
+        softmax(nb);
+        asm volatile("" : "+v"(pf[nb][0]), "+v"(pf[nb][1]));  // keep the blocks apart
+      }
+    }
+
+    if constexpr (!kEarlyK) load_k(nxt);
+    // V tile -> the wave's image, then the next tile's V loads
+#pragma unroll
+    for (int ps = 0; ps < NPASS; ++ps)
+      *reinterpret_cast<u32x4*>(vimg + lds_off(RPW * ps + vrl, vch)) = vr[ps];
+    load_v(nxt);
+
+    // O^T += V^T . P^T, l += ones . P^T (the same rounded P)
+    const tx8 ones = {(T)1.f, (T)1.f, (T)1.f, (T)1.f, (T)1.f, (T)1.f, (T)1.f, (T)1.f};
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+#pragma unroll
+      for (int e = 0; e < NE; ++e) {
+        const int base = 8192 * u + 512 * (e >> 1) + vaddr[e & 1];
+        const tx4 lo = __builtin_bit_cast(tx4, lds_read_tr(vimg, base));
+        const tx4 hi = __builtin_bit_cast(tx4, lds_read_tr(vimg, base + 4096));
+        const tx8 vf = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) acc[nb][e] = Elem<T>::mfma(vf, pf[nb][u], acc[nb][e]);
+      }
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) lacc[nb] = Elem<T>::mfma(ones, pf[nb][u], lacc[nb]);
+    }
+  }
+
+  // ---- merge the four waves' partials through LDS (wave order: deterministic)
+  constexpr int ML_OFF = 4 * NB * NE * 1024;
+  __syncthreads();  // every wave is done with its V image
+#pragma unroll
+  for (int nb = 0; nb < NB; ++nb) {
+#pragma unroll
+    for (int e = 0; e < NE; ++e)
+      *reinterpret_cast<f32x4*>(smem + (((wave * NB + nb) * NE + e) * 64 + lane) * 16) = acc[nb][e];
+    *reinterpret_cast<float2*>(smem + ML_OFF + ((wave * NB + nb) * 64 + lane) * 8) =
+        float2{m[nb], lacc[nb][0]};
+  }
+  __syncthreads();
+  const bool split = ns > 1;
+  const size_t slot = (size_t)unit * ns + piece;
+  const __amdgpu_buffer_rsrc_t rso =
+      make_rsrc(p.ws_o ? p.ws_o + slot * RW * HDIM : nullptr, split ? RW * HDIM * 4 : 0);
+  const __amdgpu_buffer_rsrc_t rsl =
+      make_rsrc(p.ws_lse ? p.ws_lse + slot * RW : nullptr, split ? RW * 4 : 0);
+  float* lse_out = p.lse ? p.lse + qrow + row0 : nullptr;
+#pragma unroll
+  for (int nb = 0; nb < NB; ++nb) {
+    float mw[4], lw[4];
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const float2 ml = *reinterpret_cast<const float2*>(smem + ML_OFF + ((w * NB + nb) * 64 + lane) * 8);
+      mw[w] = ml.x;
+      lw[w] = ml.y;
+    }
+    const float M = fmaxf(fmaxf(mw[0], mw[1]), fmaxf(mw[2], mw[3]));
+    float L = 0.f;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      mw[w] = M == ninf() ? 0.f : __builtin_amdgcn_exp2f(mw[w] - M);  // now the weight
+      L = __builtin_fmaf(mw[w], lw[w], L);
+    }
+    const float inv = L > 0.f ? 1.0f / L : 0.f;
+    const float lse2 = L > 0.f ? M + __builtin_log2f(L) : ninf();
+    const int row = 16 * nb + r16;
+#pragma unroll
+    for (int ee = 0; ee < EW; ++ee) {
+      const int e = wave * EW + ee;
+      f32x4 o = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int w = 0; w < 4; ++w) {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(smem + (((w * NB + nb) * NE + e) * 64 + lane) * 16);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = __builtin_fmaf(mw[w], a[j], o[j]);
+      }
+      o *= inv;
+      if (split) {
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), rso,
+                                               (row * HDIM + 16 * e + 4 * g) * 4, 0, 16);
+      } else {
+        tx4 out;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) out[j] = (T)o[j];
+        buf_store8(ro, row * ROW + (16 * e + 4 * g) * 2, __builtin_bit_cast(f16x4, out));
+      }
+    }
+    if (wave == 0 && g == 0) {
+      if (split)
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, lse2), rsl, row * 4, 0, 16);
+      else if (lse_out && row < nrows)
+        lse_out[row] = lse2 * 0.6931471805599453f;
+    }
+  }
+  if (!split) return;
+
+  // ---- hand the piece to the last arriver (sc1 stores, vmcnt(0) + barrier,
+  // one lane's agent-scope add, sc1 loads by the workgroup whose add came last)
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();  // every wave's stores done; the merge region is free
+  volatile int* last = reinterpret_cast<volatile int*>(smem);  // the one LDS array
+  if (tid == 0) {
+    const unsigned old =
+        __hip_atomic_fetch_add(p.ws_ctr + unit, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    *last = old == (unsigned)(ns - 1) ? 1 : 0;
+  }
+  __syncthreads();
+  if (!*last) return;
+  decode_merge_pieces<T, HDIM, NB>(p, unit, ns, ro, lse_out, row0, tid);
+  if (tid == 0) __hip_atomic_store(p.ws_ctr + unit, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+}  // namespace fa

@@ -48,6 +48,10 @@ EXPORTED_SYMBOLS = (
     "fa_fwd_bf16_ws",
     "fa_fwd_ws_bytes",
     "fa_fwd_split_pieces",
+    "fa_decode_f16",
+    "fa_decode_bf16",
+    "fa_decode_num_splits",
+    "fa_decode_ws_bytes",
     "fa_select_config",
     "fa_num_configs",
     "fa_config_info",
@@ -148,6 +152,14 @@ def load_library() -> ctypes.CDLL:
     lib.fa_fwd_ws_bytes.restype = ull
     lib.fa_fwd_split_pieces.argtypes = [i, i, i, i, i]
     lib.fa_fwd_split_pieces.restype = i
+    lib.fa_decode_f16.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, vp, i, i, vp, ull, vp]
+    lib.fa_decode_f16.restype = i
+    lib.fa_decode_bf16.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, vp, i, i, vp, ull, vp]
+    lib.fa_decode_bf16.restype = i
+    lib.fa_decode_num_splits.argtypes = [i, i, i, i, i, i]
+    lib.fa_decode_num_splits.restype = i
+    lib.fa_decode_ws_bytes.argtypes = [i, i, i, i, i, i, i]
+    lib.fa_decode_ws_bytes.restype = ull
     lib.fa_select_config.argtypes = [i, i, i, i]
     lib.fa_select_config.restype = i
     lib.fa_num_configs.argtypes = []
@@ -340,6 +352,107 @@ def flash_attention_fwd(q, k, v, causal: bool = False, out=None, config: Optiona
             rc = fn(*args, st)
     _check(rc)
     return out
+
+
+_DEC_NEED = {}  # (device, B, Hq, Hkv, Sq, cap, D, num_splits) -> (workspace bytes, pieces)
+
+
+def decode_num_splits(batch: int, heads_q: int, heads_kv: int, seqlen_q: int, kv_capacity: int,
+                      head_dim: int = HEAD_DIM, device=None) -> int:
+    """Pieces the decode entry's plan cuts each cache into on `device` (1: no split)."""
+    import torch
+
+    dev = torch.cuda.current_device() if device is None else torch.device(device).index
+    with torch.cuda.device(dev):
+        return load_library().fa_decode_num_splits(batch, heads_q, heads_kv, seqlen_q,
+                                                   kv_capacity, head_dim)
+
+
+def _check_decode(q, k_cache, v_cache, kv_lens, out):
+    """Raise FlashAttentionError unless q/out are contiguous [B,Hq,Sq,D] and
+    k_cache/v_cache contiguous [B,Hkv,cap,D] device tensors of one 16-bit dtype
+    and device with Hq % Hkv == 0, and kv_lens (if given) is int32 [B] there.
+    Dtypes, ranks and shapes are checked before where the tensors live, so
+    each rejection names its own cause whatever the device."""
+    import torch
+
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"q must be float16 or bfloat16, got {q.dtype}")
+    tensors = (("q", q), ("k_cache", k_cache), ("v_cache", v_cache), ("out", out))
+    for name, t in tensors:
+        if t.dtype != q.dtype:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be {q.dtype}, got {t.dtype}")
+        if t.dim() != 4:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be 4-D (BHSD)")
+        if not t.is_contiguous():
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be contiguous (BHSD)")
+    if out.shape != q.shape:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, "out must be [B,Hq,Sq,D] like q")
+    if k_cache.shape != v_cache.shape:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, "k_cache and v_cache must have one shape")
+    if k_cache.shape[0] != q.shape[0] or k_cache.shape[3] != q.shape[3]:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, "q and the caches must agree in batch and head_dim")
+    if k_cache.shape[1] == 0 or q.shape[1] % k_cache.shape[1] != 0:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE,
+                                  f"heads_q {q.shape[1]} is not a multiple of heads_kv {k_cache.shape[1]}")
+    if kv_lens is not None:
+        if kv_lens.dtype != torch.int32:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"kv_lens must be int32, got {kv_lens.dtype}")
+        if kv_lens.dim() != 1 or kv_lens.shape[0] != q.shape[0] or not kv_lens.is_contiguous():
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, "kv_lens must be a contiguous [B] tensor")
+    for name, t in tensors:
+        if not t.is_cuda:
+            raise FlashAttentionError(FA_ERR_NULL_POINTER, f"{name} must be a device tensor")
+        if t.device != q.device:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE,
+                                      f"{name} is on {t.device}, q on {q.device}: one device only")
+    if kv_lens is not None and (not kv_lens.is_cuda or kv_lens.device != q.device):
+        raise FlashAttentionError(FA_ERR_NULL_POINTER, f"kv_lens must be a tensor on {q.device}")
+
+
+def flash_attention_decode(q, k_cache, v_cache, kv_lens=None, causal: bool = True, out=None,
+                           return_lse: bool = False, num_splits: int = 0, stream=None):
+    """Decode attention over a K/V cache (fa_decode_f16 / fa_decode_bf16).
+
+    q: [B, Hq, Sq, D] (1 <= Sq <= 16); k_cache, v_cache: [B, Hkv, cap, D] with
+    Hq % Hkv == 0 (GQA / MQA); fp16 or bf16 contiguous device tensors of one
+    dtype, D = 128 or 64.  kv_lens: int32 [B] on the same device (None: every
+    length is cap); rows past a length are never read.  causal: bottom-right
+    aligned (query token t sees keys <= len - Sq + t).  num_splits: 0 = the
+    plan's choice (:func:`decode_num_splits`), > 0 forces that many key pieces.
+    Returns out, or (out, lse) with lse fp32 [B, Hq, Sq] (natural log) when
+    return_lse.  Enqueued on ``stream`` (default: torch's current stream); no
+    sync, graph-capturable; a split launch takes its workspace from the same
+    per-(device, stream) buffer as :func:`flash_attention_fwd`.
+    """
+    import torch
+
+    if out is None:
+        out = torch.empty_like(q)
+    _check_decode(q, k_cache, v_cache, kv_lens, out)
+    b, hq, sq, d = q.shape
+    hkv, cap = k_cache.shape[1], k_cache.shape[2]
+    lib = _lib or load_library()
+    dev = q.device.index
+    if stream is None:
+        st = torch._C._cuda_getCurrentRawStream(dev)
+    else:
+        st = stream if isinstance(stream, int) else stream.cuda_stream
+    lse = torch.empty((b, hq, sq), dtype=torch.float32, device=q.device) if return_lse else None
+    fn = lib.fa_decode_bf16 if q.dtype is torch.bfloat16 else lib.fa_decode_f16
+    with torch.cuda.device(dev):
+        key = (dev, b, hq, hkv, sq, cap, d, int(num_splits))
+        need = _DEC_NEED.get(key)
+        if need is None:
+            need = lib.fa_decode_ws_bytes(b, hq, hkv, sq, cap, d, int(num_splits))
+            _DEC_NEED[key] = need
+        ws = _workspace(need, dev, st) if need else None
+        rc = fn(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr(),
+                lse.data_ptr() if return_lse else None, b, hq, hkv, sq, cap, d,
+                kv_lens.data_ptr() if kv_lens is not None else None, int(bool(causal)),
+                int(num_splits), ws.data_ptr() if need else None, need, st)
+    _check(rc)
+    return (out, lse) if return_lse else out
 
 
 def splitkv_buffers(batch: int, heads: int, seq_len: int, num_splits: int, device="cuda"):

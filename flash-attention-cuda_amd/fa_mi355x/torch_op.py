@@ -3,6 +3,7 @@ rank 3: the wrapper that puts the kernel beside PyTorch SDPA on one box).
 
     import fa_mi355x.torch_op  # registers torch.ops.fa_mi355x.fwd
     o = torch.ops.fa_mi355x.fwd(q, k, v, causal=True)
+    o = torch.ops.fa_mi355x.decode(q, k_cache, v_cache, kv_lens, causal=True)
 
 ``q, k, v``: fp16 or bf16 ``[B, H, S, D]`` (D = 128 or 64) tensors on the GPU (BHSD, the
 reference layout, flash_attention.cu:119-122); returns a new tensor of the same shape and dtype.
@@ -22,7 +23,7 @@ from __future__ import annotations
 
 import torch
 
-from . import flash_attention_fwd
+from . import flash_attention_decode, flash_attention_fwd
 
 OP_NAME = "fa_mi355x::fwd"
 
@@ -58,3 +59,38 @@ _LIB.impl("fwd", _fwd_cpu, "CPU")
 torch.library.register_fake(OP_NAME, _fwd_fake, lib=_LIB)
 
 fwd = torch.ops.fa_mi355x.fwd
+
+# decode(q [B,Hq,Sq,D], k_cache / v_cache [B,Hkv,cap,D], kv_lens int32 [B] or
+# None): fa_mi355x.flash_attention_decode behind the same kind of registration.
+# k_cache and v_cache must be contiguous (FlashAttentionError otherwise).
+DECODE_OP_NAME = "fa_mi355x::decode"
+_LIB.define("decode(Tensor q, Tensor k_cache, Tensor v_cache, Tensor? kv_lens=None, "
+            "bool causal=True) -> Tensor")
+
+
+def _decode_gpu(q, k_cache, v_cache, kv_lens=None, causal: bool = True) -> torch.Tensor:
+    _no_grad_needed(q, k_cache, v_cache)
+    # the caches are taken as they are: a strided view (a slice of a larger
+    # cache) raises instead of being copied, which would move the whole cache
+    # once more than the kernel does
+    return flash_attention_decode(q.contiguous(), k_cache, v_cache,
+                                  None if kv_lens is None else kv_lens.contiguous(), causal=causal)
+
+
+def _decode_cpu(q, k_cache, v_cache, kv_lens=None, causal: bool = True) -> torch.Tensor:
+    raise ValueError("fa_mi355x::decode needs GPU tensors (no CPU path)")
+
+
+def _decode_fake(q, k_cache, v_cache, kv_lens=None, causal: bool = True) -> torch.Tensor:
+    _no_grad_needed(q, k_cache, v_cache)
+    torch._check(q.dim() == 4 and q.shape[-1] in (64, 128), lambda: "expected [B, Hq, Sq, 64|128]")
+    torch._check(q.dtype in (torch.float16, torch.bfloat16), lambda: "expected fp16 or bf16")
+    return torch.empty_like(q, memory_format=torch.contiguous_format)
+
+
+_LIB.impl("decode", _decode_gpu, "CUDA")
+_LIB.impl("decode", torch.library.fallthrough_kernel, "Autograd")
+_LIB.impl("decode", _decode_cpu, "CPU")
+torch.library.register_fake(DECODE_OP_NAME, _decode_fake, lib=_LIB)
+
+decode = torch.ops.fa_mi355x.decode

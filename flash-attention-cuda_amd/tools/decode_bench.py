@@ -1,0 +1,229 @@
+#!/usr/bin/env python3
+"""Decode-attention benchmark: fa_mi355x.flash_attention_decode against PyTorch
+SDPA on the same inputs, alternated in one process.
+
+Per shape: us per call (device events around a batch of calls, warmed), the
+K/V bytes the algorithm needs (2 * B * Hkv * sum(len) * D * 2, from shapes)
+over that time, that as a share of the 6.29 TB/s copy rate, the plan's
+num_splits, the SDPA time, and host_us: the Python + ctypes time to enqueue one
+call (a row whose us is no more than host_us is bound by the host, not by the
+kernel), and graph_us: the same calls replayed from one captured HIP graph, i.e.
+without the host between them.  Rows with B <= 8 also time the forced
+alternatives of the split plan (CUs filled 1x, 2x, 4x).  Caches smaller than
+the 256-MiB Infinity Cache are rotated through enough copies (>= 512 MiB in
+all) that every call streams from HBM.
+
+    python3 tools/decode_bench.py [--out profiles/decode_bench.jsonl] [--quick]
+"""
+import argparse
+import json
+import math
+import os
+import sys
+
+import torch
+import torch.nn.functional as F
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+import fa_mi355x  # noqa: E402
+
+COPY_RATE = 6.29e12  # measured copy rate, bytes/s
+MAX_SPLITS = 64
+try:  # does this torch's SDPA take grouped K/V heads itself?
+    F.scaled_dot_product_attention(torch.zeros(1, 2, 1, 8), torch.zeros(1, 1, 2, 8),
+                                   torch.zeros(1, 1, 2, 8), enable_gqa=True)
+    HAS_GQA = True
+except TypeError:
+    HAS_GQA = False
+
+
+def shapes(quick):
+    rows = []
+    for b in (1, 8, 64):
+        for n in (2048, 8192, 32768):
+            rows.append(dict(name=f"base B={b} len={n}", b=b, hq=32, hkv=8, sq=1, d=128, lens=[n] * b))
+    rows.append(dict(name="long B=1 len=131072", b=1, hq=32, hkv=8, sq=1, d=128, lens=[131072]))
+    rows.append(dict(name="speculative Sq=4", b=8, hq=32, hkv=8, sq=4, d=128, lens=[8192] * 8))
+    rows.append(dict(name="MHA Hq=Hkv=32", b=8, hq=32, hkv=32, sq=1, d=128, lens=[8192] * 8))
+    rows.append(dict(name="head_dim 64", b=8, hq=32, hkv=8, sq=1, d=64, lens=[8192] * 8))
+    rows.append(dict(name="bf16", b=8, hq=32, hkv=8, sq=1, d=128, lens=[8192] * 8, bf16=True))
+    b = 16
+    rag = [max(1, round(math.exp(math.log(32768) * i / (b - 1)))) for i in range(b)]
+    rows.append(dict(name="ragged 1..32768", b=b, hq=32, hkv=8, sq=1, d=128, lens=rag))
+    return rows[:2] + rows[-1:] if quick else rows
+
+
+def fill_splits(units, cap, cus, fill):
+    """csrc/fa_decode.hip decode_plan with kDecodeFill = fill."""
+    if units >= cus:
+        return 1
+    return max(1, min(-(-cus * fill // units), max(1, cap // 256), MAX_SPLITS))
+
+
+def time_pair(fns, iters, rounds):
+    """Median us per call of each fn; fns alternate round by round."""
+    ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+           for _ in range(rounds)] for _ in fns]
+    for fn in fns:
+        for i in range(3):
+            fn(i)
+    torch.cuda.synchronize()
+    for r in range(rounds):
+        for j, fn in enumerate(fns):
+            ev[j][r][0].record()
+            for i in range(iters):
+                fn(r * iters + i)
+            ev[j][r][1].record()
+    torch.cuda.synchronize()
+    out = []
+    for j in range(len(fns)):
+        ts = sorted(a.elapsed_time(b) * 1e3 / iters for a, b in ev[j])
+        out.append(ts[len(ts) // 2])
+    return out
+
+
+def host_us(fn, iters):
+    """Host time per call: the enqueue loop alone, from an idle device, no sync inside."""
+    import time
+
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for i in range(iters):
+        fn(i)
+    t1 = time.perf_counter()
+    torch.cuda.synchronize()
+    return (t1 - t0) * 1e6 / iters
+
+
+def graph_us(q, ks, vs, tl, iters, rounds=7):
+    """Median us per call with the host out of the way: `iters` calls of the C
+    entry (the plan's split, a workspace of this function's own) captured into
+    one HIP graph, replayed `rounds` times between device events."""
+    lib = fa_mi355x.load_library()
+    b, hq, sq, d = q.shape
+    hkv, cap = ks[0].shape[1], ks[0].shape[2]
+    need = lib.fa_decode_ws_bytes(b, hq, hkv, sq, cap, d, 0)
+    ws = torch.zeros(max(need, 1), dtype=torch.uint8, device="cuda")
+    out = torch.empty_like(q)
+    fn = lib.fa_decode_bf16 if q.dtype is torch.bfloat16 else lib.fa_decode_f16
+
+    def enqueue(st):
+        for i in range(iters):
+            rc = fn(q.data_ptr(), ks[i % len(ks)].data_ptr(), vs[i % len(vs)].data_ptr(), out.data_ptr(),
+                    None, b, hq, hkv, sq, cap, d, tl.data_ptr() if tl is not None else None, 1, 0,
+                    ws.data_ptr() if need else None, need, st)
+            assert rc == 0, rc
+
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        enqueue(side.cuda_stream)  # first-launch set-up outside the capture
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        enqueue(torch.cuda.current_stream().cuda_stream)
+    graph.replay()
+    torch.cuda.synchronize()
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+          for _ in range(rounds)]
+    for e0, e1 in ev:
+        e0.record()
+        graph.replay()
+        e1.record()
+    torch.cuda.synchronize()
+    ts = sorted(e0.elapsed_time(e1) * 1e3 / iters for e0, e1 in ev)
+    return ts[len(ts) // 2]
+
+
+def run(row, cus):
+    dt = torch.bfloat16 if row.get("bf16") else torch.float16
+    b, hq, hkv, sq, d = row["b"], row["hq"], row["hkv"], row["sq"], row["d"]
+    lens = row["lens"]
+    cap = max(lens)
+    ragged = min(lens) != cap
+    kv_bytes = 2 * hkv * sum(lens) * d * 2
+    alloc = 2 * b * hkv * cap * d * 2
+    copies = max(1, min(32, -(-(512 << 20) // alloc)))
+    gen = torch.Generator(device="cuda").manual_seed(1)
+
+    def rnd(*shape):
+        return (torch.rand(shape, generator=gen, device="cuda", dtype=torch.float32) * 2 - 1).to(dt)
+
+    ks = [rnd(b, hkv, cap, d) for _ in range(copies)]
+    vs = [rnd(b, hkv, cap, d) for _ in range(copies)]
+    q = rnd(b, hq, sq, d)
+    tl = torch.tensor(lens, dtype=torch.int32, device="cuda") if ragged else None
+    g = hq // hkv
+    mask = None
+    if ragged or sq > 1:  # bottom-right causal and per-batch lengths as an SDPA mask
+        key = torch.arange(cap, device="cuda")[None, None, :]
+        lim = torch.tensor(lens, device="cuda")[:, None, None] - sq + 1 + \
+            torch.arange(sq, device="cuda")[None, :, None]
+        mask = (key < lim)[:, None]
+    if not HAS_GQA and g > 1:
+        kx = [k.repeat_interleave(g, 1) for k in ks]
+        vx = [v.repeat_interleave(g, 1) for v in vs]
+
+    def dec(ns):
+        return lambda i: fa_mi355x.flash_attention_decode(q, ks[i % copies], vs[i % copies], tl,
+                                                          causal=True, num_splits=ns)
+
+    def sdpa(i):
+        if HAS_GQA:
+            return F.scaled_dot_product_attention(q, ks[i % copies], vs[i % copies], attn_mask=mask,
+                                                  enable_gqa=g > 1)
+        if g > 1:
+            return F.scaled_dot_product_attention(q, kx[i % copies], vx[i % copies], attn_mask=mask)
+        return F.scaled_dot_product_attention(q, ks[i % copies], vs[i % copies], attn_mask=mask)
+
+    # correctness of what is timed (SDPA is the comparison of record here)
+    err = float((dec(0)(0).float() - sdpa(0).float()).abs().max())
+    plan = fa_mi355x.decode_num_splits(b, hq, hkv, sq, cap, d)
+    iters = 20 if kv_bytes < (1 << 30) else 5
+    t_dec, t_sdpa = time_pair([dec(0), sdpa], iters, 7)
+    rec = dict(name=row["name"], batch=b, heads_q=hq, heads_kv=hkv, seqlen_q=sq, head_dim=d,
+               dtype=str(dt).split(".")[-1], kv_len_max=cap, kv_len_sum=sum(lens), copies=copies,
+               num_splits=plan, us=round(t_dec, 2), kv_bytes=kv_bytes,
+               gb_per_s=round(kv_bytes / t_dec / 1e3, 1),
+               share_of_copy_rate=round(kv_bytes / (t_dec * 1e-6) / COPY_RATE, 4),
+               sdpa_us=round(t_sdpa, 2), sdpa_over_decode=round(t_sdpa / t_dec, 2),
+               sdpa_gqa="enable_gqa" if HAS_GQA else "kv_expanded", max_abs_diff_vs_sdpa=err,
+               host_us=round(host_us(dec(0), iters), 2),
+               graph_us=round(graph_us(q, ks, vs, tl, iters), 2))
+    rec["graph_gb_per_s"] = round(kv_bytes / rec["graph_us"] / 1e3, 1)
+    rec["graph_share_of_copy_rate"] = round(kv_bytes / (rec["graph_us"] * 1e-6) / COPY_RATE, 4)
+    if b <= 8:
+        rows_ = g * sq
+        rw = 16 if rows_ <= 16 else (32 if rows_ <= 32 else 64)
+        units = b * hkv * -(-rows_ // rw)
+        alts = sorted({fill_splits(units, cap, cus, f) for f in (1, 2, 4)})
+        names = {f"fill_{f}x": fill_splits(units, cap, cus, f) for f in (1, 2, 4)}
+        ts = time_pair([dec(ns) for ns in alts], iters, 7)
+        by_ns = dict(zip(alts, ts))
+        rec["plan_alternatives"] = {k: dict(num_splits=ns, us=round(by_ns[ns], 2)) for k, ns in names.items()}
+    return rec
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..",
+                                                  "profiles", "decode_bench.jsonl"))
+    ap.add_argument("--quick", action="store_true", help="three rows only")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("decode_bench.py needs a GPU")
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        for row in shapes(args.quick):
+            rec = run(row, cus)
+            rec["cus"] = cus
+            f.write(json.dumps(rec) + "\n")
+            f.flush()
+            print(json.dumps(rec), flush=True)
+            torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()

@@ -157,6 +157,56 @@ int fa_fwd_bf16_ws(const void* q, const void* k, const void* v, void* o,
                    int piece_tiles, void* workspace, unsigned long long ws_bytes,
                    void* hip_stream);
 
+/* Decode attention over a K/V cache: a few query tokens per head (1 for
+ * decoding, up to 16 for speculative / multi-token decoding) against a long
+ * cache whose length differs per batch element, with grouped K/V heads (GQA /
+ * MQA: heads_q % heads_kv == 0, any integer group size).
+ *   O[b,hq,t,:] = softmax(Q[b,hq,t,:] . K[b,hkv,0:len_b,:]^T / sqrt(D) [+ mask])
+ *                 . V[b,hkv,0:len_b,:],          hkv = hq / (heads_q / heads_kv)
+ *   q, o   [batch][heads_q][seqlen_q][head_dim]           (1 <= seqlen_q <= 16)
+ *   k, v   [batch][heads_kv][kv_capacity][head_dim]       (the cache, BHSD)
+ *   kv_lens DEVICE int32[batch], len_b <= kv_capacity (clamped to it); NULL =
+ *           every len_b is kv_capacity.  Read by the kernel, so the call stays
+ *           sync-free and a captured graph follows lengths changed between
+ *           replays.  Rows past len_b are never read (they may hold anything).
+ *   causal = 1: bottom-right aligned, query token t sees keys <= len_b -
+ *           seqlen_q + t; 0: all len_b keys.  A row that sees no key writes
+ *           zeros and LSE = -inf.
+ *   lse    optional fp32 [batch][heads_q][seqlen_q]: natural log of the sum of
+ *           exp of the scaled scores; may be NULL.
+ * The heads_q / heads_kv * seqlen_q query rows that share a K/V head are one
+ * workgroup's rows (64 at most, else several row groups), so each K/V byte is
+ * read once per row group.  The key range [0, len_b) is cut into num_splits
+ * pieces inside the kernel and the pieces are merged in the same launch, in
+ * piece order (bit-deterministic):
+ *   num_splits = 0: the plan's choice, fa_decode_num_splits() (from the shape
+ *     and the current device's CU count; 256 if the query fails);
+ *   num_splits > 0: that many; more than the plan's upper cap (64) is
+ *     FA_ERR_BAD_CONFIG.
+ * Workspace: same contract as fa_fwd_f16_ws -- the first 64 KB are counters,
+ * zero before the first use, and every launch returns the counters it used to
+ * zero, so one buffer of the largest size needed serves any sequence of decode
+ * AND forward shapes on ONE stream.  fa_decode_ws_bytes() is what the call
+ * needs (num_splits as passed to the call; 0 when it does not split: no
+ * workspace is touched then and NULL is accepted).  FA_ERR_WORKSPACE if the
+ * call splits and workspace is NULL, short or not 16-byte aligned.
+ * All argument errors are returned before any launch.  Empty problems (batch
+ * or heads of 0) return FA_OK without launching; kv_capacity == 0 with rows
+ * present only fills O with zeros and LSE with -inf.  fa_decode_* are not
+ * tile configs: fa_config_info() does not list them. */
+int fa_decode_f16(const void* q, const void* k, const void* v, void* o, float* lse,
+                  int batch, int heads_q, int heads_kv, int seqlen_q, int kv_capacity,
+                  int head_dim, const int* kv_lens, int causal, int num_splits,
+                  void* workspace, unsigned long long ws_bytes, void* hip_stream);
+int fa_decode_bf16(const void* q, const void* k, const void* v, void* o, float* lse,
+                   int batch, int heads_q, int heads_kv, int seqlen_q, int kv_capacity,
+                   int head_dim, const int* kv_lens, int causal, int num_splits,
+                   void* workspace, unsigned long long ws_bytes, void* hip_stream);
+int fa_decode_num_splits(int batch, int heads_q, int heads_kv, int seqlen_q,
+                         int kv_capacity, int head_dim);
+unsigned long long fa_decode_ws_bytes(int batch, int heads_q, int heads_kv, int seqlen_q,
+                                      int kv_capacity, int head_dim, int num_splits);
+
 /* The dispatcher's decision (ref tier table :620-661): config id used by
  * fa_fwd_f16 for this shape.  The _ws entries may run the causal split tier
  * instead: check fa_fwd_split_pieces() first (> 0: the split tier runs with

@@ -1,0 +1,192 @@
+"""CPU tests of the decode-attention entries (fa_decode_f16 / fa_decode_bf16,
+fa_decode_num_splits, fa_decode_ws_bytes, fa_mi355x.flash_attention_decode,
+torch.ops.fa_mi355x.decode): exports, the argument checks (all returned before
+any launch, so fake pointers do), the split plan, the workspace size, the
+Python wrapper's tensor checks, the op's registration and the kernels'
+compile-time resource usage -- no kernel is launched (no GPU here)."""
+import ctypes
+import os
+import re
+import subprocess
+
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SYMBOLS = ("fa_decode_f16", "fa_decode_bf16", "fa_decode_num_splits", "fa_decode_ws_bytes")
+MAX_SPLITS = 64  # the plan's upper cap (csrc/fa_decode.hip kDecodeMaxSplits)
+
+
+def _fa():
+    import fa_mi355x
+
+    return fa_mi355x
+
+
+def test_library_exports_decode_symbols():
+    fa = _fa()
+    out = subprocess.run(["nm", "-D", "--defined-only", fa.library_path()], capture_output=True,
+                         text=True, check=True).stdout
+    syms = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    for s in SYMBOLS:
+        assert s in syms and s in fa.EXPORTED_SYMBOLS, s
+    header = open(os.path.join(ROOT, "include", "fa_mi355x.h")).read()
+    for s in SYMBOLS:
+        assert re.search(r"\b%s\s*\(" % s, header), s
+
+
+def _call(fn, q, k, v, o, b, hq, hkv, sq, cap, d, lens=None, causal=1, ns=0, ws=None, wsb=0):
+    return fn(q, k, v, o, None, b, hq, hkv, sq, cap, d, lens, causal, ns, ws, wsb, None)
+
+
+def test_argument_checks():
+    fa = _fa()
+    lib = fa.load_library()
+    p = ctypes.c_void_p(0x1000)
+    for fn in (lib.fa_decode_f16, lib.fa_decode_bf16):
+        for bad in range(4):  # each of q, k, v, o NULL in turn
+            ptrs = [None if i == bad else p for i in range(4)]
+            assert _call(fn, *ptrs, 1, 8, 2, 1, 1024, 128) == fa.FA_ERR_NULL_POINTER
+        for d in (0, 32, 96, 256):
+            assert _call(fn, p, p, p, p, 1, 8, 2, 1, 1024, d) == fa.FA_ERR_UNSUPPORTED_HEAD_DIM
+        for hq, hkv in ((8, 3), (7, 2), (4, 8)):
+            assert _call(fn, p, p, p, p, 1, hq, hkv, 1, 1024, 128) == fa.FA_ERR_BAD_SHAPE
+        for sq in (0, 17, -1):
+            assert _call(fn, p, p, p, p, 1, 8, 2, sq, 1024, 128) == fa.FA_ERR_BAD_SHAPE
+        assert _call(fn, p, p, p, p, -1, 8, 2, 1, 1024, 128) == fa.FA_ERR_BAD_SHAPE
+        assert _call(fn, p, p, p, p, 1, -8, 2, 1, 1024, 128) == fa.FA_ERR_BAD_SHAPE
+        assert _call(fn, p, p, p, p, 1, 8, -2, 1, 1024, 128) == fa.FA_ERR_BAD_SHAPE
+        assert _call(fn, p, p, p, p, 1, 8, 2, 1, -5, 128) == fa.FA_ERR_BAD_SHAPE
+        # cap * 2 * head_dim past INT_MAX
+        assert _call(fn, p, p, p, p, 1, 8, 2, 1, 8388608, 128) == fa.FA_ERR_BAD_SHAPE
+        assert _call(fn, p, p, p, p, 1, 8, 2, 1, 16777216, 64) == fa.FA_ERR_BAD_SHAPE
+        # no kv_lens, causal, fewer cache rows than query tokens
+        assert _call(fn, p, p, p, p, 1, 8, 2, 4, 3, 128, None, 1) == fa.FA_ERR_BAD_SHAPE
+        # splitting needs a workspace: present, long enough, 16-byte aligned
+        need = lib.fa_decode_ws_bytes(1, 8, 2, 1, 4096, 128, 4)
+        assert need > 65536
+        assert _call(fn, p, p, p, p, 1, 8, 2, 1, 4096, 128, ns=4) == fa.FA_ERR_WORKSPACE
+        assert _call(fn, p, p, p, p, 1, 8, 2, 1, 4096, 128, ns=4, ws=p, wsb=need - 1) == \
+            fa.FA_ERR_WORKSPACE
+        assert _call(fn, p, p, p, p, 1, 8, 2, 1, 4096, 128, ns=4, ws=ctypes.c_void_p(0x1008),
+                     wsb=need) == fa.FA_ERR_WORKSPACE
+        # more pieces than the cap
+        assert _call(fn, p, p, p, p, 1, 8, 2, 1, 4096, 128, ns=MAX_SPLITS + 1, ws=p,
+                     wsb=1 << 40) == fa.FA_ERR_BAD_CONFIG
+        # empty problems: nothing to do, nothing launched, no pointer looked at
+        assert _call(fn, None, None, None, None, 0, 8, 2, 1, 1024, 128) == fa.FA_OK
+        assert _call(fn, None, None, None, None, 1, 0, 0, 1, 1024, 128) == fa.FA_OK
+
+
+def test_split_plan():
+    """fa_decode_num_splits without a device: the default 256 CUs."""
+    lib = _fa().load_library()
+    ns = lib.fa_decode_num_splits
+    # units already fill (twice) the CUs: one piece
+    for b, hkv in ((64, 8), (512, 1), (16, 32)):
+        assert b * hkv >= 2 * 256
+        assert ns(b, 4 * hkv, hkv, 1, 32768, 128) == 1, (b, hkv)
+    assert ns(1, 32, 8, 1, 32768, 128) > 1
+    for cap in (1, 100, 255, 256, 257, 1000, 4096, 32768, 1 << 20):
+        for b, hq, hkv, sq in ((1, 32, 8, 1), (1, 8, 1, 1), (8, 32, 8, 4), (1, 28, 4, 16), (3, 7, 7, 2)):
+            for d in (64, 128):
+                n = ns(b, hq, hkv, sq, cap, d)
+                assert 1 <= n <= MAX_SPLITS, (b, hq, hkv, sq, cap, d, n)
+                assert n <= -(-cap // 256), (b, hq, hkv, sq, cap, d, n)
+    # the longest cache of the fewest units still stays under the cap
+    assert ns(1, 1, 1, 1, 8388607, 128) == MAX_SPLITS
+
+
+def test_workspace_bytes():
+    lib = _fa().load_library()
+    wsb = lib.fa_decode_ws_bytes
+    # the plan does not split: no workspace
+    assert lib.fa_decode_num_splits(64, 32, 8, 1, 32768, 128) == 1
+    assert wsb(64, 32, 8, 1, 32768, 128, 0) == 0
+    assert wsb(1, 32, 8, 1, 100, 128, 0) == 0      # too short to split
+    assert wsb(1, 32, 8, 1, 32768, 128, 1) == 0    # one forced piece
+    for shape in ((1, 32, 8, 1, 32768, 128), (8, 32, 8, 4, 8192, 128), (1, 28, 4, 3, 4096, 64),
+                  (2, 16, 1, 16, 2048, 128)):
+        assert lib.fa_decode_num_splits(*shape) > 1, shape
+        need = wsb(*shape, 0)
+        assert need >= 65536 and need % 256 == 0, shape
+        assert need == wsb(*shape, lib.fa_decode_num_splits(*shape))
+        prev = 0
+        for forced in range(2, MAX_SPLITS + 1):
+            n = wsb(*shape, forced)
+            assert n >= 65536 and n % 256 == 0 and n > prev, (shape, forced)
+            prev = n
+
+
+def _t(shape, dtype=torch.float16, device="meta"):
+    return torch.empty(shape, dtype=dtype, device=device)
+
+
+def test_python_wrapper_rejects_bad_tensors():
+    """Each rejection is raised by its own check: dtypes, ranks and shapes are
+    checked before the device, so the message names the property that is wrong
+    even though none of these tensors is on a GPU (a host kv_lens beside
+    device tensors: tests/test_decode_gpu.py)."""
+    fa = _fa()
+    q, k = (2, 8, 1, 128), (2, 2, 512, 128)
+    bad = [
+        ("q must be float16 or bfloat16",
+         _t(q, torch.float32), _t(k, torch.float32), _t(k, torch.float32), None),
+        ("q must be a device tensor", _t(q, device="cpu"), _t(k, device="cpu"), _t(k, device="cpu"), None),
+        ("q must be a device tensor", _t(q), _t(k), _t(k), None),
+        ("k_cache and v_cache must have one shape", _t(q), _t(k), _t((2, 2, 256, 128)), None),
+        ("kv_lens must be int32", _t(q), _t(k), _t(k), torch.zeros(2, dtype=torch.int64)),
+        ("kv_lens must be a contiguous \\[B\\] tensor", _t(q), _t(k), _t(k),
+         torch.zeros(3, dtype=torch.int32)),
+        ("heads_q 7 is not a multiple of heads_kv 2", _t((2, 7, 1, 128)), _t(k), _t(k), None),
+        ("k_cache must be torch.float16", _t(q), _t(k, torch.bfloat16), _t(k), None),
+        ("agree in batch and head_dim", _t(q), _t((3, 2, 512, 128)), _t((3, 2, 512, 128)), None),
+        ("agree in batch and head_dim", _t(q), _t((2, 2, 512, 64)), _t((2, 2, 512, 64)), None),
+        ("q must be 4-D", _t((8, 1, 128)), _t(k), _t(k), None),
+        ("v_cache must be contiguous", _t(q), _t(k), _t((2, 2, 128, 512)).transpose(2, 3), None),
+    ]
+    for msg, tq, tk, tv, lens in bad:
+        with pytest.raises(fa.FlashAttentionError, match=msg):
+            fa.flash_attention_decode(tq, tk, tv, lens, out=torch.empty_like(tq))
+
+
+def test_decode_op_registered_with_fake_impl():
+    import fa_mi355x.torch_op as top
+
+    assert top.DECODE_OP_NAME == "fa_mi355x::decode"
+    schema = str(torch.ops.fa_mi355x.decode.default._schema)
+    assert "Tensor? kv_lens=None" in schema and "bool causal=True" in schema, schema
+    for dtype in (torch.float16, torch.bfloat16):
+        q = _t((2, 28, 3, 128), dtype)
+        k = _t((2, 4, 4096, 128), dtype)
+        lens = torch.empty(2, dtype=torch.int32, device="meta")
+        out = torch.ops.fa_mi355x.decode(q, k, k, lens, True)
+        assert out.shape == q.shape and out.dtype == dtype and out.device.type == "meta"
+        assert torch.ops.fa_mi355x.decode(q, k, k).shape == q.shape
+    # no CPU path, forward only
+    c = torch.zeros((1, 2, 1, 128), dtype=torch.float16)
+    with pytest.raises(ValueError):
+        torch.ops.fa_mi355x.decode(c, c, c)
+    with pytest.raises(RuntimeError):
+        torch.ops.fa_mi355x.decode(_t((1, 2, 1, 128)).requires_grad_(), _t((1, 2, 8, 128)),
+                                   _t((1, 2, 8, 128)))
+
+
+@pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
+def test_no_decode_kernel_uses_scratch():
+    """Twin of test_capi.test_no_kernel_uses_scratch for csrc/fa_decode.hip:
+    every decode kernel (2 dtypes x 2 head dims x 1 / 2 / 4 row blocks) keeps
+    its state in registers."""
+    pkg = os.path.join(ROOT, "flash-attention-cuda_amd")
+    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-honor-nans",
+           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(pkg, "csrc"), "-c",
+           os.path.join(pkg, "csrc", "fa_decode.hip"), "-o", os.devnull,
+           "-Rpass-analysis=kernel-resource-usage"]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    names = re.findall(r"Function Name: (\S+)", out.stderr)
+    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", out.stderr)]
+    assert len(names) == 12 and len(names) == len(scratch), (len(names), len(scratch))
+    assert all("fa_decode_kernel" in n for n in names), names
+    spills = {n: s for n, s in zip(names, scratch) if s}
+    assert not spills, spills
