@@ -58,6 +58,19 @@ struct DecodeParams {
   float* ws_o;         // [unit][piece][16 NB][D] normalised partial O
 };
 
+// The paged twin (fa_decode_paged.hip): the cache is a pool of pages
+// [num_pages][Hkv][page_size][D] plus a block table; `k` / `v` are the pools
+// and `cap` the logical capacity max_pages * page_size.
+struct DecodePagedParams : DecodeParams {
+  const int* table;          // device int32[B][max_pages]: pool page of keys [j*page_size, +page_size)
+  int max_pages;             // table row length
+  int num_pages;             // pool pages: an id outside [0, num_pages) reads as zero rows
+  int tpp;                   // 64-key tiles per page (page_size / 64)
+  int adv_pages, adv_tiles;  // 4 / tpp, 4 % tpp: a wave's step of four tiles in (page, tile in page)
+  unsigned long long page_bytes;  // Hkv * page_size * row bytes
+  unsigned long long head_bytes;  // page_size * row bytes
+};
+
 constexpr int kDecodeVBytes = 4 * 64 * 256;  // four wave-private V images
 template <int HDIM, int NB>
 constexpr int decode_lds_bytes() {
@@ -110,8 +123,16 @@ __device__ __forceinline__ void decode_merge_pieces(const DecodeParams& p, size_
   }
 }
 
-template <class T, int HDIM, int NB>
-__global__ __launch_bounds__(256, 1) void fa_decode_kernel(DecodeParams p) {
+// PAGED = false: P = DecodeParams, the contiguous cache (fa_decode.hip).
+// PAGED = true: P = DecodePagedParams (fa_decode_paged.hip): the
+// decomposition, the order of operations and the merges are the same, only
+// where a tile's 64 rows start and how many of them are live comes from the
+// block table (tile_at() below), so the result is bit-identical to the
+// contiguous kernel on the gathered cache.  Code for PAGED sits under
+// `if constexpr`: the PAGED = false instantiations compile to the
+// instruction streams they had before the parameter existed.
+template <class T, int HDIM, int NB, bool PAGED = false, class P = DecodeParams>
+__global__ __launch_bounds__(256, 1) void fa_decode_kernel(P p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int ROW = 2 * HDIM;      // bytes per Q/K/V/O row
   constexpr int NTQ = HDIM / 32;     // 32-wide k-steps of QK^T
@@ -151,11 +172,15 @@ __global__ __launch_bounds__(256, 1) void fa_decode_kernel(DecodeParams p) {
   const int nrows = max(0, min(RW, p.rows - row0));
   const char* qb = static_cast<const char*>(p.q) + (qrow + row0) * ROW;
   char* ob = static_cast<char*>(p.o) + (qrow + row0) * ROW;
-  const size_t kvoff = (size_t)bhk * (size_t)p.cap * ROW;
+  const size_t kvoff = PAGED ? 0 : (size_t)bhk * (size_t)p.cap * ROW;
   const __amdgpu_buffer_rsrc_t rq = make_rsrc(qb, nrows * ROW);
   const __amdgpu_buffer_rsrc_t ro = make_rsrc(ob, nrows * ROW);
-  const __amdgpu_buffer_rsrc_t rk = make_rsrc(static_cast<const char*>(p.k) + kvoff, len * ROW);
-  const __amdgpu_buffer_rsrc_t rv = make_rsrc(static_cast<const char*>(p.v) + kvoff, len * ROW);
+  // contiguous: one descriptor per operand for the whole head.  Paged: one per
+  // tile, rebuilt by tile_at() before the tile's loads are issued
+  __amdgpu_buffer_rsrc_t rk =
+      make_rsrc(static_cast<const char*>(p.k) + kvoff, PAGED ? 0 : len * ROW);
+  __amdgpu_buffer_rsrc_t rv =
+      make_rsrc(static_cast<const char*>(p.v) + kvoff, PAGED ? 0 : len * ROW);
 
   // Q fragments (B operand): qf[nb][t] = Q[16 nb + r16][32 t + 8 g .. +7]; rows
   // past the group's last read as zeros.  Held in registers, except with 64
@@ -228,8 +253,14 @@ __global__ __launch_bounds__(256, 1) void fa_decode_kernel(DecodeParams p) {
   u32x4 vr[NPASS];
   // tile `tl`'s loads; a tile past the piece is addressed past the
   // descriptor's range (row len): zeros, no memory traffic, no branch
+  // (paged: the descriptors and `tofs` are the tile's own, tile_at(), and `tl` is unused)
+  [[maybe_unused]] unsigned tofs = 0;  // byte offset of the tile's rows in head hk's part of its page
   auto load_k = [&](int tl) {
-    const unsigned base = (unsigned)min(64 * tl, len) * ROW + kvo;
+    unsigned base;
+    if constexpr (PAGED)
+      base = tofs + kvo;
+    else
+      base = (unsigned)min(64 * tl, len) * ROW + kvo;
 #pragma unroll
     for (int cb = 0; cb < 4; ++cb)
 #pragma unroll
@@ -237,7 +268,11 @@ __global__ __launch_bounds__(256, 1) void fa_decode_kernel(DecodeParams p) {
         kf[cb][t] = __builtin_bit_cast(tx8, buf_load16(rk, (int)(base + 16 * cb * ROW + 64 * t)));
   };
   auto load_v = [&](int tl) {
-    const unsigned base = (unsigned)min(64 * tl, len) * ROW + vvo;
+    unsigned base;
+    if constexpr (PAGED)
+      base = tofs + vvo;
+    else
+      base = (unsigned)min(64 * tl, len) * ROW + vvo;
 #pragma unroll
     for (int ps = 0; ps < NPASS; ++ps)
       vr[ps] = __builtin_amdgcn_raw_buffer_load_b128(rv, (int)(base + ps * RPW * ROW), 0, 0);
@@ -245,10 +280,61 @@ __global__ __launch_bounds__(256, 1) void fa_decode_kernel(DecodeParams p) {
 
   int tile = t0 + wave;
   const int tend = tile < t1 ? t1 : tile;  // a wave with no tile loads nothing
+
+  // Paged: tile tl lies in the pool page table[b][tl / tpp], at 64-row block
+  // r = tl % tpp of head hk's part of it: tile_at() points the descriptors at
+  // that part, with a range that ends at the tile's last live row, and sets
+  // the loads' offset `tofs` to block r.  A wave's tiles are four apart, so
+  // (page index, block) advance by (adv_pages, adv_tiles) with one carry: no
+  // division in the loop.  T = the current tile, A = the next (tile + 4), B =
+  // the one after (tile + 8).  B's page id is fetched (a wave-uniform scalar
+  // load) while A's descriptors are built from the id fetched one iteration
+  // earlier, so kv_lens -> table -> K is a dependent chain only in the
+  // prologue.  Only entries of tiles below tend (pages holding a key below
+  // len) are read: a tile past the piece re-reads tile T's entry and gets a
+  // zero range.
+  [[maybe_unused]] int jT = 0, jA = 0, rA = 0, jB = 0, rB = 0, pgA = 0;
+  [[maybe_unused]] auto tile_at = [&](bool live, int tl, int pg, int r) {
+    if constexpr (PAGED) {
+      // a page id outside the pool: zero rows, the base stays inside the pool
+      const bool ok = (unsigned)pg < (unsigned)p.num_pages;
+      const int rows = live && ok ? 64 * r + min(len - 64 * tl, 64) : 0;
+      const size_t off = (size_t)(ok ? pg : 0) * p.page_bytes + (size_t)hk * p.head_bytes;
+      rk = make_rsrc(static_cast<const char*>(p.k) + off, rows * ROW);
+      rv = make_rsrc(static_cast<const char*>(p.v) + off, rows * ROW);
+      tofs = (unsigned)(64 * r) * ROW;
+    }
+  };
+  if constexpr (PAGED) {
+    typedef const __attribute__((address_space(4))) int* tab_t;  // scalar loads
+    const tab_t tab = (tab_t)(p.table + (size_t)b * p.max_pages);
+    int pg = 0, r = 0;
+    if (tile < tend) {
+      jT = tile / p.tpp;
+      r = tile - jT * p.tpp;
+      jA = jT + p.adv_pages, rA = r + p.adv_tiles;
+      if (rA >= p.tpp) rA -= p.tpp, ++jA;
+      jB = jA + p.adv_pages, rB = rA + p.adv_tiles;
+      if (rB >= p.tpp) rB -= p.tpp, ++jB;
+      pg = tab[jT];
+      pgA = tab[tile + 4 < tend ? jA : jT];
+    }
+    tile_at(tile < tend, tile, pg, r);
+  }
   load_k(tile < tend ? tile : ntiles);
   load_v(tile < tend ? tile : ntiles);
   for (; tile < tend; tile += 4) {
     const int nxt = tile + 4 < tend ? tile + 4 : ntiles;
+    if constexpr (PAGED) {
+      // this tile's loads are issued: the descriptors move on to the next tile
+      typedef const __attribute__((address_space(4))) int* tab_t;
+      const tab_t tab = (tab_t)(p.table + (size_t)b * p.max_pages);
+      const int pgB = tab[tile + 8 < tend ? jB : jT];
+      tile_at(tile + 4 < tend, tile + 4, pgA, rA);
+      jT = jA, jA = jB, rA = rB, pgA = pgB;
+      jB += p.adv_pages, rB += p.adv_tiles;
+      if (rB >= p.tpp) rB -= p.tpp, ++jB;
+    }
     // S^T = K . Q^T, then the online softmax in the exp2 domain, P rounded to
     // T in the PV operand layout.  kEarlyK: every block's scores first, so the
     // next K can be issued before the softmax; else block by block (16 score
@@ -333,6 +419,13 @@ __global__ __launch_bounds__(256, 1) void fa_decode_kernel(DecodeParams p) {
     }
   }
 
+  // The epilogue's lane indices.  Paged: derived again from the thread id
+  // here, not held across the loop (the 64-row head_dim-128 variant has no
+  // vector register to spare for them: scratch otherwise)
+  int etid = tid;
+  if constexpr (PAGED) asm volatile("" : "+v"(etid));
+  const int elane = etid & 63, er16 = elane & 15, eg = elane >> 4;
+
   // ---- merge the four waves' partials through LDS (wave order: deterministic)
   constexpr int ML_OFF = 4 * NB * NE * 1024;
   __syncthreads();  // every wave is done with its V image
@@ -340,8 +433,8 @@ __global__ __launch_bounds__(256, 1) void fa_decode_kernel(DecodeParams p) {
   for (int nb = 0; nb < NB; ++nb) {
 #pragma unroll
     for (int e = 0; e < NE; ++e)
-      *reinterpret_cast<f32x4*>(smem + (((wave * NB + nb) * NE + e) * 64 + lane) * 16) = acc[nb][e];
-    *reinterpret_cast<float2*>(smem + ML_OFF + ((wave * NB + nb) * 64 + lane) * 8) =
+      *reinterpret_cast<f32x4*>(smem + (((wave * NB + nb) * NE + e) * 64 + elane) * 16) = acc[nb][e];
+    *reinterpret_cast<float2*>(smem + ML_OFF + ((wave * NB + nb) * 64 + elane) * 8) =
         float2{m[nb], lacc[nb][0]};
   }
   __syncthreads();
@@ -357,7 +450,7 @@ __global__ __launch_bounds__(256, 1) void fa_decode_kernel(DecodeParams p) {
     float mw[4], lw[4];
 #pragma unroll
     for (int w = 0; w < 4; ++w) {
-      const float2 ml = *reinterpret_cast<const float2*>(smem + ML_OFF + ((w * NB + nb) * 64 + lane) * 8);
+      const float2 ml = *reinterpret_cast<const float2*>(smem + ML_OFF + ((w * NB + nb) * 64 + elane) * 8);
       mw[w] = ml.x;
       lw[w] = ml.y;
     }
@@ -370,29 +463,29 @@ __global__ __launch_bounds__(256, 1) void fa_decode_kernel(DecodeParams p) {
     }
     const float inv = L > 0.f ? 1.0f / L : 0.f;
     const float lse2 = L > 0.f ? M + __builtin_log2f(L) : ninf();
-    const int row = 16 * nb + r16;
+    const int row = 16 * nb + er16;
 #pragma unroll
     for (int ee = 0; ee < EW; ++ee) {
       const int e = wave * EW + ee;
       f32x4 o = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int w = 0; w < 4; ++w) {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(smem + (((w * NB + nb) * NE + e) * 64 + lane) * 16);
+        const f32x4 a = *reinterpret_cast<const f32x4*>(smem + (((w * NB + nb) * NE + e) * 64 + elane) * 16);
 #pragma unroll
         for (int j = 0; j < 4; ++j) o[j] = __builtin_fmaf(mw[w], a[j], o[j]);
       }
       o *= inv;
       if (split) {
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), rso,
-                                               (row * HDIM + 16 * e + 4 * g) * 4, 0, 16);
+                                               (row * HDIM + 16 * e + 4 * eg) * 4, 0, 16);
       } else {
         tx4 out;
 #pragma unroll
         for (int j = 0; j < 4; ++j) out[j] = (T)o[j];
-        buf_store8(ro, row * ROW + (16 * e + 4 * g) * 2, __builtin_bit_cast(f16x4, out));
+        buf_store8(ro, row * ROW + (16 * e + 4 * eg) * 2, __builtin_bit_cast(f16x4, out));
       }
     }
-    if (wave == 0 && g == 0) {
+    if (wave == 0 && eg == 0) {
       if (split)
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, lse2), rsl, row * 4, 0, 16);
       else if (lse_out && row < nrows)
@@ -406,15 +499,15 @@ __global__ __launch_bounds__(256, 1) void fa_decode_kernel(DecodeParams p) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();  // every wave's stores done; the merge region is free
   volatile int* last = reinterpret_cast<volatile int*>(smem);  // the one LDS array
-  if (tid == 0) {
+  if (etid == 0) {
     const unsigned old =
         __hip_atomic_fetch_add(p.ws_ctr + unit, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
     *last = old == (unsigned)(ns - 1) ? 1 : 0;
   }
   __syncthreads();
   if (!*last) return;
-  decode_merge_pieces<T, HDIM, NB>(p, unit, ns, ro, lse_out, row0, tid);
-  if (tid == 0) __hip_atomic_store(p.ws_ctr + unit, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  decode_merge_pieces<T, HDIM, NB>(p, unit, ns, ro, lse_out, row0, etid);
+  if (etid == 0) __hip_atomic_store(p.ws_ctr + unit, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 }  // namespace fa

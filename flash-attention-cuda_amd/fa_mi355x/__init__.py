@@ -52,6 +52,8 @@ EXPORTED_SYMBOLS = (
     "fa_decode_bf16",
     "fa_decode_num_splits",
     "fa_decode_ws_bytes",
+    "fa_decode_paged_f16",
+    "fa_decode_paged_bf16",
     "fa_select_config",
     "fa_num_configs",
     "fa_config_info",
@@ -156,6 +158,9 @@ def load_library() -> ctypes.CDLL:
     lib.fa_decode_f16.restype = i
     lib.fa_decode_bf16.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, vp, i, i, vp, ull, vp]
     lib.fa_decode_bf16.restype = i
+    for fn in (lib.fa_decode_paged_f16, lib.fa_decode_paged_bf16):
+        fn.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, vp, i, vp, i, i, vp, ull, vp]
+        fn.restype = i
     lib.fa_decode_num_splits.argtypes = [i, i, i, i, i, i]
     lib.fa_decode_num_splits.restype = i
     lib.fa_decode_ws_bytes.argtypes = [i, i, i, i, i, i, i]
@@ -451,6 +456,118 @@ def flash_attention_decode(q, k_cache, v_cache, kv_lens=None, causal: bool = Tru
                 lse.data_ptr() if return_lse else None, b, hq, hkv, sq, cap, d,
                 kv_lens.data_ptr() if kv_lens is not None else None, int(bool(causal)),
                 int(num_splits), ws.data_ptr() if need else None, need, st)
+    _check(rc)
+    return (out, lse) if return_lse else out
+
+
+def _check_decode_paged(q, k_pages, v_pages, block_table, kv_lens, out):
+    """Raise FlashAttentionError unless q/out are contiguous [B,Hq,Sq,D],
+    k_pages/v_pages contiguous [num_pages,Hkv,page_size,D] pools of q's 16-bit
+    dtype with page_size % 64 == 0 and Hq % Hkv == 0, block_table a contiguous
+    int32 [B,max_pages] tensor and kv_lens (if given) int32 [B], all on q's
+    device.  Dtypes, ranks and shapes are checked before where the tensors
+    live, so each rejection names its own cause whatever the device.  The
+    table's and the lengths' VALUES are not looked at (no sync)."""
+    import torch
+
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"q must be float16 or bfloat16, got {q.dtype}")
+    tensors = (("q", q), ("k_pages", k_pages), ("v_pages", v_pages), ("out", out))
+    for name, t in tensors:
+        if t.dtype != q.dtype:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be {q.dtype}, got {t.dtype}")
+        if t.dim() != 4:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be 4-D")
+        if not t.is_contiguous():
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be contiguous")
+    if out.shape != q.shape:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, "out must be [B,Hq,Sq,D] like q")
+    if k_pages.shape != v_pages.shape:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, "k_pages and v_pages must have one shape")
+    if k_pages.shape[3] != q.shape[3]:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, "q and the page pools must agree in head_dim")
+    if k_pages.shape[0] == 0:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, "the page pools hold no page")
+    if k_pages.shape[2] == 0 or k_pages.shape[2] % 64 != 0:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE,
+                                  f"page_size {k_pages.shape[2]} is not a positive multiple of 64")
+    if k_pages.shape[1] == 0 or q.shape[1] % k_pages.shape[1] != 0:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE,
+                                  f"heads_q {q.shape[1]} is not a multiple of heads_kv {k_pages.shape[1]}")
+    if block_table.dtype != torch.int32:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"block_table must be int32, got {block_table.dtype}")
+    if block_table.dim() != 2:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, "block_table must be 2-D [B, max_pages_per_seq]")
+    if block_table.shape[0] != q.shape[0]:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE,
+                                  f"block_table has {block_table.shape[0]} rows, q a batch of {q.shape[0]}")
+    if not block_table.is_contiguous():
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, "block_table must be contiguous")
+    if kv_lens is not None:
+        if kv_lens.dtype != torch.int32:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"kv_lens must be int32, got {kv_lens.dtype}")
+        if kv_lens.dim() != 1 or kv_lens.shape[0] != q.shape[0] or not kv_lens.is_contiguous():
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, "kv_lens must be a contiguous [B] tensor")
+    for name, t in tensors:
+        if not t.is_cuda:
+            raise FlashAttentionError(FA_ERR_NULL_POINTER, f"{name} must be a device tensor")
+        if t.device != q.device:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE,
+                                      f"{name} is on {t.device}, q on {q.device}: one device only")
+    if not block_table.is_cuda or block_table.device != q.device:
+        raise FlashAttentionError(FA_ERR_NULL_POINTER, f"block_table must be a tensor on {q.device}")
+    if kv_lens is not None and (not kv_lens.is_cuda or kv_lens.device != q.device):
+        raise FlashAttentionError(FA_ERR_NULL_POINTER, f"kv_lens must be a tensor on {q.device}")
+
+
+def flash_attention_decode_paged(q, k_pages, v_pages, block_table, kv_lens=None, causal: bool = True,
+                                 out=None, return_lse: bool = False, num_splits: int = 0, stream=None):
+    """Decode attention over a paged K/V cache (fa_decode_paged_f16 / _bf16).
+
+    q: [B, Hq, Sq, D] (1 <= Sq <= 16); k_pages, v_pages: the page pools,
+    [num_pages, Hkv, page_size, D] (BHSD inside a page, the serving stacks'
+    "HND" layout) with page_size % 64 == 0 and Hq % Hkv == 0; fp16 or bf16
+    contiguous device tensors of one dtype, D = 128 or 64.  block_table: int32
+    [B, max_pages_per_seq] on the same device; entry j of row b is the pool
+    page holding keys [j * page_size, (j + 1) * page_size) of element b (pages
+    may be shared and repeated).  kv_lens: int32 [B] (None: every length is
+    max_pages_per_seq * page_size).  Only table entries and rows below a
+    length are read; nothing is validated on the host, and a page id outside
+    the pool reads as zero rows (include/fa_mi355x.h).  The other arguments,
+    the return value and the contract (no sync, graph-capturable, the
+    per-(device, stream) workspace) are those of :func:`flash_attention_decode`,
+    whose result on the gathered cache this one equals bit for bit.
+    """
+    import torch
+
+    if out is None:
+        out = torch.empty_like(q)
+    _check_decode_paged(q, k_pages, v_pages, block_table, kv_lens, out)
+    b, hq, sq, d = q.shape
+    npages, hkv, psz = k_pages.shape[0], k_pages.shape[1], k_pages.shape[2]
+    mpp = block_table.shape[1]
+    lib = _lib or load_library()
+    dev = q.device.index
+    if stream is None:
+        st = torch._C._cuda_getCurrentRawStream(dev)
+    else:
+        st = stream if isinstance(stream, int) else stream.cuda_stream
+    lse = torch.empty((b, hq, sq), dtype=torch.float32, device=q.device) if return_lse else None
+    fn = lib.fa_decode_paged_bf16 if q.dtype is torch.bfloat16 else lib.fa_decode_paged_f16
+    with torch.cuda.device(dev):
+        cap = mpp * psz
+        need = 0
+        if cap <= 0x7fffffff - 64:  # (past it the entry itself refuses the shape)
+            key = (dev, b, hq, hkv, sq, cap, d, int(num_splits))
+            need = _DEC_NEED.get(key)
+            if need is None:
+                need = lib.fa_decode_ws_bytes(b, hq, hkv, sq, cap, d, int(num_splits))
+                _DEC_NEED[key] = need
+        ws = _workspace(need, dev, st) if need else None
+        rc = fn(q.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), out.data_ptr(),
+                lse.data_ptr() if return_lse else None, b, hq, hkv, sq, d, npages, psz,
+                block_table.data_ptr(), mpp, kv_lens.data_ptr() if kv_lens is not None else None,
+                int(bool(causal)), int(num_splits), ws.data_ptr() if need else None, need, st)
     _check(rc)
     return (out, lse) if return_lse else out
 

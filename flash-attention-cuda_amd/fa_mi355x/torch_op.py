@@ -4,6 +4,7 @@ rank 3: the wrapper that puts the kernel beside PyTorch SDPA on one box).
     import fa_mi355x.torch_op  # registers torch.ops.fa_mi355x.fwd
     o = torch.ops.fa_mi355x.fwd(q, k, v, causal=True)
     o = torch.ops.fa_mi355x.decode(q, k_cache, v_cache, kv_lens, causal=True)
+    o = torch.ops.fa_mi355x.decode_paged(q, k_pages, v_pages, block_table, kv_lens, causal=True)
 
 ``q, k, v``: fp16 or bf16 ``[B, H, S, D]`` (D = 128 or 64) tensors on the GPU (BHSD, the
 reference layout, flash_attention.cu:119-122); returns a new tensor of the same shape and dtype.
@@ -23,7 +24,7 @@ from __future__ import annotations
 
 import torch
 
-from . import flash_attention_decode, flash_attention_fwd
+from . import flash_attention_decode, flash_attention_decode_paged, flash_attention_fwd
 
 OP_NAME = "fa_mi355x::fwd"
 
@@ -94,3 +95,41 @@ _LIB.impl("decode", _decode_cpu, "CPU")
 torch.library.register_fake(DECODE_OP_NAME, _decode_fake, lib=_LIB)
 
 decode = torch.ops.fa_mi355x.decode
+
+# decode_paged(q [B,Hq,Sq,D], k_pages / v_pages [num_pages,Hkv,page_size,D],
+# block_table int32 [B,max_pages], kv_lens int32 [B] or None):
+# fa_mi355x.flash_attention_decode_paged behind the same kind of registration.
+# The pools are taken as they are (a strided pool raises).
+DECODE_PAGED_OP_NAME = "fa_mi355x::decode_paged"
+_LIB.define("decode_paged(Tensor q, Tensor k_pages, Tensor v_pages, Tensor block_table, "
+            "Tensor? kv_lens=None, bool causal=True) -> Tensor")
+
+
+def _decode_paged_gpu(q, k_pages, v_pages, block_table, kv_lens=None,
+                      causal: bool = True) -> torch.Tensor:
+    _no_grad_needed(q, k_pages, v_pages)
+    return flash_attention_decode_paged(q.contiguous(), k_pages, v_pages, block_table.contiguous(),
+                                        None if kv_lens is None else kv_lens.contiguous(),
+                                        causal=causal)
+
+
+def _decode_paged_cpu(q, k_pages, v_pages, block_table, kv_lens=None,
+                      causal: bool = True) -> torch.Tensor:
+    raise ValueError("fa_mi355x::decode_paged needs GPU tensors (no CPU path)")
+
+
+def _decode_paged_fake(q, k_pages, v_pages, block_table, kv_lens=None,
+                       causal: bool = True) -> torch.Tensor:
+    _no_grad_needed(q, k_pages, v_pages)
+    torch._check(q.dim() == 4 and q.shape[-1] in (64, 128), lambda: "expected [B, Hq, Sq, 64|128]")
+    torch._check(q.dtype in (torch.float16, torch.bfloat16), lambda: "expected fp16 or bf16")
+    torch._check(block_table.dim() == 2, lambda: "expected a [B, max_pages_per_seq] block table")
+    return torch.empty_like(q, memory_format=torch.contiguous_format)
+
+
+_LIB.impl("decode_paged", _decode_paged_gpu, "CUDA")
+_LIB.impl("decode_paged", torch.library.fallthrough_kernel, "Autograd")
+_LIB.impl("decode_paged", _decode_paged_cpu, "CPU")
+torch.library.register_fake(DECODE_PAGED_OP_NAME, _decode_paged_fake, lib=_LIB)
+
+decode_paged = torch.ops.fa_mi355x.decode_paged

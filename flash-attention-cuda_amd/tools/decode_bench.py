@@ -14,6 +14,16 @@ the 256-MiB Infinity Cache are rotated through enough copies (>= 512 MiB in
 all) that every call streams from HBM.
 
     python3 tools/decode_bench.py [--out profiles/decode_bench.jsonl] [--quick]
+
+--paged times fa_decode_paged_* against fa_decode_* instead (run_paged):
+the same K/V data as a randomly permuted page pool plus block table, page
+sizes 64 and 256, at three shapes (B=64 len=8192 bandwidth-bound, B=8 len=8192
+and B=1 len=32768 latency-bound).  Both entries are captured into HIP graphs
+(no host between calls) and the graphs replayed alternately in one process, a
+second contiguous leg included so that every row carries its own A/A spread:
+the figure of record is paged_over_contig beside contig_aa.
+
+    python3 tools/decode_bench.py --paged [--out profiles/decode_paged_bench.jsonl]
 """
 import argparse
 import json
@@ -54,7 +64,7 @@ def shapes(quick):
 
 
 def fill_splits(units, cap, cus, fill):
-    """csrc/fa_decode.hip decode_plan with kDecodeFill = fill."""
+    """csrc/fa_decode_host.hpp decode_plan with kDecodeFill = fill."""
     if units >= cus:
         return 1
     return max(1, min(-(-cus * fill // units), max(1, cap // 256), MAX_SPLITS))
@@ -205,19 +215,125 @@ def run(row, cus):
     return rec
 
 
+def paged_shapes():
+    return [dict(name=f"paged B={b} len={n}", b=b, hq=32, hkv=8, sq=1, d=128, n=n)
+            for b, n in ((64, 8192), (8, 8192), (1, 32768))]
+
+
+def run_paged(row, page_size, cus, placement="random", rounds=9):
+    """Paged against contiguous decode on the same data: us per call from
+    alternately replayed HIP graphs (contiguous, paged, contiguous again)."""
+    lib = fa_mi355x.load_library()
+    dt = torch.float16
+    b, hq, hkv, sq, d, cap = row["b"], row["hq"], row["hkv"], row["sq"], row["d"], row["n"]
+    mpp = cap // page_size
+    npages = b * mpp
+    kv_bytes = 2 * b * hkv * cap * d * 2
+    copies = max(1, min(32, -(-(512 << 20) // kv_bytes)))
+    gen = torch.Generator(device="cuda").manual_seed(1)
+
+    def rnd(*shape):
+        return (torch.rand(shape, generator=gen, device="cuda", dtype=torch.float32) * 2 - 1).to(dt)
+
+    def pool(x, perm):  # logical page (b, j) -> pool page perm[b * mpp + j]
+        out = torch.empty((npages, hkv, page_size, d), dtype=dt, device="cuda")
+        out[perm] = x.view(b, hkv, mpp, page_size, d).permute(0, 2, 1, 3, 4).reshape(
+            npages, hkv, page_size, d)
+        return out
+
+    ks, vs, kps, vps, tabs = [], [], [], [], []
+    for _ in range(copies):
+        k, v = rnd(b, hkv, cap, d), rnd(b, hkv, cap, d)
+        perm = torch.randperm(npages, generator=gen, device="cuda") if placement == "random" else \
+            torch.arange(npages, device="cuda")
+        ks.append(k), vs.append(v), kps.append(pool(k, perm)), vps.append(pool(v, perm))
+        tabs.append(perm.view(b, mpp).to(torch.int32).contiguous())
+    q = rnd(b, hq, sq, d)
+    plan = fa_mi355x.decode_num_splits(b, hq, hkv, sq, cap, d)
+    need = lib.fa_decode_ws_bytes(b, hq, hkv, sq, cap, d, 0)
+    ws = torch.zeros(max(need, 1), dtype=torch.uint8, device="cuda")
+    wsp = ws.data_ptr() if need else None
+    outs = [torch.empty_like(q) for _ in range(2)]
+    iters = 20 if kv_bytes < (1 << 30) else 5
+
+    def contig(st):
+        for i in range(iters):
+            c = i % copies
+            rc = lib.fa_decode_f16(q.data_ptr(), ks[c].data_ptr(), vs[c].data_ptr(), outs[0].data_ptr(),
+                                   None, b, hq, hkv, sq, cap, d, None, 1, 0, wsp, need, st)
+            assert rc == 0, rc
+
+    def paged(st):
+        for i in range(iters):
+            c = i % copies
+            rc = lib.fa_decode_paged_f16(q.data_ptr(), kps[c].data_ptr(), vps[c].data_ptr(),
+                                         outs[1].data_ptr(), None, b, hq, hkv, sq, d, npages, page_size,
+                                         tabs[c].data_ptr(), mpp, None, 1, 0, wsp, need, st)
+            assert rc == 0, rc
+
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):  # first-launch set-up outside the captures
+        contig(side.cuda_stream)
+        paged(side.cuda_stream)
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    same = bool(torch.equal(outs[0], outs[1]))  # both ran copy (iters - 1) % copies last
+    graphs = []
+    for fn in (contig, paged):
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            fn(torch.cuda.current_stream().cuda_stream)
+        g.replay()
+        graphs.append(g)
+    torch.cuda.synchronize()
+    legs = (0, 1, 0)  # contiguous, paged, contiguous again (the A/A leg)
+    ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+           for _ in range(rounds)] for _ in legs]
+    for r in range(rounds):
+        for j, gi in enumerate(legs):
+            ev[j][r][0].record()
+            graphs[gi].replay()
+            ev[j][r][1].record()
+    torch.cuda.synchronize()
+    ts = [sorted(a.elapsed_time(c) * 1e3 / iters for a, c in e) for e in ev]
+    med = [t[len(t) // 2] for t in ts]
+    return dict(name=row["name"], page_size=page_size, placement=placement, batch=b, heads_q=hq, heads_kv=hkv, seqlen_q=sq,
+                head_dim=d, dtype="float16", kv_len=cap, num_pages=npages, copies=copies,
+                num_splits=plan, kv_bytes=kv_bytes, rounds=rounds, iters=iters, bit_identical=same,
+                contig_us=round(med[0], 2), paged_us=round(med[1], 2), contig2_us=round(med[2], 2),
+                contig_min_us=round(min(ts[0][0], ts[2][0]), 2),
+                contig_max_us=round(max(ts[0][-1], ts[2][-1]), 2),
+                paged_min_us=round(ts[1][0], 2), paged_max_us=round(ts[1][-1], 2),
+                paged_over_contig=round(med[1] / med[0], 4), contig_aa=round(med[2] / med[0], 4),
+                contig_share_of_copy_rate=round(kv_bytes / (med[0] * 1e-6) / COPY_RATE, 4),
+                paged_share_of_copy_rate=round(kv_bytes / (med[1] * 1e-6) / COPY_RATE, 4))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..",
-                                                  "profiles", "decode_bench.jsonl"))
+    ap.add_argument("--out", default=None, help="default profiles/decode_bench.jsonl "
+                    "(profiles/decode_paged_bench.jsonl with --paged)")
     ap.add_argument("--quick", action="store_true", help="three rows only")
+    ap.add_argument("--paged", action="store_true",
+                    help="paged against contiguous decode, page sizes 64 and 256")
+    ap.add_argument("--placement", choices=("random", "identity"), default="random",
+                    help="--paged: pool pages under a random permutation (default) or in logical order")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "profiles",
+                                "decode_paged_bench.jsonl" if args.paged else "decode_bench.jsonl")
     if not torch.cuda.is_available():
         sys.exit("decode_bench.py needs a GPU")
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    if args.paged:
+        jobs = [(run_paged, (row, ps, cus, args.placement)) for row in paged_shapes() for ps in (64, 256)]
+    else:
+        jobs = [(run, (row, cus)) for row in shapes(args.quick)]
     with open(args.out, "w") as f:
-        for row in shapes(args.quick):
-            rec = run(row, cus)
+        for fn, a in jobs:
+            rec = fn(*a)
             rec["cus"] = cus
             f.write(json.dumps(rec) + "\n")
             f.flush()

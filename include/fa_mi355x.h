@@ -207,6 +207,60 @@ int fa_decode_num_splits(int batch, int heads_q, int heads_kv, int seqlen_q,
 unsigned long long fa_decode_ws_bytes(int batch, int heads_q, int heads_kv, int seqlen_q,
                                       int kv_capacity, int head_dim, int num_splits);
 
+/* Decode attention over a PAGED K/V cache: fa_decode_* with the cache held as
+ * a pool of fixed-size pages plus a per-sequence block table (the layout of
+ * the serving stacks), so sequences grow, finish and share prefixes without
+ * the cache being gathered first.
+ *   q, o      [batch][heads_q][seqlen_q][head_dim]          (1 <= seqlen_q <= 16)
+ *   k_pages, v_pages  [num_pages][heads_kv][page_size][head_dim], contiguous:
+ *             BHSD inside each page (the serving stacks' "HND" page layout).
+ *   page_size any positive multiple of 64 (64, 128, 192, ...: a 64-key tile
+ *             never straddles two pages), page_size * 2 * head_dim <= INT_MAX.
+ *   block_table DEVICE int32[batch][max_pages_per_seq], row-major: entry j of
+ *             row b is the pool page holding keys [j * page_size, (j + 1) *
+ *             page_size) of batch element b.  Pages may be shared between
+ *             batch elements and listed more than once.
+ *   kv_lens   DEVICE int32[batch], clamped to the logical capacity
+ *             kv_capacity := max_pages_per_seq * page_size; NULL = that
+ *             capacity for every element.
+ * Everything else (causal, lse, GQA, row groups, num_splits, the workspace)
+ * is as for fa_decode_* with that kv_capacity: num_splits = 0 takes
+ * fa_decode_num_splits(batch, heads_q, heads_kv, seqlen_q, kv_capacity,
+ * head_dim), the workspace is fa_decode_ws_bytes(..., kv_capacity, head_dim,
+ * num_splits), and one per-stream workspace serves paged decode, contiguous
+ * decode and forward launches in any order.
+ * The kernel is the contiguous one with a per-tile descriptor: the same
+ * workgroups, tiles, order of operations and merges.  For the same data and
+ * the same num_splits, O and LSE are BIT-IDENTICAL to fa_decode_* run on the
+ * gathered [batch][heads_kv][kv_capacity][head_dim] cache.
+ * What is read: only the table entries of pages that hold a key below len_b,
+ * and of those pages only the rows below len_b.  Entries past that, rows past
+ * the length in the last page and unmapped pages may hold anything (NaN bit
+ * patterns included); they never reach O.
+ * Nothing is validated on the host (the call stays sync-free and
+ * graph-capturable: table and lengths may change between replays).  A page id
+ * outside [0, num_pages) in an entry that is read touches no memory: that
+ * tile reads as zero rows, the batch element's output is unspecified but
+ * finite, every other element is unaffected.
+ * Argument errors, returned before any launch: page_size not a positive
+ * multiple of 64 (or past the byte range above), num_pages <= 0,
+ * max_pages_per_seq < 0 or kv_capacity > INT_MAX - 64: FA_ERR_BAD_SHAPE;
+ * block_table (or q, k_pages, v_pages, o) NULL with kv_capacity > 0:
+ * FA_ERR_NULL_POINTER; head_dim, seqlen_q, heads_q % heads_kv, num_splits and
+ * the workspace as for fa_decode_*.  Empty problems (batch or heads of 0)
+ * return FA_OK without launching; kv_capacity == 0 (max_pages_per_seq == 0)
+ * with rows present only fills O with zeros and LSE with -inf. */
+int fa_decode_paged_f16(const void* q, const void* k_pages, const void* v_pages, void* o, float* lse,
+                        int batch, int heads_q, int heads_kv, int seqlen_q, int head_dim,
+                        int num_pages, int page_size, const int* block_table, int max_pages_per_seq,
+                        const int* kv_lens, int causal, int num_splits,
+                        void* workspace, unsigned long long ws_bytes, void* hip_stream);
+int fa_decode_paged_bf16(const void* q, const void* k_pages, const void* v_pages, void* o, float* lse,
+                         int batch, int heads_q, int heads_kv, int seqlen_q, int head_dim,
+                         int num_pages, int page_size, const int* block_table, int max_pages_per_seq,
+                         const int* kv_lens, int causal, int num_splits,
+                         void* workspace, unsigned long long ws_bytes, void* hip_stream);
+
 /* The dispatcher's decision (ref tier table :620-661): config id used by
  * fa_fwd_f16 for this shape.  The _ws entries may run the causal split tier
  * instead: check fa_fwd_split_pieces() first (> 0: the split tier runs with
