@@ -129,8 +129,8 @@ __device__ __forceinline__ void decode_merge_pieces(const DecodeParams& p, size_
 // where a tile's 64 rows start and how many of them are live comes from the
 // block table (tile_at() below), so the result is bit-identical to the
 // contiguous kernel on the gathered cache.  Code for PAGED sits under
-// `if constexpr`: the PAGED = false instantiations compile to the
-// instruction streams they had before the parameter existed.
+// `if constexpr`: the PAGED = false instantiations carry none of it
+// (DESIGN.md §3.0h).
 template <class T, int HDIM, int NB, bool PAGED = false, class P = DecodeParams>
 __global__ __launch_bounds__(256, 1) void fa_decode_kernel(P p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -239,13 +239,15 @@ __global__ __launch_bounds__(256, 1) void fa_decode_kernel(P p) {
                   8 * (pp & 1);
   }
 
-  f32x4 acc[NB][NE], lacc[NB];
-  float m[NB];
+  // lsum: the lane's share of its row's l (its 16 keys of every tile); the four
+  // lanes of a row add theirs up once, before the in-CU merge
+  f32x4 acc[NB][NE];
+  float m[NB], lsum[NB];
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb) {
 #pragma unroll
     for (int e = 0; e < NE; ++e) acc[nb][e] = f32x4{};
-    lacc[nb] = f32x4{};
+    lsum[nb] = 0.f;
     m[nb] = ninf();
   }
 
@@ -370,14 +372,24 @@ __global__ __launch_bounds__(256, 1) void fa_decode_kernel(P p) {
       const float msafe = mnew == ninf() ? 0.f : mnew;  // a row that has seen no key yet
       const float alpha = __builtin_amdgcn_exp2f(m[nb] - msafe);
       m[nb] = mnew;
-#pragma unroll
-      for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-          pf[nb][cb >> 1][4 * (cb & 1) + i] = (T)__builtin_amdgcn_exp2f(s[nb][cb][i] - msafe);
+      // l takes the fp32 exponentials, P their rounding to T: a sum of rounded
+      // P would put T's rounding (2^-9 relative for bf16) into the LSE of a
+      // row with few keys
+      lsum[nb] *= alpha;
 #pragma unroll
       for (int e = 0; e < NE; ++e) acc[nb][e] *= alpha;
-      lacc[nb] *= alpha;
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const float ex = __builtin_amdgcn_exp2f(s[nb][cb][i] - msafe);
+          pf[nb][cb >> 1][4 * (cb & 1) + i] = (T)ex;
+          lsum[nb] += ex;
+        }
+        // 16 keys at a time (with O rescaled first): this order keeps the 64-row
+        // head_dim-128 variant out of scratch
+        if constexpr (!kEarlyK) asm volatile("" : "+v"(lsum[nb]));
+      }
     };
     if constexpr (kEarlyK) {
 #pragma unroll
@@ -401,8 +413,7 @@ __global__ __launch_bounds__(256, 1) void fa_decode_kernel(P p) {
       *reinterpret_cast<u32x4*>(vimg + lds_off(RPW * ps + vrl, vch)) = vr[ps];
     load_v(nxt);
 
-    // O^T += V^T . P^T, l += ones . P^T (the same rounded P)
-    const tx8 ones = {(T)1.f, (T)1.f, (T)1.f, (T)1.f, (T)1.f, (T)1.f, (T)1.f, (T)1.f};
+    // O^T += V^T . P^T
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
 #pragma unroll
@@ -414,8 +425,6 @@ __global__ __launch_bounds__(256, 1) void fa_decode_kernel(P p) {
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) acc[nb][e] = Elem<T>::mfma(vf, pf[nb][u], acc[nb][e]);
       }
-#pragma unroll
-      for (int nb = 0; nb < NB; ++nb) lacc[nb] = Elem<T>::mfma(ones, pf[nb][u], lacc[nb]);
     }
   }
 
@@ -435,7 +444,7 @@ __global__ __launch_bounds__(256, 1) void fa_decode_kernel(P p) {
     for (int e = 0; e < NE; ++e)
       *reinterpret_cast<f32x4*>(smem + (((wave * NB + nb) * NE + e) * 64 + elane) * 16) = acc[nb][e];
     *reinterpret_cast<float2*>(smem + ML_OFF + ((wave * NB + nb) * 64 + elane) * 8) =
-        float2{m[nb], lacc[nb][0]};
+        float2{m[nb], sum_xor32(sum_xor16(lsum[nb]))};
   }
   __syncthreads();
   const bool split = ns > 1;
