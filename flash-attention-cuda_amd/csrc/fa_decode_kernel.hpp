@@ -71,6 +71,38 @@ struct DecodePagedParams : DecodeParams {
   unsigned long long head_bytes;  // page_size * row bytes
 };
 
+// The FP8 cache twins (fa_decode_kv8.hip, fa_decode_paged_kv8.hip): K and V
+// are OCP FP8 E4M3 bytes with one fp32 scale per K/V head each (device
+// arrays of Hkv floats, nullptr = 1.0); Q and O stay 16-bit.
+struct DecodeKv8Params : DecodeParams {
+  const float* k_scale;
+  const float* v_scale;
+};
+struct DecodePagedKv8Params : DecodePagedParams {
+  const float* k_scale;
+  const float* v_scale;
+};
+
+// 8 E4M3 bytes (two words) -> 8 elements of T.  Exact: every finite E4M3 code
+// is representable in f16 and in bf16, and the scale operand is 1.0.
+template <class T>
+__device__ __forceinline__ typename Elem<T>::x8 cvt_fp8x8(unsigned w0, unsigned w1) {
+  typedef T tx2 __attribute__((ext_vector_type(2)));
+  tx2 a, b, c, d;
+  if constexpr (std::is_same<T, __bf16>::value) {
+    a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, 1.0f, false);
+    b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, 1.0f, true);
+    c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, 1.0f, false);
+    d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, 1.0f, true);
+  } else {
+    a = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w0, 1.0f, false);
+    b = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w0, 1.0f, true);
+    c = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w1, 1.0f, false);
+    d = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w1, 1.0f, true);
+  }
+  return typename Elem<T>::x8{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
+}
+
 constexpr int kDecodeVBytes = 4 * 64 * 256;  // four wave-private V images
 template <int HDIM, int NB>
 constexpr int decode_lds_bytes() {
@@ -131,14 +163,30 @@ __device__ __forceinline__ void decode_merge_pieces(const DecodeParams& p, size_
 // contiguous kernel on the gathered cache.  Code for PAGED sits under
 // `if constexpr`: the PAGED = false instantiations carry none of it
 // (DESIGN.md §3.0h).
-template <class T, int HDIM, int NB, bool PAGED = false, class P = DecodeParams>
+//
+// KV = T: the cache holds T.  KV = unsigned char (P = a Kv8 params struct): the
+// cache holds E4M3 bytes, converted to T in registers:
+//   K: one 16-B load per lane covers the lane's 8 dims of TWO k-steps (dims
+//      64 tt + 16 g + 8 h .. +7 for k-step 2 tt + h), and Q's fragments are
+//      loaded under the same permutation of d (the sum over d has no order);
+//   V: one 16-B load carries 16 elements of a row and becomes two 16-B writes
+//      into the same wave-private image, so the transposed reads and the PV
+//      MFMAs are those of the 16-bit kernel;
+//   k_scale[hkv] is folded into the score scale c, v_scale[hkv] into the
+//      normalisation of the in-CU merge.
+// All of it sits under `if constexpr (KV8)`: the KV = T instantiations carry
+// none of it.
+template <class T, int HDIM, int NB, bool PAGED = false, class P = DecodeParams, class KV = T>
 __global__ __launch_bounds__(256, 1) void fa_decode_kernel(P p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int ROW = 2 * HDIM;      // bytes per Q/K/V/O row
+  constexpr bool KV8 = !std::is_same<KV, T>::value;
+  static_assert(!KV8 || std::is_same<KV, unsigned char>::value, "the cache holds T or E4M3 bytes");
+  constexpr int ROW = 2 * HDIM;      // bytes per Q/O row
+  constexpr int CROW = KV8 ? HDIM : 2 * HDIM;  // bytes per K/V cache row
   constexpr int NTQ = HDIM / 32;     // 32-wide k-steps of QK^T
   constexpr int NE = HDIM / 16;      // 16-wide d-blocks of O
   constexpr int RW = 16 * NB;        // query rows per workgroup
-  constexpr int RPW = 512 / HDIM;    // V rows one load instruction of a wave covers
+  constexpr int RPW = (KV8 ? 1024 : 512) / HDIM;  // V rows one load instruction of a wave covers
   constexpr int NPASS = 64 / RPW;    // V load instructions per tile
   constexpr int EW = NE / 4;         // d-blocks each wave finishes in the in-CU merge
   // the next tile's K is issued right after QK^T; with 64 rows at head_dim 128
@@ -172,36 +220,44 @@ __global__ __launch_bounds__(256, 1) void fa_decode_kernel(P p) {
   const int nrows = max(0, min(RW, p.rows - row0));
   const char* qb = static_cast<const char*>(p.q) + (qrow + row0) * ROW;
   char* ob = static_cast<char*>(p.o) + (qrow + row0) * ROW;
-  const size_t kvoff = PAGED ? 0 : (size_t)bhk * (size_t)p.cap * ROW;
+  const size_t kvoff = PAGED ? 0 : (size_t)bhk * (size_t)p.cap * CROW;
   const __amdgpu_buffer_rsrc_t rq = make_rsrc(qb, nrows * ROW);
   const __amdgpu_buffer_rsrc_t ro = make_rsrc(ob, nrows * ROW);
   // contiguous: one descriptor per operand for the whole head.  Paged: one per
   // tile, rebuilt by tile_at() before the tile's loads are issued
   __amdgpu_buffer_rsrc_t rk =
-      make_rsrc(static_cast<const char*>(p.k) + kvoff, PAGED ? 0 : len * ROW);
+      make_rsrc(static_cast<const char*>(p.k) + kvoff, PAGED ? 0 : len * CROW);
   __amdgpu_buffer_rsrc_t rv =
-      make_rsrc(static_cast<const char*>(p.v) + kvoff, PAGED ? 0 : len * ROW);
+      make_rsrc(static_cast<const char*>(p.v) + kvoff, PAGED ? 0 : len * CROW);
+
+  // score scale: the cache's K scale rides on it (a wave-uniform load)
+  [[maybe_unused]] float csc = 1.0f;
+  if constexpr (KV8) csc = p.k_scale ? p.c * p.k_scale[hk] : p.c;
 
   // Q fragments (B operand): qf[nb][t] = Q[16 nb + r16][32 t + 8 g .. +7]; rows
   // past the group's last read as zeros.  Held in registers, except with 64
   // rows at head_dim 128 (kQLds: the register file cannot hold them beside
   // the O accumulator and both prefetches): there wave nb parks block nb's
   // fragments lane-linearly behind the V images and every wave re-reads them
-  // per tile.
+  // per tile.  KV8: k-step t holds dims 64 (t >> 1) + 16 g + 8 (t & 1) .. +7,
+  // the dims K's 16-byte loads deliver.
   tx8 qf[kQLds ? 1 : NB][NTQ];
   char* qimg = smem + kDecodeVBytes;
   if constexpr (kQLds) {
 #pragma unroll
     for (int t = 0; t < NTQ; ++t)
       *reinterpret_cast<u32x4*>(qimg + ((wave * NTQ + t) * 64 + lane) * 16) = __builtin_bit_cast(
-          u32x4, buf_load16(rq, (16 * wave + r16) * ROW + (4 * t + g) * 16));
+          u32x4, buf_load16(rq, (16 * wave + r16) * ROW +
+                              (KV8 ? 128 * (t >> 1) + 32 * g + 16 * (t & 1) : (4 * t + g) * 16)));
     __syncthreads();
   } else {
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
       for (int t = 0; t < NTQ; ++t)
-        qf[nb][t] = __builtin_bit_cast(tx8, buf_load16(rq, (16 * nb + r16) * ROW + (4 * t + g) * 16));
+        qf[nb][t] = __builtin_bit_cast(
+            tx8, buf_load16(rq, (16 * nb + r16) * ROW +
+                                    (KV8 ? 128 * (t >> 1) + 32 * g + 16 * (t & 1) : (4 * t + g) * 16)));
   }
   auto qfrag = [&](int nb, int t) -> tx8 {
     if constexpr (kQLds)
@@ -223,12 +279,21 @@ __global__ __launch_bounds__(256, 1) void fa_decode_kernel(P p) {
   // S^T accumulator of lane (g, r16) holds keys 16 cb + 4 sg + i (the order
   // the transposed V reads deliver)
   const unsigned krow = 4 * ((((r16 >> 2) & 1) << 1) | (r16 >> 3)) + (r16 & 3);
-  const unsigned kvo = krow * ROW + g * 16;
+  const unsigned kvo = krow * CROW + g * 16;
   // V staging (conflict-free writes into image A) and transposed reads
-  const int vrl = HDIM == 128 ? 2 * ((lane >> 5) & 1) + ((lane >> 2) & 1)
-                              : 2 * ((lane >> 4) & 3) + ((lane >> 2) & 1);
-  const int vch = HDIM == 128 ? 4 * ((lane >> 3) & 3) + (lane & 3) : 4 * ((lane >> 3) & 1) + (lane & 3);
-  const unsigned vvo = vrl * ROW + vch * 16;
+  // KV8: lane = (16-B piece vch of cache row vrl); the piece becomes chunks
+  // 2 vch and 2 vch + 1 of the image row.  ds_write_b128 banks are 128 B wide
+  // per 8 consecutive lanes: lane bits 0..2 = (vch bit 0, row bit 0, row bit
+  // 2), which lds_off() turns into the 8 distinct 16-B slots of a bank row
+  // (slot bit 0 = row bit 2 ^ j, bit 1 = vch bit 0 ^ row bit 3, + 4 (row & 1)).
+  const int vrl = KV8 ? (HDIM == 128 ? ((lane >> 1) & 1) + 2 * ((lane >> 5) & 1) + 4 * ((lane >> 2) & 1)
+                                     : ((lane >> 1) & 1) + 2 * ((lane >> 4) & 1) +
+                                           4 * ((lane >> 2) & 1) + 8 * ((lane >> 5) & 1))
+                      : HDIM == 128 ? 2 * ((lane >> 5) & 1) + ((lane >> 2) & 1)
+                                    : 2 * ((lane >> 4) & 3) + ((lane >> 2) & 1);
+  const int vch = KV8 ? (HDIM == 128 ? (lane & 1) + 2 * ((lane >> 3) & 3) : (lane & 1) + 2 * ((lane >> 3) & 1))
+                      : HDIM == 128 ? 4 * ((lane >> 3) & 3) + (lane & 3) : 4 * ((lane >> 3) & 1) + (lane & 3);
+  const unsigned vvo = vrl * CROW + vch * 16;
   char* vimg = smem + 16384 * wave;
   int vaddr[2];
   {
@@ -251,7 +316,8 @@ __global__ __launch_bounds__(256, 1) void fa_decode_kernel(P p) {
     m[nb] = ninf();
   }
 
-  tx8 kf[4][NTQ];
+  tx8 kf[4][NTQ];  // (unused with KV8)
+  [[maybe_unused]] u32x4 kq[KV8 ? 4 : 1][KV8 ? NTQ / 2 : 1];  // KV8: 16 bytes = two k-steps
   u32x4 vr[NPASS];
   // tile `tl`'s loads; a tile past the piece is addressed past the
   // descriptor's range (row len): zeros, no memory traffic, no branch
@@ -262,22 +328,30 @@ __global__ __launch_bounds__(256, 1) void fa_decode_kernel(P p) {
     if constexpr (PAGED)
       base = tofs + kvo;
     else
-      base = (unsigned)min(64 * tl, len) * ROW + kvo;
+      base = (unsigned)min(64 * tl, len) * CROW + kvo;
+    if constexpr (KV8) {
 #pragma unroll
-    for (int cb = 0; cb < 4; ++cb)
+      for (int cb = 0; cb < 4; ++cb)
 #pragma unroll
-      for (int t = 0; t < NTQ; ++t)
-        kf[cb][t] = __builtin_bit_cast(tx8, buf_load16(rk, (int)(base + 16 * cb * ROW + 64 * t)));
+        for (int tt = 0; tt < NTQ / 2; ++tt)
+          kq[cb][tt] = __builtin_amdgcn_raw_buffer_load_b128(rk, (int)(base + 16 * cb * CROW + 64 * tt), 0, 0);
+    } else {
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+        for (int t = 0; t < NTQ; ++t)
+          kf[cb][t] = __builtin_bit_cast(tx8, buf_load16(rk, (int)(base + 16 * cb * ROW + 64 * t)));
+    }
   };
   auto load_v = [&](int tl) {
     unsigned base;
     if constexpr (PAGED)
       base = tofs + vvo;
     else
-      base = (unsigned)min(64 * tl, len) * ROW + vvo;
+      base = (unsigned)min(64 * tl, len) * CROW + vvo;
 #pragma unroll
     for (int ps = 0; ps < NPASS; ++ps)
-      vr[ps] = __builtin_amdgcn_raw_buffer_load_b128(rv, (int)(base + ps * RPW * ROW), 0, 0);
+      vr[ps] = __builtin_amdgcn_raw_buffer_load_b128(rv, (int)(base + ps * RPW * CROW), 0, 0);
   };
 
   int tile = t0 + wave;
@@ -302,9 +376,9 @@ __global__ __launch_bounds__(256, 1) void fa_decode_kernel(P p) {
       const bool ok = (unsigned)pg < (unsigned)p.num_pages;
       const int rows = live && ok ? 64 * r + min(len - 64 * tl, 64) : 0;
       const size_t off = (size_t)(ok ? pg : 0) * p.page_bytes + (size_t)hk * p.head_bytes;
-      rk = make_rsrc(static_cast<const char*>(p.k) + off, rows * ROW);
-      rv = make_rsrc(static_cast<const char*>(p.v) + off, rows * ROW);
-      tofs = (unsigned)(64 * r) * ROW;
+      rk = make_rsrc(static_cast<const char*>(p.k) + off, rows * CROW);
+      rv = make_rsrc(static_cast<const char*>(p.v) + off, rows * CROW);
+      tofs = (unsigned)(64 * r) * CROW;
     }
   };
   if constexpr (PAGED) {
@@ -350,11 +424,21 @@ __global__ __launch_bounds__(256, 1) void fa_decode_kernel(P p) {
       for (int cb = 0; cb < 4; ++cb)
 #pragma unroll
         for (int t = 0; t < NTQ; ++t)
-          s[nb][cb] = Elem<T>::mfma(kf[cb][t], qfrag(nb, t), t == 0 ? f32x4{} : s[nb][cb]);
+          if constexpr (KV8)
+            s[nb][cb] = Elem<T>::mfma(
+                cvt_fp8x8<T>(kq[cb][t >> 1][2 * (t & 1)], kq[cb][t >> 1][2 * (t & 1) + 1]),
+                qfrag(nb, t), t == 0 ? f32x4{} : s[nb][cb]);
+          else
+            s[nb][cb] = Elem<T>::mfma(kf[cb][t], qfrag(nb, t), t == 0 ? f32x4{} : s[nb][cb]);
     };
     auto softmax = [&](int nb) {
 #pragma unroll
-      for (int cb = 0; cb < 4; ++cb) s[nb][cb] *= p.c;
+      for (int cb = 0; cb < 4; ++cb) {
+        if constexpr (KV8)
+          s[nb][cb] *= csc;
+        else
+          s[nb][cb] *= p.c;
+      }
       if (need_mask) {
 #pragma unroll
         for (int cb = 0; cb < 4; ++cb)
@@ -408,9 +492,18 @@ __global__ __launch_bounds__(256, 1) void fa_decode_kernel(P p) {
 
     if constexpr (!kEarlyK) load_k(nxt);
     // V tile -> the wave's image, then the next tile's V loads
+    if constexpr (KV8) {
 #pragma unroll
-    for (int ps = 0; ps < NPASS; ++ps)
-      *reinterpret_cast<u32x4*>(vimg + lds_off(RPW * ps + vrl, vch)) = vr[ps];
+      for (int ps = 0; ps < NPASS; ++ps)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+          *reinterpret_cast<tx8*>(vimg + lds_off(RPW * ps + vrl, 2 * vch + j)) =
+              cvt_fp8x8<T>(vr[ps][2 * j], vr[ps][2 * j + 1]);
+    } else {
+#pragma unroll
+      for (int ps = 0; ps < NPASS; ++ps)
+        *reinterpret_cast<u32x4*>(vimg + lds_off(RPW * ps + vrl, vch)) = vr[ps];
+    }
     load_v(nxt);
 
     // O^T += V^T . P^T
@@ -447,6 +540,11 @@ __global__ __launch_bounds__(256, 1) void fa_decode_kernel(P p) {
         float2{m[nb], sum_xor32(sum_xor16(lsum[nb]))};
   }
   __syncthreads();
+  // KV8: the cache's V scale rides on the normalisation (unsplit store and split partials alike)
+  [[maybe_unused]] float vsc = 1.0f;
+  if constexpr (KV8) {
+    if (p.v_scale) vsc = p.v_scale[hk];
+  }
   const bool split = ns > 1;
   const size_t slot = (size_t)unit * ns + piece;
   const __amdgpu_buffer_rsrc_t rso =
@@ -470,7 +568,7 @@ __global__ __launch_bounds__(256, 1) void fa_decode_kernel(P p) {
       mw[w] = M == ninf() ? 0.f : __builtin_amdgcn_exp2f(mw[w] - M);  // now the weight
       L = __builtin_fmaf(mw[w], lw[w], L);
     }
-    const float inv = L > 0.f ? 1.0f / L : 0.f;
+    const float inv = KV8 ? (L > 0.f ? 1.0f / L : 0.f) * vsc : L > 0.f ? 1.0f / L : 0.f;
     const float lse2 = L > 0.f ? M + __builtin_log2f(L) : ninf();
     const int row = 16 * nb + er16;
 #pragma unroll

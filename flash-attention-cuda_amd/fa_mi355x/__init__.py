@@ -54,6 +54,10 @@ EXPORTED_SYMBOLS = (
     "fa_decode_ws_bytes",
     "fa_decode_paged_f16",
     "fa_decode_paged_bf16",
+    "fa_decode_kv8_f16",
+    "fa_decode_kv8_bf16",
+    "fa_decode_paged_kv8_f16",
+    "fa_decode_paged_kv8_bf16",
     "fa_select_config",
     "fa_num_configs",
     "fa_config_info",
@@ -160,6 +164,12 @@ def load_library() -> ctypes.CDLL:
     lib.fa_decode_bf16.restype = i
     for fn in (lib.fa_decode_paged_f16, lib.fa_decode_paged_bf16):
         fn.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, vp, i, vp, i, i, vp, ull, vp]
+        fn.restype = i
+    for fn in (lib.fa_decode_kv8_f16, lib.fa_decode_kv8_bf16):
+        fn.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, vp, i, i, vp, ull, vp, vp, vp]
+        fn.restype = i
+    for fn in (lib.fa_decode_paged_kv8_f16, lib.fa_decode_paged_kv8_bf16):
+        fn.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, vp, i, vp, i, i, vp, ull, vp, vp, vp]
         fn.restype = i
     lib.fa_decode_num_splits.argtypes = [i, i, i, i, i, i]
     lib.fa_decode_num_splits.restype = i
@@ -373,10 +383,62 @@ def decode_num_splits(batch: int, heads_q: int, heads_kv: int, seqlen_q: int, kv
                                                    kv_capacity, head_dim)
 
 
-def _check_decode(q, k_cache, v_cache, kv_lens, out):
+def _kv8_caches(q, kname, k, vname, v, k_scale, v_scale) -> bool:
+    """True when both caches are torch.float8_e4m3fn (the kv8 entries), False
+    when both have q's dtype; FlashAttentionError for every other pairing and
+    for scales given beside a 16-bit cache."""
+    import torch
+
+    fp8 = torch.float8_e4m3fn
+    if k.dtype is fp8 or v.dtype is fp8:
+        if k.dtype != v.dtype:
+            raise FlashAttentionError(
+                FA_ERR_BAD_SHAPE,
+                f"{kname} and {vname} must have one dtype, got {k.dtype} and {v.dtype}")
+        return True
+    other_fp8 = tuple(getattr(torch, n) for n in ("float8_e4m3fnuz", "float8_e5m2", "float8_e5m2fnuz",
+                                                  "float8_e8m0fnu") if hasattr(torch, n))
+    for name, t in ((kname, k), (vname, v)):
+        if t.dtype in other_fp8:
+            raise FlashAttentionError(
+                FA_ERR_BAD_SHAPE,
+                f"{name}: {t.dtype} is not supported, an FP8 cache must be torch.float8_e4m3fn (OCP E4M3)")
+        if t.dtype != q.dtype:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be {q.dtype}, got {t.dtype}")
+    if k_scale is not None or v_scale is not None:
+        raise FlashAttentionError(
+            FA_ERR_BAD_SHAPE,
+            f"k_scale / v_scale go with a torch.float8_e4m3fn cache only, the cache is {k.dtype}")
+    return False
+
+
+def _check_scales(heads_kv, k_scale, v_scale):
+    """Each scale (if given) is a contiguous float32 [Hkv] tensor."""
+    import torch
+
+    for name, t in (("k_scale", k_scale), ("v_scale", v_scale)):
+        if t is None:
+            continue
+        if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 1
+                or t.shape[0] != heads_kv or not t.is_contiguous()):
+            got = f"{t.dtype} {list(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+            raise FlashAttentionError(
+                FA_ERR_BAD_SHAPE,
+                f"{name} must be a contiguous float32 [Hkv = {heads_kv}] tensor, got {got}")
+
+
+def _check_scales_device(q, k_scale, v_scale):
+    for name, t in (("k_scale", k_scale), ("v_scale", v_scale)):
+        if t is not None and (not t.is_cuda or t.device != q.device):
+            raise FlashAttentionError(FA_ERR_NULL_POINTER, f"{name} must be a tensor on {q.device}")
+
+
+def _check_decode(q, k_cache, v_cache, kv_lens, out, k_scale=None, v_scale=None):
     """Raise FlashAttentionError unless q/out are contiguous [B,Hq,Sq,D] and
     k_cache/v_cache contiguous [B,Hkv,cap,D] device tensors of one 16-bit dtype
-    and device with Hq % Hkv == 0, and kv_lens (if given) is int32 [B] there.
+    (or both torch.float8_e4m3fn beside a 16-bit q, with optional float32
+    [Hkv] scales: returns True then) and device with Hq % Hkv == 0, and
+    kv_lens (if given) is int32 [B] there.
     Dtypes, ranks and shapes are checked before where the tensors live, so
     each rejection names its own cause whatever the device."""
     import torch
@@ -384,8 +446,9 @@ def _check_decode(q, k_cache, v_cache, kv_lens, out):
     if q.dtype not in (torch.float16, torch.bfloat16):
         raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"q must be float16 or bfloat16, got {q.dtype}")
     tensors = (("q", q), ("k_cache", k_cache), ("v_cache", v_cache), ("out", out))
+    kv8 = _kv8_caches(q, "k_cache", k_cache, "v_cache", v_cache, k_scale, v_scale)
     for name, t in tensors:
-        if t.dtype != q.dtype:
+        if t.dtype != q.dtype and not (kv8 and t is not out):
             raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be {q.dtype}, got {t.dtype}")
         if t.dim() != 4:
             raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be 4-D (BHSD)")
@@ -400,6 +463,7 @@ def _check_decode(q, k_cache, v_cache, kv_lens, out):
     if k_cache.shape[1] == 0 or q.shape[1] % k_cache.shape[1] != 0:
         raise FlashAttentionError(FA_ERR_BAD_SHAPE,
                                   f"heads_q {q.shape[1]} is not a multiple of heads_kv {k_cache.shape[1]}")
+    _check_scales(k_cache.shape[1], k_scale, v_scale)
     if kv_lens is not None:
         if kv_lens.dtype != torch.int32:
             raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"kv_lens must be int32, got {kv_lens.dtype}")
@@ -413,11 +477,15 @@ def _check_decode(q, k_cache, v_cache, kv_lens, out):
                                       f"{name} is on {t.device}, q on {q.device}: one device only")
     if kv_lens is not None and (not kv_lens.is_cuda or kv_lens.device != q.device):
         raise FlashAttentionError(FA_ERR_NULL_POINTER, f"kv_lens must be a tensor on {q.device}")
+    _check_scales_device(q, k_scale, v_scale)
+    return kv8
 
 
 def flash_attention_decode(q, k_cache, v_cache, kv_lens=None, causal: bool = True, out=None,
-                           return_lse: bool = False, num_splits: int = 0, stream=None):
-    """Decode attention over a K/V cache (fa_decode_f16 / fa_decode_bf16).
+                           return_lse: bool = False, num_splits: int = 0, stream=None,
+                           k_scale=None, v_scale=None):
+    """Decode attention over a K/V cache (fa_decode_f16 / fa_decode_bf16, or
+    fa_decode_kv8_* over an FP8 cache).
 
     q: [B, Hq, Sq, D] (1 <= Sq <= 16); k_cache, v_cache: [B, Hkv, cap, D] with
     Hq % Hkv == 0 (GQA / MQA); fp16 or bf16 contiguous device tensors of one
@@ -429,12 +497,18 @@ def flash_attention_decode(q, k_cache, v_cache, kv_lens=None, causal: bool = Tru
     return_lse.  Enqueued on ``stream`` (default: torch's current stream); no
     sync, graph-capturable; a split launch takes its workspace from the same
     per-(device, stream) buffer as :func:`flash_attention_fwd`.
+
+    FP8 cache: when k_cache and v_cache are both torch.float8_e4m3fn (q and
+    out stay 16-bit), K is read as k_scale[hkv] * k_cache and V as
+    v_scale[hkv] * v_cache; k_scale, v_scale: contiguous float32 [Hkv] tensors
+    on q's device (None: 1.0).  Their values are read on the device, so a
+    captured graph follows them.  Scales beside a 16-bit cache are an error.
     """
     import torch
 
     if out is None:
         out = torch.empty_like(q)
-    _check_decode(q, k_cache, v_cache, kv_lens, out)
+    kv8 = _check_decode(q, k_cache, v_cache, kv_lens, out, k_scale, v_scale)
     b, hq, sq, d = q.shape
     hkv, cap = k_cache.shape[1], k_cache.shape[2]
     lib = _lib or load_library()
@@ -444,7 +518,13 @@ def flash_attention_decode(q, k_cache, v_cache, kv_lens=None, causal: bool = Tru
     else:
         st = stream if isinstance(stream, int) else stream.cuda_stream
     lse = torch.empty((b, hq, sq), dtype=torch.float32, device=q.device) if return_lse else None
-    fn = lib.fa_decode_bf16 if q.dtype is torch.bfloat16 else lib.fa_decode_f16
+    if kv8:
+        fn = lib.fa_decode_kv8_bf16 if q.dtype is torch.bfloat16 else lib.fa_decode_kv8_f16
+        tail = (k_scale.data_ptr() if k_scale is not None else None,
+                v_scale.data_ptr() if v_scale is not None else None)
+    else:
+        fn = lib.fa_decode_bf16 if q.dtype is torch.bfloat16 else lib.fa_decode_f16
+        tail = ()
     with torch.cuda.device(dev):
         key = (dev, b, hq, hkv, sq, cap, d, int(num_splits))
         need = _DEC_NEED.get(key)
@@ -455,15 +535,16 @@ def flash_attention_decode(q, k_cache, v_cache, kv_lens=None, causal: bool = Tru
         rc = fn(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr(),
                 lse.data_ptr() if return_lse else None, b, hq, hkv, sq, cap, d,
                 kv_lens.data_ptr() if kv_lens is not None else None, int(bool(causal)),
-                int(num_splits), ws.data_ptr() if need else None, need, st)
+                int(num_splits), ws.data_ptr() if need else None, need, st, *tail)
     _check(rc)
     return (out, lse) if return_lse else out
 
 
-def _check_decode_paged(q, k_pages, v_pages, block_table, kv_lens, out):
+def _check_decode_paged(q, k_pages, v_pages, block_table, kv_lens, out, k_scale=None, v_scale=None):
     """Raise FlashAttentionError unless q/out are contiguous [B,Hq,Sq,D],
     k_pages/v_pages contiguous [num_pages,Hkv,page_size,D] pools of q's 16-bit
-    dtype with page_size % 64 == 0 and Hq % Hkv == 0, block_table a contiguous
+    dtype (or both torch.float8_e4m3fn, with optional float32 [Hkv] scales:
+    returns True then) with page_size % 64 == 0 and Hq % Hkv == 0, block_table a contiguous
     int32 [B,max_pages] tensor and kv_lens (if given) int32 [B], all on q's
     device.  Dtypes, ranks and shapes are checked before where the tensors
     live, so each rejection names its own cause whatever the device.  The
@@ -473,8 +554,9 @@ def _check_decode_paged(q, k_pages, v_pages, block_table, kv_lens, out):
     if q.dtype not in (torch.float16, torch.bfloat16):
         raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"q must be float16 or bfloat16, got {q.dtype}")
     tensors = (("q", q), ("k_pages", k_pages), ("v_pages", v_pages), ("out", out))
+    kv8 = _kv8_caches(q, "k_pages", k_pages, "v_pages", v_pages, k_scale, v_scale)
     for name, t in tensors:
-        if t.dtype != q.dtype:
+        if t.dtype != q.dtype and not (kv8 and t is not out):
             raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be {q.dtype}, got {t.dtype}")
         if t.dim() != 4:
             raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be 4-D")
@@ -494,6 +576,7 @@ def _check_decode_paged(q, k_pages, v_pages, block_table, kv_lens, out):
     if k_pages.shape[1] == 0 or q.shape[1] % k_pages.shape[1] != 0:
         raise FlashAttentionError(FA_ERR_BAD_SHAPE,
                                   f"heads_q {q.shape[1]} is not a multiple of heads_kv {k_pages.shape[1]}")
+    _check_scales(k_pages.shape[1], k_scale, v_scale)
     if block_table.dtype != torch.int32:
         raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"block_table must be int32, got {block_table.dtype}")
     if block_table.dim() != 2:
@@ -518,11 +601,15 @@ def _check_decode_paged(q, k_pages, v_pages, block_table, kv_lens, out):
         raise FlashAttentionError(FA_ERR_NULL_POINTER, f"block_table must be a tensor on {q.device}")
     if kv_lens is not None and (not kv_lens.is_cuda or kv_lens.device != q.device):
         raise FlashAttentionError(FA_ERR_NULL_POINTER, f"kv_lens must be a tensor on {q.device}")
+    _check_scales_device(q, k_scale, v_scale)
+    return kv8
 
 
 def flash_attention_decode_paged(q, k_pages, v_pages, block_table, kv_lens=None, causal: bool = True,
-                                 out=None, return_lse: bool = False, num_splits: int = 0, stream=None):
-    """Decode attention over a paged K/V cache (fa_decode_paged_f16 / _bf16).
+                                 out=None, return_lse: bool = False, num_splits: int = 0, stream=None,
+                                 k_scale=None, v_scale=None):
+    """Decode attention over a paged K/V cache (fa_decode_paged_f16 / _bf16, or
+    fa_decode_paged_kv8_* over an FP8 pool).
 
     q: [B, Hq, Sq, D] (1 <= Sq <= 16); k_pages, v_pages: the page pools,
     [num_pages, Hkv, page_size, D] (BHSD inside a page, the serving stacks'
@@ -536,13 +623,14 @@ def flash_attention_decode_paged(q, k_pages, v_pages, block_table, kv_lens=None,
     the pool reads as zero rows (include/fa_mi355x.h).  The other arguments,
     the return value and the contract (no sync, graph-capturable, the
     per-(device, stream) workspace) are those of :func:`flash_attention_decode`,
-    whose result on the gathered cache this one equals bit for bit.
+    whose result on the gathered cache this one equals bit for bit.  Pools of
+    torch.float8_e4m3fn with k_scale / v_scale: as for that function.
     """
     import torch
 
     if out is None:
         out = torch.empty_like(q)
-    _check_decode_paged(q, k_pages, v_pages, block_table, kv_lens, out)
+    kv8 = _check_decode_paged(q, k_pages, v_pages, block_table, kv_lens, out, k_scale, v_scale)
     b, hq, sq, d = q.shape
     npages, hkv, psz = k_pages.shape[0], k_pages.shape[1], k_pages.shape[2]
     mpp = block_table.shape[1]
@@ -553,7 +641,13 @@ def flash_attention_decode_paged(q, k_pages, v_pages, block_table, kv_lens=None,
     else:
         st = stream if isinstance(stream, int) else stream.cuda_stream
     lse = torch.empty((b, hq, sq), dtype=torch.float32, device=q.device) if return_lse else None
-    fn = lib.fa_decode_paged_bf16 if q.dtype is torch.bfloat16 else lib.fa_decode_paged_f16
+    if kv8:
+        fn = lib.fa_decode_paged_kv8_bf16 if q.dtype is torch.bfloat16 else lib.fa_decode_paged_kv8_f16
+        tail = (k_scale.data_ptr() if k_scale is not None else None,
+                v_scale.data_ptr() if v_scale is not None else None)
+    else:
+        fn = lib.fa_decode_paged_bf16 if q.dtype is torch.bfloat16 else lib.fa_decode_paged_f16
+        tail = ()
     with torch.cuda.device(dev):
         cap = mpp * psz
         need = 0
@@ -567,7 +661,7 @@ def flash_attention_decode_paged(q, k_pages, v_pages, block_table, kv_lens=None,
         rc = fn(q.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), out.data_ptr(),
                 lse.data_ptr() if return_lse else None, b, hq, hkv, sq, d, npages, psz,
                 block_table.data_ptr(), mpp, kv_lens.data_ptr() if kv_lens is not None else None,
-                int(bool(causal)), int(num_splits), ws.data_ptr() if need else None, need, st)
+                int(bool(causal)), int(num_splits), ws.data_ptr() if need else None, need, st, *tail)
     _check(rc)
     return (out, lse) if return_lse else out
 

@@ -5,6 +5,7 @@ rank 3: the wrapper that puts the kernel beside PyTorch SDPA on one box).
     o = torch.ops.fa_mi355x.fwd(q, k, v, causal=True)
     o = torch.ops.fa_mi355x.decode(q, k_cache, v_cache, kv_lens, causal=True)
     o = torch.ops.fa_mi355x.decode_paged(q, k_pages, v_pages, block_table, kv_lens, causal=True)
+    o = torch.ops.fa_mi355x.decode(q, k8_cache, v8_cache, kv_lens, k_scale=ks, v_scale=vs)  # FP8 cache
 
 ``q, k, v``: fp16 or bf16 ``[B, H, S, D]`` (D = 128 or 64) tensors on the GPU (BHSD, the
 reference layout, flash_attention.cu:119-122); returns a new tensor of the same shape and dtype.
@@ -64,25 +65,31 @@ fwd = torch.ops.fa_mi355x.fwd
 # decode(q [B,Hq,Sq,D], k_cache / v_cache [B,Hkv,cap,D], kv_lens int32 [B] or
 # None): fa_mi355x.flash_attention_decode behind the same kind of registration.
 # k_cache and v_cache must be contiguous (FlashAttentionError otherwise).
+# An FP8 cache (both torch.float8_e4m3fn) takes k_scale / v_scale, float32
+# [Hkv] or None (= 1.0); their values are read on the device.
 DECODE_OP_NAME = "fa_mi355x::decode"
 _LIB.define("decode(Tensor q, Tensor k_cache, Tensor v_cache, Tensor? kv_lens=None, "
-            "bool causal=True) -> Tensor")
+            "bool causal=True, Tensor? k_scale=None, Tensor? v_scale=None) -> Tensor")
 
 
-def _decode_gpu(q, k_cache, v_cache, kv_lens=None, causal: bool = True) -> torch.Tensor:
+def _decode_gpu(q, k_cache, v_cache, kv_lens=None, causal: bool = True, k_scale=None,
+                v_scale=None) -> torch.Tensor:
     _no_grad_needed(q, k_cache, v_cache)
     # the caches are taken as they are: a strided view (a slice of a larger
     # cache) raises instead of being copied, which would move the whole cache
     # once more than the kernel does
     return flash_attention_decode(q.contiguous(), k_cache, v_cache,
-                                  None if kv_lens is None else kv_lens.contiguous(), causal=causal)
+                                  None if kv_lens is None else kv_lens.contiguous(), causal=causal,
+                                  k_scale=k_scale, v_scale=v_scale)
 
 
-def _decode_cpu(q, k_cache, v_cache, kv_lens=None, causal: bool = True) -> torch.Tensor:
+def _decode_cpu(q, k_cache, v_cache, kv_lens=None, causal: bool = True, k_scale=None,
+                v_scale=None) -> torch.Tensor:
     raise ValueError("fa_mi355x::decode needs GPU tensors (no CPU path)")
 
 
-def _decode_fake(q, k_cache, v_cache, kv_lens=None, causal: bool = True) -> torch.Tensor:
+def _decode_fake(q, k_cache, v_cache, kv_lens=None, causal: bool = True, k_scale=None,
+                 v_scale=None) -> torch.Tensor:
     _no_grad_needed(q, k_cache, v_cache)
     torch._check(q.dim() == 4 and q.shape[-1] in (64, 128), lambda: "expected [B, Hq, Sq, 64|128]")
     torch._check(q.dtype in (torch.float16, torch.bfloat16), lambda: "expected fp16 or bf16")
@@ -105,21 +112,21 @@ _LIB.define("decode_paged(Tensor q, Tensor k_pages, Tensor v_pages, Tensor block
             "Tensor? kv_lens=None, bool causal=True) -> Tensor")
 
 
-def _decode_paged_gpu(q, k_pages, v_pages, block_table, kv_lens=None,
-                      causal: bool = True) -> torch.Tensor:
+def _decode_paged_gpu(q, k_pages, v_pages, block_table, kv_lens=None, causal: bool = True,
+                      k_scale=None, v_scale=None) -> torch.Tensor:
     _no_grad_needed(q, k_pages, v_pages)
     return flash_attention_decode_paged(q.contiguous(), k_pages, v_pages, block_table.contiguous(),
                                         None if kv_lens is None else kv_lens.contiguous(),
-                                        causal=causal)
+                                        causal=causal, k_scale=k_scale, v_scale=v_scale)
 
 
-def _decode_paged_cpu(q, k_pages, v_pages, block_table, kv_lens=None,
-                      causal: bool = True) -> torch.Tensor:
+def _decode_paged_cpu(q, k_pages, v_pages, block_table, kv_lens=None, causal: bool = True,
+                      k_scale=None, v_scale=None) -> torch.Tensor:
     raise ValueError("fa_mi355x::decode_paged needs GPU tensors (no CPU path)")
 
 
-def _decode_paged_fake(q, k_pages, v_pages, block_table, kv_lens=None,
-                       causal: bool = True) -> torch.Tensor:
+def _decode_paged_fake(q, k_pages, v_pages, block_table, kv_lens=None, causal: bool = True,
+                       k_scale=None, v_scale=None) -> torch.Tensor:
     _no_grad_needed(q, k_pages, v_pages)
     torch._check(q.dim() == 4 and q.shape[-1] in (64, 128), lambda: "expected [B, Hq, Sq, 64|128]")
     torch._check(q.dtype in (torch.float16, torch.bfloat16), lambda: "expected fp16 or bf16")
@@ -131,5 +138,19 @@ _LIB.impl("decode_paged", _decode_paged_gpu, "CUDA")
 _LIB.impl("decode_paged", torch.library.fallthrough_kernel, "Autograd")
 _LIB.impl("decode_paged", _decode_paged_cpu, "CPU")
 torch.library.register_fake(DECODE_PAGED_OP_NAME, _decode_paged_fake, lib=_LIB)
+
+# The FP8 pool's scales: the default overload's schema is pinned as it stands
+# (it takes FP8 pools too, with scales of 1.0), so k_scale / v_scale come in a
+# second overload with the same leading arguments.  A call through the packet
+# torch.ops.fa_mi355x.decode_paged(...) that names or passes a scale resolves
+# to it; every call the default overload accepts still resolves to the default.
+DECODE_PAGED_KV8_OP_NAME = "fa_mi355x::decode_paged.kv8"
+_LIB.define("decode_paged.kv8(Tensor q, Tensor k_pages, Tensor v_pages, Tensor block_table, "
+            "Tensor? kv_lens=None, bool causal=True, Tensor? k_scale=None, "
+            "Tensor? v_scale=None) -> Tensor")
+_LIB.impl("decode_paged.kv8", _decode_paged_gpu, "CUDA")
+_LIB.impl("decode_paged.kv8", torch.library.fallthrough_kernel, "Autograd")
+_LIB.impl("decode_paged.kv8", _decode_paged_cpu, "CPU")
+torch.library.register_fake(DECODE_PAGED_KV8_OP_NAME, _decode_paged_fake, lib=_LIB)
 
 decode_paged = torch.ops.fa_mi355x.decode_paged

@@ -24,6 +24,17 @@ second contiguous leg included so that every row carries its own A/A spread:
 the figure of record is paged_over_contig beside contig_aa.
 
     python3 tools/decode_bench.py --paged [--out profiles/decode_paged_bench.jsonl]
+
+--kv8 times the FP8-cache entries fa_decode_kv8_* against fa_decode_* on the
+same logical shape (run_kv8): the 16-bit cache and its E4M3 quantisation (one
+scale per K/V head), both captured into HIP graphs and replayed alternately
+16-bit / kv8 / 16-bit in one process, so every row carries its own A/A spread;
+the figure of record is kv8_over_kv16 beside kv16_aa, and kv8's own bytes per
+second against the copy rate.  Rows marked `paged` add fa_decode_paged_kv8_* on
+the same bytes as a randomly permuted pool, page sizes 64 and 256, in the same
+rotation.
+
+    python3 tools/decode_bench.py --kv8 [--out profiles/decode_kv8_bench.jsonl]
 """
 import argparse
 import json
@@ -310,24 +321,174 @@ def run_paged(row, page_size, cus, placement="random", rounds=9):
                 paged_share_of_copy_rate=round(kv_bytes / (med[1] * 1e-6) / COPY_RATE, 4))
 
 
+def kv8_shapes():
+    base = dict(hq=32, hkv=8, sq=1, d=128)
+    return [dict(base, name="B=64 len=8192", b=64, n=8192, paged=True),
+            dict(base, name="B=64 len=32768", b=64, n=32768),
+            dict(base, name="B=8 len=8192", b=8, n=8192, paged=True),
+            dict(base, name="B=1 len=32768", b=1, n=32768, paged=True),
+            dict(base, name="speculative: B=8 len=8192 Sq=4", b=8, n=8192, sq=4),
+            dict(base, name="head_dim 64: B=8 len=8192", b=8, n=8192, d=64),
+            dict(base, name="bf16: B=8 len=8192", b=8, n=8192, bf16=True)]
+
+
+def run_kv8(row, cus, rounds=9):
+    """The kv8 entry against the 16-bit entry on the same logical shape: us per
+    call from alternately replayed HIP graphs (16-bit, kv8, 16-bit again, then
+    the paged kv8 legs of rows that ask for them)."""
+    lib = fa_mi355x.load_library()
+    bf16 = bool(row.get("bf16"))
+    dt = torch.bfloat16 if bf16 else torch.float16
+    f8 = torch.float8_e4m3fn
+    b, hq, hkv, sq, d, cap = row["b"], row["hq"], row["hkv"], row["sq"], row["d"], row["n"]
+    kv16_bytes = 2 * b * hkv * cap * d * 2
+    kv8_bytes = kv16_bytes // 2
+    copies = max(1, min(32, -(-(512 << 20) // kv8_bytes)))  # the kv8 leg, too, streams >= 512 MiB
+    page_sizes = (64, 256) if row.get("paged") else ()
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    # values in [-1, 1) against scales of 2^-3 .. 2^-2: codes up to 8, every head its own scale
+    k_scale = torch.tensor([2.0 ** -(3 - (h & 1)) for h in range(hkv)], dtype=torch.float32, device="cuda")
+    v_scale = torch.tensor([2.0 ** -(2 + (h & 1)) for h in range(hkv)], dtype=torch.float32, device="cuda")
+
+    def rnd(*shape):
+        return (torch.rand(shape, generator=gen, device="cuda", dtype=torch.float32) * 2 - 1).to(dt)
+
+    def quant(x, scale):
+        return (x.float() / scale[None, :, None, None]).to(f8)
+
+    def pool(x, perm, ps):  # logical page (b, j) -> pool page perm[b * mpp + j]
+        mpp = cap // ps
+        out = torch.empty((b * mpp, hkv, ps, d), dtype=torch.uint8, device="cuda")
+        out[perm] = x.view(torch.uint8).view(b, hkv, mpp, ps, d).permute(0, 2, 1, 3, 4).reshape(
+            b * mpp, hkv, ps, d)
+        return out.view(f8)
+
+    ks, vs, k8s, v8s = [], [], [], []
+    pools = {ps: ([], [], []) for ps in page_sizes}
+    for _ in range(copies):
+        k, v = rnd(b, hkv, cap, d), rnd(b, hkv, cap, d)
+        k8, v8 = quant(k, k_scale), quant(v, v_scale)
+        ks.append(k), vs.append(v), k8s.append(k8), v8s.append(v8)
+        for ps in page_sizes:
+            npages = b * (cap // ps)
+            perm = torch.randperm(npages, generator=gen, device="cuda")
+            pools[ps][0].append(pool(k8, perm, ps))
+            pools[ps][1].append(pool(v8, perm, ps))
+            pools[ps][2].append(perm.view(b, cap // ps).to(torch.int32).contiguous())
+    q = rnd(b, hq, sq, d)
+    plan = fa_mi355x.decode_num_splits(b, hq, hkv, sq, cap, d)
+    need = lib.fa_decode_ws_bytes(b, hq, hkv, sq, cap, d, 0)
+    ws = torch.zeros(max(need, 1), dtype=torch.uint8, device="cuda")
+    wsp = ws.data_ptr() if need else None
+    outs = [torch.empty_like(q) for _ in range(2 + len(page_sizes))]
+    iters = 20 if kv16_bytes < (1 << 30) else 5
+    fn16 = lib.fa_decode_bf16 if bf16 else lib.fa_decode_f16
+    fn8 = lib.fa_decode_kv8_bf16 if bf16 else lib.fa_decode_kv8_f16
+    fnp8 = lib.fa_decode_paged_kv8_bf16 if bf16 else lib.fa_decode_paged_kv8_f16
+
+    def kv16(st):
+        for i in range(iters):
+            c = i % copies
+            rc = fn16(q.data_ptr(), ks[c].data_ptr(), vs[c].data_ptr(), outs[0].data_ptr(), None,
+                      b, hq, hkv, sq, cap, d, None, 1, 0, wsp, need, st)
+            assert rc == 0, rc
+
+    def kv8(st):
+        for i in range(iters):
+            c = i % copies
+            rc = fn8(q.data_ptr(), k8s[c].data_ptr(), v8s[c].data_ptr(), outs[1].data_ptr(), None,
+                     b, hq, hkv, sq, cap, d, None, 1, 0, wsp, need, st, k_scale.data_ptr(),
+                     v_scale.data_ptr())
+            assert rc == 0, rc
+
+    def paged8(j, ps):
+        kps, vps, tabs = pools[ps]
+
+        def fn(st):
+            for i in range(iters):
+                c = i % copies
+                rc = fnp8(q.data_ptr(), kps[c].data_ptr(), vps[c].data_ptr(), outs[2 + j].data_ptr(),
+                          None, b, hq, hkv, sq, d, kps[c].shape[0], ps, tabs[c].data_ptr(), cap // ps,
+                          None, 1, 0, wsp, need, st, k_scale.data_ptr(), v_scale.data_ptr())
+                assert rc == 0, rc
+        return fn
+
+    fns = [kv16, kv8] + [paged8(j, ps) for j, ps in enumerate(page_sizes)]
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):  # first-launch set-up outside the captures
+        for fn in fns:
+            fn(side.cuda_stream)
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    # every leg ran copy (iters - 1) % copies last: what the quantisation costs on this data,
+    # and the paged legs' bits against the contiguous kv8 leg's
+    quant_err = float((outs[1].float() - outs[0].float()).abs().max())
+    same = all(bool(torch.equal(outs[1], outs[2 + j])) for j in range(len(page_sizes)))
+    graphs = []
+    for fn in fns:
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            fn(torch.cuda.current_stream().cuda_stream)
+        g.replay()
+        graphs.append(g)
+    torch.cuda.synchronize()
+    legs = (0, 1, 0) + tuple(2 + j for j in range(len(page_sizes)))
+    ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+           for _ in range(rounds)] for _ in legs]
+    for r in range(rounds):
+        for j, gi in enumerate(legs):
+            ev[j][r][0].record()
+            graphs[gi].replay()
+            ev[j][r][1].record()
+    torch.cuda.synchronize()
+    ts = [sorted(a.elapsed_time(c) * 1e3 / iters for a, c in e) for e in ev]
+    med = [t[len(t) // 2] for t in ts]
+    rec = dict(name=row["name"], batch=b, heads_q=hq, heads_kv=hkv, seqlen_q=sq, head_dim=d,
+               dtype=str(dt).split(".")[-1], kv_len=cap, copies=copies, num_splits=plan,
+               kv16_bytes=kv16_bytes, kv8_bytes=kv8_bytes, rounds=rounds, iters=iters,
+               kv16_us=round(med[0], 2), kv8_us=round(med[1], 2), kv16b_us=round(med[2], 2),
+               kv16_min_us=round(min(ts[0][0], ts[2][0]), 2), kv16_max_us=round(max(ts[0][-1], ts[2][-1]), 2),
+               kv8_min_us=round(ts[1][0], 2), kv8_max_us=round(ts[1][-1], 2),
+               kv8_over_kv16=round(med[1] / med[0], 4), kv16_aa=round(med[2] / med[0], 4),
+               kv16_share_of_copy_rate=round(kv16_bytes / (med[0] * 1e-6) / COPY_RATE, 4),
+               kv8_gb_per_s=round(kv8_bytes / med[1] / 1e3, 1),
+               kv8_share_of_copy_rate=round(kv8_bytes / (med[1] * 1e-6) / COPY_RATE, 4),
+               max_abs_diff_kv8_vs_kv16=quant_err)
+    for j, ps in enumerate(page_sizes):
+        t = med[3 + j]
+        rec[f"paged{ps}_kv8_us"] = round(t, 2)
+        rec[f"paged{ps}_kv8_over_kv8"] = round(t / med[1], 4)
+        rec[f"paged{ps}_kv8_over_kv16"] = round(t / med[0], 4)
+    if page_sizes:
+        rec["paged_bit_identical"] = same
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="default profiles/decode_bench.jsonl "
-                    "(profiles/decode_paged_bench.jsonl with --paged)")
+                    "(profiles/decode_paged_bench.jsonl with --paged, "
+                    "profiles/decode_kv8_bench.jsonl with --kv8)")
     ap.add_argument("--quick", action="store_true", help="three rows only")
     ap.add_argument("--paged", action="store_true",
                     help="paged against contiguous decode, page sizes 64 and 256")
+    ap.add_argument("--kv8", action="store_true",
+                    help="the FP8-cache entries against the 16-bit ones on the same shapes")
     ap.add_argument("--placement", choices=("random", "identity"), default="random",
                     help="--paged: pool pages under a random permutation (default) or in logical order")
     args = ap.parse_args()
     if args.out is None:
         args.out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "profiles",
+                                "decode_kv8_bench.jsonl" if args.kv8 else
                                 "decode_paged_bench.jsonl" if args.paged else "decode_bench.jsonl")
     if not torch.cuda.is_available():
         sys.exit("decode_bench.py needs a GPU")
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    if args.paged:
+    if args.kv8:
+        jobs = [(run_kv8, (row, cus)) for row in kv8_shapes()]
+    elif args.paged:
         jobs = [(run_paged, (row, ps, cus, args.placement)) for row in paged_shapes() for ps in (64, 256)]
     else:
         jobs = [(run, (row, cus)) for row in shapes(args.quick)]

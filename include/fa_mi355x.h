@@ -261,6 +261,52 @@ int fa_decode_paged_bf16(const void* q, const void* k_pages, const void* v_pages
                          const int* kv_lens, int causal, int num_splits,
                          void* workspace, unsigned long long ws_bytes, void* hip_stream);
 
+/* Decode attention over an FP8 K/V cache: fa_decode_* and fa_decode_paged_*
+ * with K and V stored as OCP FP8 E4M3 (torch.float8_e4m3fn: one byte per
+ * element, no infinities, 0x7f / 0xff = NaN) and one fp32 scale per K/V head
+ * for K and one for V.  q and o stay fp16 (_f16) or bf16 (_bf16):
+ *   O[b,hq,t,:] = softmax(Q . (k_scale[hkv] * K8)^T / sqrt(D) [+ mask])
+ *                 (v_scale[hkv] * V8)
+ *   k, v      [batch][heads_kv][kv_capacity][head_dim] bytes, contiguous;
+ *   k_pages, v_pages  [num_pages][heads_kv][page_size][head_dim] bytes.
+ *   k_scale, v_scale  DEVICE float[heads_kv], or NULL (= 1.0 for every head).
+ *             Device arrays so that nothing syncs: a captured graph follows
+ *             values rewritten between replays.  A per-tensor scale is the
+ *             array filled with one value.
+ * Every other argument, the status codes, the order of the argument checks
+ * (all before any launch), the accepted capacities and page sizes, the split
+ * plan (fa_decode_num_splits) and the workspace (fa_decode_ws_bytes) are those
+ * of the 16-bit twin; one per-stream workspace serves all of them.
+ * The bytes are converted to the 16-bit type in registers, exactly (every
+ * finite E4M3 code is representable in fp16 and in bf16); k_scale enters the
+ * score scale (and through it the LSE), v_scale the final normalisation, both
+ * in fp32.  Rows past kv_lens[b], unmapped pages and out-of-pool page ids are
+ * never read, as for the 16-bit entries.  The paged entry's O and LSE are
+ * bit-identical to the contiguous kv8 entry's on the gathered cache with the
+ * same num_splits.  Writing (quantising) into the cache is the caller's. */
+int fa_decode_kv8_f16(const void* q, const void* k, const void* v, void* o, float* lse,
+                      int batch, int heads_q, int heads_kv, int seqlen_q, int kv_capacity,
+                      int head_dim, const int* kv_lens, int causal, int num_splits,
+                      void* workspace, unsigned long long ws_bytes, void* hip_stream,
+                      const float* k_scale, const float* v_scale);
+int fa_decode_kv8_bf16(const void* q, const void* k, const void* v, void* o, float* lse,
+                       int batch, int heads_q, int heads_kv, int seqlen_q, int kv_capacity,
+                       int head_dim, const int* kv_lens, int causal, int num_splits,
+                       void* workspace, unsigned long long ws_bytes, void* hip_stream,
+                       const float* k_scale, const float* v_scale);
+int fa_decode_paged_kv8_f16(const void* q, const void* k_pages, const void* v_pages, void* o,
+                            float* lse, int batch, int heads_q, int heads_kv, int seqlen_q,
+                            int head_dim, int num_pages, int page_size, const int* block_table,
+                            int max_pages_per_seq, const int* kv_lens, int causal, int num_splits,
+                            void* workspace, unsigned long long ws_bytes, void* hip_stream,
+                            const float* k_scale, const float* v_scale);
+int fa_decode_paged_kv8_bf16(const void* q, const void* k_pages, const void* v_pages, void* o,
+                             float* lse, int batch, int heads_q, int heads_kv, int seqlen_q,
+                             int head_dim, int num_pages, int page_size, const int* block_table,
+                             int max_pages_per_seq, const int* kv_lens, int causal, int num_splits,
+                             void* workspace, unsigned long long ws_bytes, void* hip_stream,
+                             const float* k_scale, const float* v_scale);
+
 /* The dispatcher's decision (ref tier table :620-661): config id used by
  * fa_fwd_f16 for this shape.  The _ws entries may run the causal split tier
  * instead: check fa_fwd_split_pieces() first (> 0: the split tier runs with
