@@ -1,13 +1,23 @@
-// Host-side geometry, split plan and workspace layout of the decode entries,
-// shared by fa_decode.hip (contiguous cache) and fa_decode_paged.hip (page
-// pool + block table), so that both cut a problem the same way and one
-// per-stream workspace serves either.
+// Host side of the decode entries of include/fa_mi355x.h, shared by the four
+// cache families (fa_decode.hip: contiguous, fa_decode_paged.hip: page pool +
+// block table, fa_decode_kv8.hip and fa_decode_paged_kv8.hip: the same two over
+// FP8 bytes): geometry, split plan and workspace layout, so that all cut a
+// problem the same way and one per-stream workspace serves any of them, then
+// the one entry body (decode_entry) and the one launcher under it.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include <math.h>
+#include <stdint.h>
+
 #include <algorithm>
 #include <atomic>
+#include <mutex>
+#include <type_traits>
+
+#include "fa_decode_kernel.hpp"
+#include "fa_mi355x.h"
 
 namespace fa {
 
@@ -91,6 +101,143 @@ inline void decode_set_workspace(Params& p, const DecodeGeom& ge, int ns, void* 
   p.ws_ctr = reinterpret_cast<unsigned*>(w);
   p.ws_lse = reinterpret_cast<float*>(w + kDecodeCtrBytes);
   p.ws_o = reinterpret_cast<float*>(w + kDecodeCtrBytes + decode_lse_bytes(ge, ns));
+}
+
+// One kernel instantiation: the once-per-device dynamic-LDS attribute (the
+// flag tables are this instantiation's own), then the launch.
+template <class T, int HDIM, int NB, bool PAGED, class P, class KV>
+static int decode_launch_inst(const P& p, unsigned grid, hipStream_t stream) {
+  constexpr int kLds = decode_lds_bytes<HDIM, NB>();
+  constexpr auto kernel = fa_decode_kernel<T, HDIM, NB, PAGED, P, KV>;
+  static std::once_flag flags[64];
+  static hipError_t errs[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return FA_ERR_HIP;
+  std::call_once(flags[dev], [dev] {
+    errs[dev] = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    kLds);
+  });
+  if (errs[dev] != hipSuccess) return FA_ERR_HIP;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), kLds, stream, p);
+  return hipGetLastError() == hipSuccess ? FA_OK : FA_ERR_LAUNCH;
+}
+
+template <class T, int HDIM, bool PAGED, bool KV8, class P>
+static int decode_launch_nb(int nb, const P& p, unsigned grid, hipStream_t stream) {
+  using KV = std::conditional_t<KV8, unsigned char, T>;
+  switch (nb) {
+    case 1: return decode_launch_inst<T, HDIM, 1, PAGED, P, KV>(p, grid, stream);
+    case 2: return decode_launch_inst<T, HDIM, 2, PAGED, P, KV>(p, grid, stream);
+    default: return decode_launch_inst<T, HDIM, 4, PAGED, P, KV>(p, grid, stream);
+  }
+}
+
+// what the paged entries take in place of kv_capacity
+struct DecodePages {
+  int num_pages, page_size;
+  const int* block_table;
+  int max_pages_per_seq;
+};
+
+// The body of all eight entries.  PAGED: `k` / `v` are the page pools, `pg`
+// describes them and kv_capacity (passed as 0) becomes max_pages_per_seq *
+// page_size; otherwise `pg` is unused.  KV8: the cache holds E4M3 bytes and
+// k_scale / v_scale go to the kernel; otherwise they are unused.  The twelve
+// kernels a <PAGED, KV8> pair can launch are instantiated from here.
+template <bool PAGED, bool KV8>
+static int decode_entry(int dtype, const void* q, const void* k, const void* v, void* o, float* lse,
+                        int batch, int heads_q, int heads_kv, int seqlen_q, int kv_capacity,
+                        int head_dim, const DecodePages& pg, const int* kv_lens, int causal,
+                        int num_splits, void* ws, unsigned long long ws_bytes, void* hip_stream,
+                        const float* k_scale, const float* v_scale) {
+  using P = std::conditional_t<PAGED, std::conditional_t<KV8, DecodePagedKv8Params, DecodePagedParams>,
+                               std::conditional_t<KV8, DecodeKv8Params, DecodeParams>>;
+  if (batch < 0 || heads_q < 0 || heads_kv < 0 || kv_capacity < 0 || head_dim < 0 || num_splits < 0)
+    return FA_ERR_BAD_SHAPE;
+  if (head_dim != 128 && head_dim != 64) return FA_ERR_UNSUPPORTED_HEAD_DIM;
+  if (seqlen_q < 1 || seqlen_q > 16) return FA_ERR_BAD_SHAPE;
+  if constexpr (PAGED) {
+    // a 64-key tile must not straddle two pages
+    if (pg.page_size <= 0 || pg.page_size % 64 != 0) return FA_ERR_BAD_SHAPE;
+    if (pg.num_pages <= 0 || pg.max_pages_per_seq < 0) return FA_ERR_BAD_SHAPE;
+    // a head's rows of one page are addressed through one buffer resource whose
+    // byte range (page_size * 2 * head_dim) is a 32-bit int.  The FP8 entries
+    // keep the 16-bit bound (their range is half that): both accept the same
+    // page sizes
+    if ((long long)pg.page_size * 2 * head_dim > 0x7fffffffLL) return FA_ERR_BAD_SHAPE;
+    // key indices (up to the end of the last tile) are 32-bit ints in the kernel
+    if ((long long)pg.max_pages_per_seq * pg.page_size > 0x7fffffffLL - 64) return FA_ERR_BAD_SHAPE;
+    kv_capacity = pg.max_pages_per_seq * pg.page_size;
+  }
+  if (batch == 0 || heads_q == 0) return FA_OK;
+  if (heads_kv == 0 || heads_q % heads_kv != 0) return FA_ERR_BAD_SHAPE;
+  if ((long long)batch * heads_q * seqlen_q > 0x7fffffffLL) return FA_ERR_BAD_SHAPE;
+  if constexpr (!PAGED) {
+    // a head's cache rows are addressed through one buffer resource whose byte
+    // range (cap * 2 * head_dim) is a 32-bit int.  The FP8 entries keep the
+    // 16-bit bound (their range is half that): both accept the same capacities
+    if ((long long)kv_capacity * 2 * head_dim > 0x7fffffffLL) return FA_ERR_BAD_SHAPE;
+    if (!kv_lens && causal && kv_capacity < seqlen_q && kv_capacity > 0) return FA_ERR_BAD_SHAPE;
+  }
+  hipStream_t stream = (hipStream_t)hip_stream;
+  const size_t nrow = (size_t)batch * heads_q * seqlen_q;
+  if (kv_capacity == 0) {
+    // rows but no keys: O = 0, LSE = -inf; nothing else runs
+    if (!o) return FA_ERR_NULL_POINTER;
+    return decode_fill_empty(o, lse, nrow, head_dim, stream) ? FA_OK : FA_ERR_HIP;
+  }
+  if (!q || !k || !v || !o || (PAGED && !pg.block_table)) return FA_ERR_NULL_POINTER;
+  const DecodeGeom ge = decode_geom(batch, heads_q, heads_kv, seqlen_q);
+  if (num_splits > kDecodeMaxSplits) return FA_ERR_BAD_CONFIG;
+  const int ns = num_splits > 0 ? num_splits : decode_plan(ge, kv_capacity);
+  if (ge.units * ns > 0x7fffffffLL) return FA_ERR_BAD_SHAPE;
+  if (ns > 1) {
+    // one arrival counter per unit in the 64-KB region (the plan splits only
+    // when units are fewer than CUs; a forced split of more units is refused)
+    if (ge.units > (long long)(kDecodeCtrBytes / 4)) return FA_ERR_BAD_CONFIG;
+    // the slabs take 16-B sc1 stores / loads: a 16-byte aligned workspace
+    if (!ws || ws_bytes < decode_ws_total(ge, head_dim, ns) || (reinterpret_cast<uintptr_t>(ws) & 15) != 0)
+      return FA_ERR_WORKSPACE;
+  }
+  P p = {};
+  p.q = q;
+  p.k = k;
+  p.v = v;
+  p.o = o;
+  p.lse = lse;
+  p.kv_lens = kv_lens;
+  p.hq = heads_q;
+  p.hkv = heads_kv;
+  p.sq = seqlen_q;
+  p.cap = kv_capacity;
+  p.group = ge.group;
+  p.rows = ge.rows;
+  p.rgroups = ge.rgroups;
+  p.num_splits = ns;
+  p.causal = causal ? 1 : 0;
+  p.c = 1.4426950408889634f / sqrtf((float)head_dim);
+  if (ns > 1) decode_set_workspace(p, ge, ns, ws);
+  if constexpr (PAGED) {
+    p.table = pg.block_table;
+    p.max_pages = pg.max_pages_per_seq;
+    p.num_pages = pg.num_pages;
+    p.tpp = pg.page_size / 64;
+    p.adv_pages = 4 / p.tpp;
+    p.adv_tiles = 4 % p.tpp;
+    using CacheElem = std::conditional_t<KV8, unsigned char, f16>;  // f16 and bf16: one size
+    p.head_bytes = (unsigned long long)pg.page_size * sizeof(CacheElem) * head_dim;
+    p.page_bytes = p.head_bytes * heads_kv;
+  }
+  if constexpr (KV8) {
+    p.k_scale = k_scale;
+    p.v_scale = v_scale;
+  }
+  const unsigned grid = (unsigned)(ge.units * ns);
+  if (dtype == FA_DTYPE_BF16)
+    return head_dim == 128 ? decode_launch_nb<__bf16, 128, PAGED, KV8>(ge.nb, p, grid, stream)
+                           : decode_launch_nb<__bf16, 64, PAGED, KV8>(ge.nb, p, grid, stream);
+  return head_dim == 128 ? decode_launch_nb<f16, 128, PAGED, KV8>(ge.nb, p, grid, stream)
+                         : decode_launch_nb<f16, 64, PAGED, KV8>(ge.nb, p, grid, stream);
 }
 
 }  // namespace fa

@@ -412,10 +412,45 @@ def _kv8_caches(q, kname, k, vname, v, k_scale, v_scale) -> bool:
     return False
 
 
-def _check_scales(heads_kv, k_scale, v_scale):
-    """Each scale (if given) is a contiguous float32 [Hkv] tensor."""
+def _check_scales_device(q, k_scale, v_scale):
+    for name, t in (("k_scale", k_scale), ("v_scale", v_scale)):
+        if t is not None and (not t.is_cuda or t.device != q.device):
+            raise FlashAttentionError(FA_ERR_NULL_POINTER, f"{name} must be a tensor on {q.device}")
+
+
+def _check_decode_head(q, kname, k, vname, v, out, k_scale, v_scale, layout):
+    """What both decode checks begin with: q's dtype, the cache pairing
+    (:func:`_kv8_caches`, whose answer is returned), then dtype, rank and
+    contiguity of q, the caches and out in that order, and out's shape.
+    `layout` is what the family's rank and contiguity messages end in."""
     import torch
 
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"q must be float16 or bfloat16, got {q.dtype}")
+    kv8 = _kv8_caches(q, kname, k, vname, v, k_scale, v_scale)
+    for name, t in (("q", q), (kname, k), (vname, v), ("out", out)):
+        if t.dtype != q.dtype and not (kv8 and t is not out):
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be {q.dtype}, got {t.dtype}")
+        if t.dim() != 4:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be 4-D{layout}")
+        if not t.is_contiguous():
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be contiguous{layout}")
+    if out.shape != q.shape:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, "out must be [B,Hq,Sq,D] like q")
+    return kv8
+
+
+def _check_decode_tail(q, kname, k, vname, v, out, k_scale, v_scale, block_table, kv_lens):
+    """What both decode checks end with, after the family's own shape checks:
+    Hq % Hkv, each scale (if given) a contiguous float32 [Hkv] tensor, the
+    block table (paged only: None otherwise), kv_lens, and then where all of
+    them live."""
+    import torch
+
+    heads_kv = k.shape[1]
+    if heads_kv == 0 or q.shape[1] % heads_kv != 0:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE,
+                                  f"heads_q {q.shape[1]} is not a multiple of heads_kv {heads_kv}")
     for name, t in (("k_scale", k_scale), ("v_scale", v_scale)):
         if t is None:
             continue
@@ -425,12 +460,32 @@ def _check_scales(heads_kv, k_scale, v_scale):
             raise FlashAttentionError(
                 FA_ERR_BAD_SHAPE,
                 f"{name} must be a contiguous float32 [Hkv = {heads_kv}] tensor, got {got}")
-
-
-def _check_scales_device(q, k_scale, v_scale):
-    for name, t in (("k_scale", k_scale), ("v_scale", v_scale)):
+    if block_table is not None:
+        if block_table.dtype != torch.int32:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE,
+                                      f"block_table must be int32, got {block_table.dtype}")
+        if block_table.dim() != 2:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, "block_table must be 2-D [B, max_pages_per_seq]")
+        if block_table.shape[0] != q.shape[0]:
+            raise FlashAttentionError(
+                FA_ERR_BAD_SHAPE, f"block_table has {block_table.shape[0]} rows, q a batch of {q.shape[0]}")
+        if not block_table.is_contiguous():
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, "block_table must be contiguous")
+    if kv_lens is not None:
+        if kv_lens.dtype != torch.int32:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"kv_lens must be int32, got {kv_lens.dtype}")
+        if kv_lens.dim() != 1 or kv_lens.shape[0] != q.shape[0] or not kv_lens.is_contiguous():
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, "kv_lens must be a contiguous [B] tensor")
+    for name, t in (("q", q), (kname, k), (vname, v), ("out", out)):
+        if not t.is_cuda:
+            raise FlashAttentionError(FA_ERR_NULL_POINTER, f"{name} must be a device tensor")
+        if t.device != q.device:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE,
+                                      f"{name} is on {t.device}, q on {q.device}: one device only")
+    for name, t in (("block_table", block_table), ("kv_lens", kv_lens)):
         if t is not None and (not t.is_cuda or t.device != q.device):
             raise FlashAttentionError(FA_ERR_NULL_POINTER, f"{name} must be a tensor on {q.device}")
+    _check_scales_device(q, k_scale, v_scale)
 
 
 def _check_decode(q, k_cache, v_cache, kv_lens, out, k_scale=None, v_scale=None):
@@ -441,44 +496,92 @@ def _check_decode(q, k_cache, v_cache, kv_lens, out, k_scale=None, v_scale=None)
     kv_lens (if given) is int32 [B] there.
     Dtypes, ranks and shapes are checked before where the tensors live, so
     each rejection names its own cause whatever the device."""
-    import torch
-
-    if q.dtype not in (torch.float16, torch.bfloat16):
-        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"q must be float16 or bfloat16, got {q.dtype}")
-    tensors = (("q", q), ("k_cache", k_cache), ("v_cache", v_cache), ("out", out))
-    kv8 = _kv8_caches(q, "k_cache", k_cache, "v_cache", v_cache, k_scale, v_scale)
-    for name, t in tensors:
-        if t.dtype != q.dtype and not (kv8 and t is not out):
-            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be {q.dtype}, got {t.dtype}")
-        if t.dim() != 4:
-            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be 4-D (BHSD)")
-        if not t.is_contiguous():
-            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be contiguous (BHSD)")
-    if out.shape != q.shape:
-        raise FlashAttentionError(FA_ERR_BAD_SHAPE, "out must be [B,Hq,Sq,D] like q")
+    kv8 = _check_decode_head(q, "k_cache", k_cache, "v_cache", v_cache, out, k_scale, v_scale, " (BHSD)")
     if k_cache.shape != v_cache.shape:
         raise FlashAttentionError(FA_ERR_BAD_SHAPE, "k_cache and v_cache must have one shape")
     if k_cache.shape[0] != q.shape[0] or k_cache.shape[3] != q.shape[3]:
         raise FlashAttentionError(FA_ERR_BAD_SHAPE, "q and the caches must agree in batch and head_dim")
-    if k_cache.shape[1] == 0 or q.shape[1] % k_cache.shape[1] != 0:
-        raise FlashAttentionError(FA_ERR_BAD_SHAPE,
-                                  f"heads_q {q.shape[1]} is not a multiple of heads_kv {k_cache.shape[1]}")
-    _check_scales(k_cache.shape[1], k_scale, v_scale)
-    if kv_lens is not None:
-        if kv_lens.dtype != torch.int32:
-            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"kv_lens must be int32, got {kv_lens.dtype}")
-        if kv_lens.dim() != 1 or kv_lens.shape[0] != q.shape[0] or not kv_lens.is_contiguous():
-            raise FlashAttentionError(FA_ERR_BAD_SHAPE, "kv_lens must be a contiguous [B] tensor")
-    for name, t in tensors:
-        if not t.is_cuda:
-            raise FlashAttentionError(FA_ERR_NULL_POINTER, f"{name} must be a device tensor")
-        if t.device != q.device:
-            raise FlashAttentionError(FA_ERR_BAD_SHAPE,
-                                      f"{name} is on {t.device}, q on {q.device}: one device only")
-    if kv_lens is not None and (not kv_lens.is_cuda or kv_lens.device != q.device):
-        raise FlashAttentionError(FA_ERR_NULL_POINTER, f"kv_lens must be a tensor on {q.device}")
-    _check_scales_device(q, k_scale, v_scale)
+    _check_decode_tail(q, "k_cache", k_cache, "v_cache", v_cache, out, k_scale, v_scale, None, kv_lens)
     return kv8
+
+
+def _check_decode_paged(q, k_pages, v_pages, block_table, kv_lens, out, k_scale=None, v_scale=None):
+    """Raise FlashAttentionError unless q/out are contiguous [B,Hq,Sq,D],
+    k_pages/v_pages contiguous [num_pages,Hkv,page_size,D] pools of q's 16-bit
+    dtype (or both torch.float8_e4m3fn, with optional float32 [Hkv] scales:
+    returns True then) with page_size % 64 == 0 and Hq % Hkv == 0, block_table a contiguous
+    int32 [B,max_pages] tensor and kv_lens (if given) int32 [B], all on q's
+    device.  Dtypes, ranks and shapes are checked before where the tensors
+    live, so each rejection names its own cause whatever the device.  The
+    table's and the lengths' VALUES are not looked at (no sync)."""
+    kv8 = _check_decode_head(q, "k_pages", k_pages, "v_pages", v_pages, out, k_scale, v_scale, "")
+    if k_pages.shape != v_pages.shape:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, "k_pages and v_pages must have one shape")
+    if k_pages.shape[3] != q.shape[3]:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, "q and the page pools must agree in head_dim")
+    if k_pages.shape[0] == 0:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, "the page pools hold no page")
+    if k_pages.shape[2] == 0 or k_pages.shape[2] % 64 != 0:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE,
+                                  f"page_size {k_pages.shape[2]} is not a positive multiple of 64")
+    _check_decode_tail(q, "k_pages", k_pages, "v_pages", v_pages, out, k_scale, v_scale, block_table,
+                       kv_lens)
+    return kv8
+
+
+_DEC_ENTRY = {}  # (paged, kv8, bf16) -> the C entry
+
+
+def _decode_call(kv8, q, k, v, out, block_table, kv_lens, causal, return_lse, num_splits, stream,
+                 k_scale, v_scale):
+    """The call of both decode functions after their checks: the stream, the
+    optional LSE, the split workspace and the C entry of q's dtype.
+    block_table: None when k, v are a contiguous cache (the fa_decode_*
+    entries), the table when they are page pools (the fa_decode_paged_*
+    entries); kv8: the _kv8 entries, which also take the two scales."""
+    import torch
+
+    b, hq, sq, d = q.shape
+    hkv, cap = k.shape[1], k.shape[2]
+    paged = block_table is not None
+    if paged:
+        npages, psz, mpp = k.shape[0], cap, block_table.shape[1]
+        cap = mpp * psz
+        cache = (d, npages, psz, block_table.data_ptr(), mpp)
+    else:
+        cache = (cap, d)
+    lib = _lib or load_library()
+    which = (paged, kv8, q.dtype is torch.bfloat16)
+    fn = _DEC_ENTRY.get(which)
+    if fn is None:
+        fn = _DEC_ENTRY[which] = getattr(lib, "fa_decode" + ("_paged" if paged else "")
+                                         + ("_kv8" if kv8 else "") + ("_bf16" if which[2] else "_f16"))
+    tail = ()
+    if kv8:
+        tail = (k_scale.data_ptr() if k_scale is not None else None,
+                v_scale.data_ptr() if v_scale is not None else None)
+    dev = q.device.index
+    if stream is None:
+        st = torch._C._cuda_getCurrentRawStream(dev)
+    else:
+        st = stream if isinstance(stream, int) else stream.cuda_stream
+    lse = torch.empty((b, hq, sq), dtype=torch.float32, device=q.device) if return_lse else None
+    ns = int(num_splits)
+    with torch.cuda.device(dev):
+        need = 0
+        if not paged or cap <= 0x7fffffff - 64:  # (past it the paged entry itself refuses the shape)
+            key = (dev, b, hq, hkv, sq, cap, d, ns)
+            need = _DEC_NEED.get(key)
+            if need is None:
+                need = lib.fa_decode_ws_bytes(b, hq, hkv, sq, cap, d, ns)
+                _DEC_NEED[key] = need
+        ws = _workspace(need, dev, st) if need else None
+        rc = fn(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
+                lse.data_ptr() if return_lse else None, b, hq, hkv, sq, *cache,
+                kv_lens.data_ptr() if kv_lens is not None else None, int(bool(causal)), ns,
+                ws.data_ptr() if need else None, need, st, *tail)
+    _check(rc)
+    return (out, lse) if return_lse else out
 
 
 def flash_attention_decode(q, k_cache, v_cache, kv_lens=None, causal: bool = True, out=None,
@@ -504,105 +607,13 @@ def flash_attention_decode(q, k_cache, v_cache, kv_lens=None, causal: bool = Tru
     on q's device (None: 1.0).  Their values are read on the device, so a
     captured graph follows them.  Scales beside a 16-bit cache are an error.
     """
-    import torch
-
     if out is None:
+        import torch
+
         out = torch.empty_like(q)
     kv8 = _check_decode(q, k_cache, v_cache, kv_lens, out, k_scale, v_scale)
-    b, hq, sq, d = q.shape
-    hkv, cap = k_cache.shape[1], k_cache.shape[2]
-    lib = _lib or load_library()
-    dev = q.device.index
-    if stream is None:
-        st = torch._C._cuda_getCurrentRawStream(dev)
-    else:
-        st = stream if isinstance(stream, int) else stream.cuda_stream
-    lse = torch.empty((b, hq, sq), dtype=torch.float32, device=q.device) if return_lse else None
-    if kv8:
-        fn = lib.fa_decode_kv8_bf16 if q.dtype is torch.bfloat16 else lib.fa_decode_kv8_f16
-        tail = (k_scale.data_ptr() if k_scale is not None else None,
-                v_scale.data_ptr() if v_scale is not None else None)
-    else:
-        fn = lib.fa_decode_bf16 if q.dtype is torch.bfloat16 else lib.fa_decode_f16
-        tail = ()
-    with torch.cuda.device(dev):
-        key = (dev, b, hq, hkv, sq, cap, d, int(num_splits))
-        need = _DEC_NEED.get(key)
-        if need is None:
-            need = lib.fa_decode_ws_bytes(b, hq, hkv, sq, cap, d, int(num_splits))
-            _DEC_NEED[key] = need
-        ws = _workspace(need, dev, st) if need else None
-        rc = fn(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr(),
-                lse.data_ptr() if return_lse else None, b, hq, hkv, sq, cap, d,
-                kv_lens.data_ptr() if kv_lens is not None else None, int(bool(causal)),
-                int(num_splits), ws.data_ptr() if need else None, need, st, *tail)
-    _check(rc)
-    return (out, lse) if return_lse else out
-
-
-def _check_decode_paged(q, k_pages, v_pages, block_table, kv_lens, out, k_scale=None, v_scale=None):
-    """Raise FlashAttentionError unless q/out are contiguous [B,Hq,Sq,D],
-    k_pages/v_pages contiguous [num_pages,Hkv,page_size,D] pools of q's 16-bit
-    dtype (or both torch.float8_e4m3fn, with optional float32 [Hkv] scales:
-    returns True then) with page_size % 64 == 0 and Hq % Hkv == 0, block_table a contiguous
-    int32 [B,max_pages] tensor and kv_lens (if given) int32 [B], all on q's
-    device.  Dtypes, ranks and shapes are checked before where the tensors
-    live, so each rejection names its own cause whatever the device.  The
-    table's and the lengths' VALUES are not looked at (no sync)."""
-    import torch
-
-    if q.dtype not in (torch.float16, torch.bfloat16):
-        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"q must be float16 or bfloat16, got {q.dtype}")
-    tensors = (("q", q), ("k_pages", k_pages), ("v_pages", v_pages), ("out", out))
-    kv8 = _kv8_caches(q, "k_pages", k_pages, "v_pages", v_pages, k_scale, v_scale)
-    for name, t in tensors:
-        if t.dtype != q.dtype and not (kv8 and t is not out):
-            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be {q.dtype}, got {t.dtype}")
-        if t.dim() != 4:
-            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be 4-D")
-        if not t.is_contiguous():
-            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be contiguous")
-    if out.shape != q.shape:
-        raise FlashAttentionError(FA_ERR_BAD_SHAPE, "out must be [B,Hq,Sq,D] like q")
-    if k_pages.shape != v_pages.shape:
-        raise FlashAttentionError(FA_ERR_BAD_SHAPE, "k_pages and v_pages must have one shape")
-    if k_pages.shape[3] != q.shape[3]:
-        raise FlashAttentionError(FA_ERR_BAD_SHAPE, "q and the page pools must agree in head_dim")
-    if k_pages.shape[0] == 0:
-        raise FlashAttentionError(FA_ERR_BAD_SHAPE, "the page pools hold no page")
-    if k_pages.shape[2] == 0 or k_pages.shape[2] % 64 != 0:
-        raise FlashAttentionError(FA_ERR_BAD_SHAPE,
-                                  f"page_size {k_pages.shape[2]} is not a positive multiple of 64")
-    if k_pages.shape[1] == 0 or q.shape[1] % k_pages.shape[1] != 0:
-        raise FlashAttentionError(FA_ERR_BAD_SHAPE,
-                                  f"heads_q {q.shape[1]} is not a multiple of heads_kv {k_pages.shape[1]}")
-    _check_scales(k_pages.shape[1], k_scale, v_scale)
-    if block_table.dtype != torch.int32:
-        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"block_table must be int32, got {block_table.dtype}")
-    if block_table.dim() != 2:
-        raise FlashAttentionError(FA_ERR_BAD_SHAPE, "block_table must be 2-D [B, max_pages_per_seq]")
-    if block_table.shape[0] != q.shape[0]:
-        raise FlashAttentionError(FA_ERR_BAD_SHAPE,
-                                  f"block_table has {block_table.shape[0]} rows, q a batch of {q.shape[0]}")
-    if not block_table.is_contiguous():
-        raise FlashAttentionError(FA_ERR_BAD_SHAPE, "block_table must be contiguous")
-    if kv_lens is not None:
-        if kv_lens.dtype != torch.int32:
-            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"kv_lens must be int32, got {kv_lens.dtype}")
-        if kv_lens.dim() != 1 or kv_lens.shape[0] != q.shape[0] or not kv_lens.is_contiguous():
-            raise FlashAttentionError(FA_ERR_BAD_SHAPE, "kv_lens must be a contiguous [B] tensor")
-    for name, t in tensors:
-        if not t.is_cuda:
-            raise FlashAttentionError(FA_ERR_NULL_POINTER, f"{name} must be a device tensor")
-        if t.device != q.device:
-            raise FlashAttentionError(FA_ERR_BAD_SHAPE,
-                                      f"{name} is on {t.device}, q on {q.device}: one device only")
-    if not block_table.is_cuda or block_table.device != q.device:
-        raise FlashAttentionError(FA_ERR_NULL_POINTER, f"block_table must be a tensor on {q.device}")
-    if kv_lens is not None and (not kv_lens.is_cuda or kv_lens.device != q.device):
-        raise FlashAttentionError(FA_ERR_NULL_POINTER, f"kv_lens must be a tensor on {q.device}")
-    _check_scales_device(q, k_scale, v_scale)
-    return kv8
+    return _decode_call(kv8, q, k_cache, v_cache, out, None, kv_lens, causal, return_lse, num_splits,
+                        stream, k_scale, v_scale)
 
 
 def flash_attention_decode_paged(q, k_pages, v_pages, block_table, kv_lens=None, causal: bool = True,
@@ -626,44 +637,13 @@ def flash_attention_decode_paged(q, k_pages, v_pages, block_table, kv_lens=None,
     whose result on the gathered cache this one equals bit for bit.  Pools of
     torch.float8_e4m3fn with k_scale / v_scale: as for that function.
     """
-    import torch
-
     if out is None:
+        import torch
+
         out = torch.empty_like(q)
     kv8 = _check_decode_paged(q, k_pages, v_pages, block_table, kv_lens, out, k_scale, v_scale)
-    b, hq, sq, d = q.shape
-    npages, hkv, psz = k_pages.shape[0], k_pages.shape[1], k_pages.shape[2]
-    mpp = block_table.shape[1]
-    lib = _lib or load_library()
-    dev = q.device.index
-    if stream is None:
-        st = torch._C._cuda_getCurrentRawStream(dev)
-    else:
-        st = stream if isinstance(stream, int) else stream.cuda_stream
-    lse = torch.empty((b, hq, sq), dtype=torch.float32, device=q.device) if return_lse else None
-    if kv8:
-        fn = lib.fa_decode_paged_kv8_bf16 if q.dtype is torch.bfloat16 else lib.fa_decode_paged_kv8_f16
-        tail = (k_scale.data_ptr() if k_scale is not None else None,
-                v_scale.data_ptr() if v_scale is not None else None)
-    else:
-        fn = lib.fa_decode_paged_bf16 if q.dtype is torch.bfloat16 else lib.fa_decode_paged_f16
-        tail = ()
-    with torch.cuda.device(dev):
-        cap = mpp * psz
-        need = 0
-        if cap <= 0x7fffffff - 64:  # (past it the entry itself refuses the shape)
-            key = (dev, b, hq, hkv, sq, cap, d, int(num_splits))
-            need = _DEC_NEED.get(key)
-            if need is None:
-                need = lib.fa_decode_ws_bytes(b, hq, hkv, sq, cap, d, int(num_splits))
-                _DEC_NEED[key] = need
-        ws = _workspace(need, dev, st) if need else None
-        rc = fn(q.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), out.data_ptr(),
-                lse.data_ptr() if return_lse else None, b, hq, hkv, sq, d, npages, psz,
-                block_table.data_ptr(), mpp, kv_lens.data_ptr() if kv_lens is not None else None,
-                int(bool(causal)), int(num_splits), ws.data_ptr() if need else None, need, st, *tail)
-    _check(rc)
-    return (out, lse) if return_lse else out
+    return _decode_call(kv8, q, k_pages, v_pages, out, block_table, kv_lens, causal, return_lse,
+                        num_splits, stream, k_scale, v_scale)
 
 
 def splitkv_buffers(batch: int, heads: int, seq_len: int, num_splits: int, device="cuda"):

@@ -14,7 +14,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ("fa_decode_f16", "fa_decode_bf16", "fa_decode_num_splits", "fa_decode_ws_bytes")
-MAX_SPLITS = 64  # the plan's upper cap (csrc/fa_decode.hip kDecodeMaxSplits)
+MAX_SPLITS = 64  # the plan's upper cap (csrc/fa_decode_host.hpp kDecodeMaxSplits)
 
 
 def _fa():
@@ -76,6 +76,47 @@ def test_argument_checks():
         # empty problems: nothing to do, nothing launched, no pointer looked at
         assert _call(fn, None, None, None, None, 0, 8, 2, 1, 1024, 128) == fa.FA_OK
         assert _call(fn, None, None, None, None, 1, 0, 0, 1, 1024, 128) == fa.FA_OK
+
+
+def test_eight_entries_answer_shared_arguments_alike():
+    """The contiguous, paged, FP8 and paged FP8 entries (f16 and bf16 each) run
+    one host body (csrc/fa_decode_host.hpp): a violation of an argument they
+    share gets the same status from all eight, in the same precedence.  Every
+    pointer is NULL, so nothing can launch; the family's own arguments are valid
+    (kv_capacity 256, or 4 pages of 64 keys with 4 table entries per row)."""
+    fa = _fa()
+    lib = fa.load_library()
+    base = dict(batch=2, heads_q=8, heads_kv=2, seqlen_q=1, head_dim=128, num_splits=0)
+    shape, dim, ok, null = (fa.FA_ERR_BAD_SHAPE, fa.FA_ERR_UNSUPPORTED_HEAD_DIM, fa.FA_OK,
+                            fa.FA_ERR_NULL_POINTER)
+    rows = [({name: -1}, shape) for name in ("batch", "heads_q", "heads_kv", "head_dim", "num_splits")]
+    rows += [
+        (dict(head_dim=96), dim), (dict(head_dim=0), dim),
+        (dict(seqlen_q=0), shape), (dict(seqlen_q=17), shape),
+        (dict(batch=0), ok), (dict(heads_q=0), ok),
+        (dict(heads_kv=0), shape), (dict(heads_kv=3), shape),
+        (dict(batch=1 << 20, heads_q=1 << 12, heads_kv=1), shape),  # rows past INT_MAX
+        ({}, null),
+        # precedence
+        (dict(head_dim=96, seqlen_q=0), dim),
+        (dict(batch=0, seqlen_q=17), shape),
+        (dict(batch=0, heads_kv=0), ok),
+    ]
+
+    def statuses(batch, heads_q, heads_kv, seqlen_q, head_dim, num_splits):
+        n5, bhhs = (None,) * 5, (batch, heads_q, heads_kv, seqlen_q)
+        end = (None, 1, num_splits, None, 0, None)  # kv_lens, causal, num_splits, ws, ws_bytes, stream
+        contig = n5 + bhhs + (256, head_dim) + end
+        # head_dim, num_pages, page_size, block_table, max_pages_per_seq
+        paged = n5 + bhhs + (head_dim, 4, 64, None, 4) + end
+        return [getattr(lib, "fa_decode" + fam + dt)(*args)
+                for fam, args in (("", contig), ("_paged", paged), ("_kv8", contig + (None, None)),
+                                  ("_paged_kv8", paged + (None, None)))
+                for dt in ("_f16", "_bf16")]
+
+    for change, want in rows:
+        got = statuses(**dict(base, **change))
+        assert len(got) == 8 and got == [want] * 8, (change, want, got)
 
 
 def test_split_plan():
