@@ -58,6 +58,12 @@ EXPORTED_SYMBOLS = (
     "fa_decode_kv8_bf16",
     "fa_decode_paged_kv8_f16",
     "fa_decode_paged_kv8_bf16",
+    "fa_cache_append_16",
+    "fa_cache_append_paged_16",
+    "fa_cache_append_kv8_f16",
+    "fa_cache_append_kv8_bf16",
+    "fa_cache_append_paged_kv8_f16",
+    "fa_cache_append_paged_kv8_bf16",
     "fa_select_config",
     "fa_num_configs",
     "fa_config_info",
@@ -171,6 +177,15 @@ def load_library() -> ctypes.CDLL:
     for fn in (lib.fa_decode_paged_kv8_f16, lib.fa_decode_paged_kv8_bf16):
         fn.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, vp, i, vp, i, i, vp, ull, vp, vp, vp]
         fn.restype = i
+    lib.fa_cache_append_16.argtypes = [vp, vp, vp, vp, i, i, i, i, i, vp, vp, vp]
+    lib.fa_cache_append_paged_16.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, vp, i, vp, vp, vp]
+    for fn in (lib.fa_cache_append_kv8_f16, lib.fa_cache_append_kv8_bf16):
+        fn.argtypes = lib.fa_cache_append_16.argtypes + [vp, vp]
+    for fn in (lib.fa_cache_append_paged_kv8_f16, lib.fa_cache_append_paged_kv8_bf16):
+        fn.argtypes = lib.fa_cache_append_paged_16.argtypes + [vp, vp]
+    for name in EXPORTED_SYMBOLS:
+        if name.startswith("fa_cache_append"):
+            getattr(lib, name).restype = i
     lib.fa_decode_num_splits.argtypes = [i, i, i, i, i, i]
     lib.fa_decode_num_splits.restype = i
     lib.fa_decode_ws_bytes.argtypes = [i, i, i, i, i, i, i]
@@ -440,11 +455,13 @@ def _check_decode_head(q, kname, k, vname, v, out, k_scale, v_scale, layout):
     return kv8
 
 
-def _check_decode_tail(q, kname, k, vname, v, out, k_scale, v_scale, block_table, kv_lens):
+def _check_decode_tail(q, kname, k, vname, v, out, k_scale, v_scale, block_table, kv_lens,
+                       qname="q", oname="out"):
     """What both decode checks end with, after the family's own shape checks:
     Hq % Hkv, each scale (if given) a contiguous float32 [Hkv] tensor, the
     block table (paged only: None otherwise), kv_lens, and then where all of
-    them live."""
+    them live.  The append checks end with it too, with k_new and v_new
+    (`qname`, `oname`) in the places of q and out."""
     import torch
 
     heads_kv = k.shape[1]
@@ -468,7 +485,8 @@ def _check_decode_tail(q, kname, k, vname, v, out, k_scale, v_scale, block_table
             raise FlashAttentionError(FA_ERR_BAD_SHAPE, "block_table must be 2-D [B, max_pages_per_seq]")
         if block_table.shape[0] != q.shape[0]:
             raise FlashAttentionError(
-                FA_ERR_BAD_SHAPE, f"block_table has {block_table.shape[0]} rows, q a batch of {q.shape[0]}")
+                FA_ERR_BAD_SHAPE,
+                f"block_table has {block_table.shape[0]} rows, {qname} a batch of {q.shape[0]}")
         if not block_table.is_contiguous():
             raise FlashAttentionError(FA_ERR_BAD_SHAPE, "block_table must be contiguous")
     if kv_lens is not None:
@@ -476,12 +494,12 @@ def _check_decode_tail(q, kname, k, vname, v, out, k_scale, v_scale, block_table
             raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"kv_lens must be int32, got {kv_lens.dtype}")
         if kv_lens.dim() != 1 or kv_lens.shape[0] != q.shape[0] or not kv_lens.is_contiguous():
             raise FlashAttentionError(FA_ERR_BAD_SHAPE, "kv_lens must be a contiguous [B] tensor")
-    for name, t in (("q", q), (kname, k), (vname, v), ("out", out)):
+    for name, t in ((qname, q), (kname, k), (vname, v), (oname, out)):
         if not t.is_cuda:
             raise FlashAttentionError(FA_ERR_NULL_POINTER, f"{name} must be a device tensor")
         if t.device != q.device:
-            raise FlashAttentionError(FA_ERR_BAD_SHAPE,
-                                      f"{name} is on {t.device}, q on {q.device}: one device only")
+            raise FlashAttentionError(
+                FA_ERR_BAD_SHAPE, f"{name} is on {t.device}, {qname} on {q.device}: one device only")
     for name, t in (("block_table", block_table), ("kv_lens", kv_lens)):
         if t is not None and (not t.is_cuda or t.device != q.device):
             raise FlashAttentionError(FA_ERR_NULL_POINTER, f"{name} must be a tensor on {q.device}")
@@ -644,6 +662,145 @@ def flash_attention_decode_paged(q, k_pages, v_pages, block_table, kv_lens=None,
     kv8 = _check_decode_paged(q, k_pages, v_pages, block_table, kv_lens, out, k_scale, v_scale)
     return _decode_call(kv8, q, k_pages, v_pages, out, block_table, kv_lens, causal, return_lse,
                         num_splits, stream, k_scale, v_scale)
+
+
+def _check_append(k_new, v_new, kname, k, vname, v, block_table, kv_lens, new_lens, k_scale, v_scale):
+    """Raise FlashAttentionError unless k_new / v_new are contiguous
+    [B,Hkv,Sn,D] tensors of one 16-bit dtype and shape, the caches (`kname`,
+    `vname`: [B,Hkv,cap,D], or with a block table the pools
+    [num_pages,Hkv,page_size,D]) have that dtype or are both
+    torch.float8_e4m3fn (returns True then) and agree with k_new in Hkv and D
+    (and B when contiguous), kv_lens is given, and lengths, table and scales
+    are what the decode wrappers take -- in their order and with their
+    messages (:func:`_kv8_caches`, :func:`_check_decode_tail`)."""
+    import torch
+
+    paged = block_table is not None
+    if k_new.dtype not in (torch.float16, torch.bfloat16):
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE,
+                                  f"k_new must be float16 or bfloat16, got {k_new.dtype}")
+    kv8 = _kv8_caches(k_new, kname, k, vname, v, k_scale, v_scale)
+    layout = "" if paged else " (BHSD)"
+    for name, t in (("k_new", k_new), ("v_new", v_new), (kname, k), (vname, v)):
+        if t.dtype != k_new.dtype and not (kv8 and t is not v_new):
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be {k_new.dtype}, got {t.dtype}")
+        if t.dim() != 4:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be 4-D{layout}")
+        if not t.is_contiguous():
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be contiguous{layout}")
+    if v_new.shape != k_new.shape:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, "k_new and v_new must have one shape, [B,Hkv,Sn,D]")
+    if k_new.shape[2] < 1:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, "k_new holds no token (Sn must be >= 1)")
+    if k.shape != v.shape:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{kname} and {vname} must have one shape")
+    if k.shape[1] != k_new.shape[1] or k.shape[3] != k_new.shape[3]:
+        raise FlashAttentionError(
+            FA_ERR_BAD_SHAPE,
+            f"k_new and the {'page pools' if paged else 'caches'} must agree in heads_kv and head_dim")
+    if paged:
+        if k.shape[0] == 0:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, "the page pools hold no page")
+        if k.shape[2] == 0 or k.shape[2] % 64 != 0:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE,
+                                      f"page_size {k.shape[2]} is not a positive multiple of 64")
+    elif k.shape[0] != k_new.shape[0]:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, "k_new and the caches must agree in batch")
+    if kv_lens is None:
+        raise FlashAttentionError(
+            FA_ERR_NULL_POINTER,
+            "kv_lens is required: the int32 [B] lengths after the append (what decode takes next)")
+    if new_lens is not None:
+        if new_lens.dtype != torch.int32:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"new_lens must be int32, got {new_lens.dtype}")
+        if new_lens.dim() != 1 or new_lens.shape[0] != k_new.shape[0] or not new_lens.is_contiguous():
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, "new_lens must be a contiguous [B] tensor")
+    _check_decode_tail(k_new, kname, k, vname, v, v_new, k_scale, v_scale, block_table, kv_lens,
+                       qname="k_new", oname="v_new")
+    if new_lens is not None and (not new_lens.is_cuda or new_lens.device != k_new.device):
+        raise FlashAttentionError(FA_ERR_NULL_POINTER, f"new_lens must be a tensor on {k_new.device}")
+    return kv8
+
+
+def _append_call(kv8, k_new, v_new, k, v, block_table, kv_lens, new_lens, stream, k_scale, v_scale):
+    """The call of both append functions after their checks (the twin of
+    :func:`_decode_call`): the stream and the C entry of the cache form."""
+    import torch
+
+    b, hkv, sn, d = k_new.shape
+    if block_table is not None:
+        cache = (d, k.shape[0], k.shape[2], block_table.data_ptr(), block_table.shape[1])
+    else:
+        cache = (k.shape[2], d)
+    lib = _lib or load_library()
+    name = "fa_cache_append" + ("_paged" if block_table is not None else "")
+    tail = ()
+    if kv8:
+        name += "_kv8_bf16" if k_new.dtype is torch.bfloat16 else "_kv8_f16"
+        tail = (k_scale.data_ptr() if k_scale is not None else None,
+                v_scale.data_ptr() if v_scale is not None else None)
+    else:
+        name += "_16"
+    dev = k_new.device.index
+    if stream is None:
+        st = torch._C._cuda_getCurrentRawStream(dev)
+    else:
+        st = stream if isinstance(stream, int) else stream.cuda_stream
+    with torch.cuda.device(dev):
+        rc = getattr(lib, name)(k_new.data_ptr(), v_new.data_ptr(), k.data_ptr(), v.data_ptr(), b, hkv,
+                                sn, *cache, kv_lens.data_ptr(),
+                                new_lens.data_ptr() if new_lens is not None else None, st, *tail)
+    _check(rc)
+
+
+def flash_attention_cache_append(k_new, v_new, k_cache, v_cache, kv_lens, new_lens=None,
+                                 k_scale=None, v_scale=None, stream=None) -> None:
+    """Write new K/V tokens into the cache :func:`flash_attention_decode`
+    reads (fa_cache_append_16, or fa_cache_append_kv8_* into an FP8 cache), K
+    and V in one launch.
+
+    k_new, v_new: [B, Hkv, Sn, D] fp16 or bf16 contiguous device tensors of one
+    shape (Sn >= 1, D = 128 or 64); k_cache, v_cache: [B, Hkv, cap, D],
+    contiguous, of k_new's dtype or both torch.float8_e4m3fn.  kv_lens: int32
+    [B], REQUIRED: the lengths AFTER the append, the tensor the following
+    decode call takes.  new_lens: int32 [B] (None: Sn everywhere); element b
+    appends its first n_b = clamp(new_lens[b], 0, Sn) tokens, token t to cache
+    row kv_lens[b] - n_b + t.  A row is written iff it lies in [0, cap)
+    (kv_lens is not clamped); nothing else in the caches is touched.
+
+    FP8 cache: the stored byte is E4M3(clamp(float(x) * (1.0f / s), -448,
+    448)), round to nearest even, with s = k_scale[hkv] / v_scale[hkv]
+    (float32 [Hkv] device tensors, None: 1.0) -- the reciprocal-multiply form
+    is the contract (include/fa_mi355x.h).  Scales beside a 16-bit cache are an
+    error.  Lengths and scales are read on the device: no sync, no workspace,
+    graph-capturable.  Returns None.
+    """
+    kv8 = _check_append(k_new, v_new, "k_cache", k_cache, "v_cache", v_cache, None, kv_lens, new_lens,
+                        k_scale, v_scale)
+    _append_call(kv8, k_new, v_new, k_cache, v_cache, None, kv_lens, new_lens, stream, k_scale, v_scale)
+
+
+def flash_attention_cache_append_paged(k_new, v_new, k_pages, v_pages, block_table, kv_lens,
+                                       new_lens=None, k_scale=None, v_scale=None, stream=None) -> None:
+    """:func:`flash_attention_cache_append` into the page pools
+    :func:`flash_attention_decode_paged` reads (fa_cache_append_paged_16 /
+    fa_cache_append_paged_kv8_*).
+
+    k_pages, v_pages: [num_pages, Hkv, page_size, D] with page_size % 64 == 0;
+    block_table: int32 [B, max_pages_per_seq].  Row r of element b lives in
+    page block_table[b, r // page_size] at offset r % page_size and is written
+    iff r lies in [0, max_pages_per_seq * page_size) and that id in [0,
+    num_pages): an out-of-pool id drops the row (the write-side twin of "reads
+    as zero rows").  Two elements whose tables map the same page row race: one
+    wins, unspecified which.  Everything else as for the contiguous function;
+    the table is read on the device.  Returns None.
+    """
+    if block_table is None:
+        raise FlashAttentionError(FA_ERR_NULL_POINTER, "block_table is required")
+    kv8 = _check_append(k_new, v_new, "k_pages", k_pages, "v_pages", v_pages, block_table, kv_lens,
+                        new_lens, k_scale, v_scale)
+    _append_call(kv8, k_new, v_new, k_pages, v_pages, block_table, kv_lens, new_lens, stream, k_scale,
+                 v_scale)
 
 
 def splitkv_buffers(batch: int, heads: int, seq_len: int, num_splits: int, device="cuda"):

@@ -6,6 +6,8 @@ rank 3: the wrapper that puts the kernel beside PyTorch SDPA on one box).
     o = torch.ops.fa_mi355x.decode(q, k_cache, v_cache, kv_lens, causal=True)
     o = torch.ops.fa_mi355x.decode_paged(q, k_pages, v_pages, block_table, kv_lens, causal=True)
     o = torch.ops.fa_mi355x.decode(q, k8_cache, v8_cache, kv_lens, k_scale=ks, v_scale=vs)  # FP8 cache
+    torch.ops.fa_mi355x.cache_append(k_new, v_new, k_cache, v_cache, kv_lens)  # writes the caches
+    torch.ops.fa_mi355x.cache_append_paged(k_new, v_new, k_pages, v_pages, block_table, kv_lens)
 
 ``q, k, v``: fp16 or bf16 ``[B, H, S, D]`` (D = 128 or 64) tensors on the GPU (BHSD, the
 reference layout, flash_attention.cu:119-122); returns a new tensor of the same shape and dtype.
@@ -25,7 +27,8 @@ from __future__ import annotations
 
 import torch
 
-from . import flash_attention_decode, flash_attention_decode_paged, flash_attention_fwd
+from . import (flash_attention_cache_append, flash_attention_cache_append_paged,
+               flash_attention_decode, flash_attention_decode_paged, flash_attention_fwd)
 
 OP_NAME = "fa_mi355x::fwd"
 
@@ -154,3 +157,71 @@ _LIB.impl("decode_paged.kv8", _decode_paged_cpu, "CPU")
 torch.library.register_fake(DECODE_PAGED_KV8_OP_NAME, _decode_paged_fake, lib=_LIB)
 
 decode_paged = torch.ops.fa_mi355x.decode_paged
+
+# cache_append(k_new / v_new [B,Hkv,Sn,D], k_cache / v_cache [B,Hkv,cap,D],
+# kv_lens int32 [B]: the lengths after the append) and cache_append_paged (the
+# pools and the block table): fa_mi355x.flash_attention_cache_append[_paged]
+# behind the same kind of registration.  The caches are mutated in place and
+# nothing is returned; they are taken as they are (a strided cache raises).
+CACHE_APPEND_OP_NAME = "fa_mi355x::cache_append"
+_LIB.define("cache_append(Tensor k_new, Tensor v_new, Tensor(a!) k_cache, Tensor(b!) v_cache, "
+            "Tensor kv_lens, Tensor? new_lens=None, Tensor? k_scale=None, "
+            "Tensor? v_scale=None) -> ()")
+
+
+def _cache_append_gpu(k_new, v_new, k_cache, v_cache, kv_lens, new_lens=None, k_scale=None,
+                      v_scale=None) -> None:
+    flash_attention_cache_append(k_new.contiguous(), v_new.contiguous(), k_cache, v_cache,
+                                 kv_lens.contiguous(),
+                                 None if new_lens is None else new_lens.contiguous(),
+                                 k_scale=k_scale, v_scale=v_scale)
+
+
+def _cache_append_cpu(k_new, v_new, k_cache, v_cache, kv_lens, new_lens=None, k_scale=None,
+                      v_scale=None) -> None:
+    raise ValueError("fa_mi355x::cache_append needs GPU tensors (no CPU path)")
+
+
+def _cache_append_fake(k_new, v_new, k_cache, v_cache, kv_lens, new_lens=None, k_scale=None,
+                       v_scale=None) -> None:
+    torch._check(k_new.dim() == 4 and k_new.shape[-1] in (64, 128), lambda: "expected [B, Hkv, Sn, 64|128]")
+    torch._check(k_new.dtype in (torch.float16, torch.bfloat16), lambda: "expected fp16 or bf16")
+    torch._check(k_cache.dim() == 4 and v_cache.dim() == 4, lambda: "expected 4-D caches")
+
+
+_LIB.impl("cache_append", _cache_append_gpu, "CUDA")
+_LIB.impl("cache_append", _cache_append_cpu, "CPU")
+torch.library.register_fake(CACHE_APPEND_OP_NAME, _cache_append_fake, lib=_LIB)
+
+cache_append = torch.ops.fa_mi355x.cache_append
+
+CACHE_APPEND_PAGED_OP_NAME = "fa_mi355x::cache_append_paged"
+_LIB.define("cache_append_paged(Tensor k_new, Tensor v_new, Tensor(a!) k_pages, Tensor(b!) v_pages, "
+            "Tensor block_table, Tensor kv_lens, Tensor? new_lens=None, Tensor? k_scale=None, "
+            "Tensor? v_scale=None) -> ()")
+
+
+def _cache_append_paged_gpu(k_new, v_new, k_pages, v_pages, block_table, kv_lens, new_lens=None,
+                            k_scale=None, v_scale=None) -> None:
+    flash_attention_cache_append_paged(k_new.contiguous(), v_new.contiguous(), k_pages, v_pages,
+                                       block_table.contiguous(), kv_lens.contiguous(),
+                                       None if new_lens is None else new_lens.contiguous(),
+                                       k_scale=k_scale, v_scale=v_scale)
+
+
+def _cache_append_paged_cpu(k_new, v_new, k_pages, v_pages, block_table, kv_lens, new_lens=None,
+                            k_scale=None, v_scale=None) -> None:
+    raise ValueError("fa_mi355x::cache_append_paged needs GPU tensors (no CPU path)")
+
+
+def _cache_append_paged_fake(k_new, v_new, k_pages, v_pages, block_table, kv_lens, new_lens=None,
+                             k_scale=None, v_scale=None) -> None:
+    _cache_append_fake(k_new, v_new, k_pages, v_pages, kv_lens, new_lens, k_scale, v_scale)
+    torch._check(block_table.dim() == 2, lambda: "expected a [B, max_pages_per_seq] block table")
+
+
+_LIB.impl("cache_append_paged", _cache_append_paged_gpu, "CUDA")
+_LIB.impl("cache_append_paged", _cache_append_paged_cpu, "CPU")
+torch.library.register_fake(CACHE_APPEND_PAGED_OP_NAME, _cache_append_paged_fake, lib=_LIB)
+
+cache_append_paged = torch.ops.fa_mi355x.cache_append_paged

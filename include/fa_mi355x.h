@@ -283,7 +283,8 @@ int fa_decode_paged_bf16(const void* q, const void* k_pages, const void* v_pages
  * in fp32.  Rows past kv_lens[b], unmapped pages and out-of-pool page ids are
  * never read, as for the 16-bit entries.  The paged entry's O and LSE are
  * bit-identical to the contiguous kv8 entry's on the gathered cache with the
- * same num_splits.  Writing (quantising) into the cache is the caller's. */
+ * same num_splits.  fa_cache_append_kv8_* below write (quantise into) these
+ * caches. */
 int fa_decode_kv8_f16(const void* q, const void* k, const void* v, void* o, float* lse,
                       int batch, int heads_q, int heads_kv, int seqlen_q, int kv_capacity,
                       int head_dim, const int* kv_lens, int causal, int num_splits,
@@ -306,6 +307,82 @@ int fa_decode_paged_kv8_bf16(const void* q, const void* k_pages, const void* v_p
                              int max_pages_per_seq, const int* kv_lens, int causal, int num_splits,
                              void* workspace, unsigned long long ws_bytes, void* hip_stream,
                              const float* k_scale, const float* v_scale);
+
+/* Cache append: write new K/V tokens into the caches the decode entries read,
+ * K and V in one launch.
+ *   k_new, v_new  [batch][heads_kv][seqlen_new][head_dim], fp16 or bf16,
+ *             contiguous; seqlen_new >= 1, head_dim 128 or 64.
+ *   k_cache, v_cache  [batch][heads_kv][kv_capacity][head_dim], or the pools
+ *             k_pages, v_pages [num_pages][heads_kv][page_size][head_dim] with
+ *             block_table as for fa_decode_paged_* (kv_capacity :=
+ *             max_pages_per_seq * page_size).
+ *   kv_lens   DEVICE int32[batch], REQUIRED: each element's length AFTER the
+ *             append -- the tensor the following decode call takes.
+ *   new_lens  DEVICE int32[batch], or NULL (= seqlen_new for every element).
+ *     n_b = clamp(new_lens[b], 0, seqlen_new)
+ *     for t in [0, n_b):  r = kv_lens[b] - n_b + t
+ *       cache row r of (b, hkv) <- k_new[b][hkv][t][:]        (same for V)
+ * Tokens t >= n_b are ignored (right-padded ragged prefill, elements with
+ * nothing to append).  A row is written if and only if 0 <= r < kv_capacity;
+ * kv_lens[b] is NOT clamped: a length past the capacity drops the rows that do
+ * not exist, it does not shift them.  Paged: row r lives in page
+ * block_table[b][r / page_size] at offset r % page_size and is written if and
+ * only if that id is inside [0, num_pages) -- the write-side twin of "an
+ * out-of-pool page id reads as zero rows".  Whether a row is written is decided
+ * before any address is formed from it, and no byte of the caches other than
+ * the rows named above is ever written.  Two batch elements whose tables map
+ * the same page row are the caller's problem: one of them wins, unspecified
+ * which.
+ * _16: a 16-bit cache of k_new's type; a bit copy, so fp16 and bf16 share the
+ * entry.  _kv8_f16 / _kv8_bf16 (the suffix is k_new's type): an FP8 E4M3
+ * cache as fa_decode_kv8_* reads it.  The byte stored for a source element x
+ * with s = k_scale[hkv] (v_scale[hkv] for V; NULL = 1.0) is
+ *     y    = float(x) * (1.0f / s)       both in IEEE fp32, 1.0f / s correctly rounded
+ *     byte = E4M3(clamp(y, -448, 448))   round to nearest even, subnormals
+ *                                        down to 2^-9, -0.0 keeps its sign
+ * +-inf saturates to +-448; a NaN stores a NaN code (0x7f or 0xff).  The
+ * reciprocal-multiply form IS the contract (not x / s; the two agree exactly
+ * for power-of-two scales).  Any finite scale in [2^-32, 2^32] is covered;
+ * outside it, and for non-positive scales, the bytes are unspecified.
+ * Lengths, table and scales are read on the device: no host read, no sync, no
+ * workspace; everything is enqueued on hip_stream and is graph-capturable, and
+ * table, lengths, scales and k_new / v_new contents may change between
+ * replays.
+ * Argument checks, all before any HIP call, in this order: a negative size:
+ * FA_ERR_BAD_SHAPE; head_dim not 64 or 128: FA_ERR_UNSUPPORTED_HEAD_DIM;
+ * seqlen_new < 1 (or > INT_MAX - 64), page_size / num_pages /
+ * max_pages_per_seq / capacity outside what fa_decode_paged_* accepts:
+ * FA_ERR_BAD_SHAPE; batch or heads_kv of 0: FA_OK, nothing enqueued;
+ * kv_capacity * 2 * head_dim > INT_MAX (contiguous, as fa_decode_*):
+ * FA_ERR_BAD_SHAPE; kv_capacity == 0: FA_OK, nothing enqueued; k_new, v_new, a
+ * cache, kv_lens or block_table NULL: FA_ERR_NULL_POINTER. */
+int fa_cache_append_16(const void* k_new, const void* v_new, void* k_cache, void* v_cache,
+                       int batch, int heads_kv, int seqlen_new, int kv_capacity, int head_dim,
+                       const int* kv_lens, const int* new_lens, void* hip_stream);
+int fa_cache_append_paged_16(const void* k_new, const void* v_new, void* k_pages, void* v_pages,
+                             int batch, int heads_kv, int seqlen_new, int head_dim, int num_pages,
+                             int page_size, const int* block_table, int max_pages_per_seq,
+                             const int* kv_lens, const int* new_lens, void* hip_stream);
+int fa_cache_append_kv8_f16(const void* k_new, const void* v_new, void* k_cache, void* v_cache,
+                            int batch, int heads_kv, int seqlen_new, int kv_capacity, int head_dim,
+                            const int* kv_lens, const int* new_lens, void* hip_stream,
+                            const float* k_scale, const float* v_scale);
+int fa_cache_append_kv8_bf16(const void* k_new, const void* v_new, void* k_cache, void* v_cache,
+                             int batch, int heads_kv, int seqlen_new, int kv_capacity, int head_dim,
+                             const int* kv_lens, const int* new_lens, void* hip_stream,
+                             const float* k_scale, const float* v_scale);
+int fa_cache_append_paged_kv8_f16(const void* k_new, const void* v_new, void* k_pages,
+                                  void* v_pages, int batch, int heads_kv, int seqlen_new,
+                                  int head_dim, int num_pages, int page_size,
+                                  const int* block_table, int max_pages_per_seq,
+                                  const int* kv_lens, const int* new_lens, void* hip_stream,
+                                  const float* k_scale, const float* v_scale);
+int fa_cache_append_paged_kv8_bf16(const void* k_new, const void* v_new, void* k_pages,
+                                   void* v_pages, int batch, int heads_kv, int seqlen_new,
+                                   int head_dim, int num_pages, int page_size,
+                                   const int* block_table, int max_pages_per_seq,
+                                   const int* kv_lens, const int* new_lens, void* hip_stream,
+                                   const float* k_scale, const float* v_scale);
 
 /* The dispatcher's decision (ref tier table :620-661): config id used by
  * fa_fwd_f16 for this shape.  The _ws entries may run the causal split tier
