@@ -1,6 +1,6 @@
 """Inputs whose exact attention output is known in closed form and moves by far
-more than the gate when one key is wrong (a helper module, not a test: load
-it by file path, tests/ is not on sys.path).  numpy and torch only.
+more than the gate when one key is wrong (a helper module, not a test:
+`import keysense_inputs` from a test file).  numpy and torch only.
 
 Why: on inputs drawn from [-0.5, 0.5] the softmax is nearly flat, every output
 is close to the mean of V and shrinks like 1/sqrt(S), and an absolute 1e-3

@@ -12,31 +12,14 @@ PyTorch SDPA in bf16 1.4e-3 on the same inputs.
 import pytest
 
 torch = pytest.importorskip("torch")
+from fwd_helpers import fa as _fa, rand_scaled_cast, ref_fp32 as _ref  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 TOL = 5e-3
 
 
-def _fa():
-    import fa_mi355x
-
-    return fa_mi355x
-
-
 def _rand(shape, seed, scale=1.0):
-    g = torch.Generator(device="cuda")
-    g.manual_seed(seed)
-    t = torch.empty(shape, dtype=torch.float32, device="cuda").uniform_(-0.5, 0.5, generator=g)
-    return (t * scale).to(torch.bfloat16)
-
-
-def _ref(q, k, v, causal):
-    q, k, v = q.float(), k.float(), v.float()
-    s = (q @ k.transpose(-1, -2)) / (q.shape[-1] ** 0.5)
-    if causal:
-        n = q.shape[-2]
-        s = s.masked_fill(~torch.ones(n, n, device=q.device, dtype=torch.bool).tril(), float("-inf"))
-    return torch.softmax(s, -1) @ v
+    return rand_scaled_cast(shape, seed, torch.bfloat16, scale)
 
 
 def _bf16_configs(causal):

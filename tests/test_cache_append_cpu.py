@@ -7,128 +7,25 @@ reference against torch's CPU conversion over every 16-bit pattern, and the
 kernels' compile-time resource usage -- no kernel is launched (no GPU here)."""
 import ctypes
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import capi_checks
+from capi_checks import fa as _fa
+from fp8_contract import NAN_PATTERNS, all_patterns, integer_reference_bytes, torch_reference_bytes
+
 SYMBOLS = ("fa_cache_append_16", "fa_cache_append_paged_16", "fa_cache_append_kv8_f16",
            "fa_cache_append_kv8_bf16", "fa_cache_append_paged_kv8_f16",
            "fa_cache_append_paged_kv8_bf16")
 FP8 = torch.float8_e4m3fn
 SCALES = (1.0, 2.0 ** -6, 0.3, 3.7)
-NAN_PATTERNS = {torch.float16: 2046, torch.bfloat16: 254}
-
-
-def _fa():
-    import fa_mi355x
-
-    return fa_mi355x
 
 
 # ---------------------------------------------------------------------------
-# The contract of the FP8 cache, twice: the torch expression on the CPU (the
-# reference the GPU tests compare with) and an integer-only model of it.
-
-def torch_reference_bytes(x, scale):
-    """E4M3 bytes (uint8 tensor) of the 16-bit CPU tensor `x` under the fp32
-    scale `scale`: E4M3(clamp(float(x) * (1.0f / s), -448, 448)) by torch's CPU
-    conversion.  The reciprocal is taken in double and rounded to fp32 by the
-    multiplication, which equals the correctly rounded fp32 reciprocal (53 >=
-    2 * 24 + 2 bits: the double rounding is innocuous)."""
-    s = float(np.float32(scale))
-    assert x.device.type == "cpu"
-    return torch.clamp(x.float() * (1.0 / s), -448, 448).to(FP8).view(torch.uint8)
-
-
-def _rne_scalar(m, sticky, nbits):
-    """Python int m (with a sticky flag for bits below it) rounded to nearest
-    even at nbits significant bits: (mantissa, bits shifted out)."""
-    sh = max(m.bit_length() - nbits, 0)
-    if sh == 0:
-        return m, 0
-    lo, half = m & ((1 << sh) - 1), 1 << (sh - 1)
-    m >>= sh
-    if lo > half or (lo == half and (sticky or (m & 1))):
-        m += 1
-    if m.bit_length() > nbits:
-        m >>= 1
-        sh += 1
-    return m, sh
-
-
-def _rne_shift(m, sh):
-    """int64 array m >> sh (sh >= 1, elementwise), rounded to nearest even."""
-    sh = np.minimum(sh, 62)
-    q = m >> sh
-    lo = m & ((np.int64(1) << sh) - 1)
-    half = np.int64(1) << (sh - 1)
-    return q + ((lo > half) | ((lo == half) & ((q & 1) == 1))).astype(np.int64)
-
-
-def _bit_length(m):
-    n = np.zeros(m.shape, dtype=np.int64)
-    for k in range(48):
-        n += (m >> k) > 0
-    return n
-
-
-def integer_reference_bytes(bits, dtype, scale):
-    """The contract in integer arithmetic only.  bits: uint16 array of source
-    patterns; returns (uint8 bytes, bool is_nan).  Steps: the correctly rounded
-    fp32 reciprocal of the fp32 scale, the fp32 product (rounded to 24 bits:
-    the double rounding is part of the contract), the clamp, then E4M3 by
-    round-to-nearest-even with subnormals (quantum 2^-9) and the zero's sign."""
-    sb = int(np.float32(scale).view(np.uint32))
-    se, sf = (sb >> 23) & 0xff, sb & 0x7fffff
-    assert sb >> 31 == 0 and 0 < se < 255, "a positive normal scale"
-    ms, es = (1 << 23) | sf, se - 150                     # s = ms * 2^es
-    q, rem = divmod(1 << 60, ms)                          # 1/s = (2^60 / ms) * 2^(-60 - es)
-    mr, sh = _rne_scalar(q, rem != 0, 24)
-    er = -60 - es + sh                                    # fl32(1/s) = mr * 2^er
-
-    b = bits.astype(np.int64)
-    sign = b >> 15
-    if dtype is torch.float16:
-        e, f, emax, hidden, bias = (b >> 10) & 31, b & 1023, 31, 1024, 25
-    else:
-        e, f, emax, hidden, bias = (b >> 7) & 255, b & 127, 255, 128, 134
-    is_nan = (e == emax) & (f != 0)
-    is_inf = (e == emax) & (f == 0)
-    mx = np.where(e == 0, f, f + hidden)                  # |x| = mx * 2^ex
-    ex = np.where(e == 0, 1, e) - bias
-
-    # fp32 product: 24 significant bits, nearest even (an fp32-subnormal or
-    # overflowing product needs no model: it is far below 2^-10 / above 448)
-    p = mx * mr
-    pe = ex + er
-    over = np.maximum(_bit_length(p) - 24, 0)
-    m = np.where(over > 0, _rne_shift(p, np.maximum(over, 1)), p)
-    me = pe + over
-    # exponent of the leading bit; m == 2^24 after a carry is handled by it too
-    top = _bit_length(m) - 1 + me
-    # clamp to 448 = 0x1.cp8
-    norm = np.where(m > 0, m << np.clip(24 - _bit_length(m), 0, 24), 0)   # >= 24 bits, leading bit set
-    norm = np.where(_bit_length(norm) > 24, norm >> 1, norm)
-    big = (top > 8) | ((top == 8) & (norm >= 0xE00000)) | is_inf
-    # E4M3: quantum 2^(max(top, -6) - 3)
-    eeff = np.maximum(top, -6)
-    shift = (eeff - 3) - me
-    k = np.where(shift > 0, _rne_shift(m, np.maximum(shift, 1)), m << np.clip(-shift, 0, 8))
-    byte = ((eeff + 6) << 3) + k
-    byte = np.where(m == 0, 0, byte)
-    byte = np.where(big, 0x7e, byte)
-    byte = np.where(is_nan, 0x7f, byte) | (sign << 7)
-    return byte.astype(np.uint8), is_nan
-
-
-def all_patterns(dtype):
-    """Every bit pattern of the 16-bit type once, as a CPU tensor."""
-    return torch.arange(65536, dtype=torch.int32).to(torch.int16).view(dtype)
-
+# The contract of the FP8 cache (tests/fp8_contract.py): the torch expression
+# on the CPU against the integer-only model of it.
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["f16", "bf16"])
 def test_fp8_contract_integer_model_equals_torch_cpu(dtype):
@@ -164,15 +61,7 @@ def test_fp8_contract_landmarks():
 # Exports and argument checks
 
 def test_library_exports_append_symbols():
-    fa = _fa()
-    out = subprocess.run(["nm", "-D", "--defined-only", fa.library_path()], capture_output=True,
-                         text=True, check=True).stdout
-    syms = {line.split()[-1] for line in out.splitlines() if line.strip()}
-    header = open(os.path.join(ROOT, "include", "fa_mi355x.h")).read()
-    for s in SYMBOLS:
-        assert s in syms, s
-        assert s in fa.EXPORTED_SYMBOLS, s
-        assert re.search(r"\b%s\s*\(" % s, header), s
+    capi_checks.assert_exported(SYMBOLS)
 
 
 P = ctypes.c_void_p
@@ -345,22 +234,14 @@ def test_ops_schemas_fake_and_cpu():
 # ---------------------------------------------------------------------------
 # Compile-time resource usage
 
-@pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
+@pytest.mark.skipif(not os.path.exists(capi_checks.HIPCC), reason="needs hipcc")
 def test_append_kernels_use_no_scratch_and_no_lds():
     """16-bit: 2 head dims x contiguous / paged = 4 kernels (one bit copy for
     fp16 and bf16); FP8: 2 source types x 2 head dims x contiguous / paged = 8.
     Every one compiles for gfx950 with no scratch and no LDS."""
-    pkg = os.path.join(ROOT, "flash-attention-cuda_amd")
-    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
-           "-fno-honor-nans", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(pkg, "csrc"),
-           "-c", os.path.join(pkg, "csrc", "fa_cache_append.hip"), "-o", os.devnull,
-           "-Rpass-analysis=kernel-resource-usage"]
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    names = re.findall(r"Function Name: (\S+)", out.stderr)
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", out.stderr)]
-    lds = [int(x) for x in re.findall(r"LDS Size \[bytes/block\]: (\d+)", out.stderr)]
-    assert len(names) == 12 and len(scratch) == 12 and len(lds) == 12, (names, scratch, lds)
+    (kernels,) = capi_checks.kernel_resource_usage(["fa_cache_append.hip"], timeout=900)
+    names, scratch, lds = (list(x) for x in zip(*kernels))
+    assert len(names) == 12, (names, scratch, lds)
     assert len(set(names)) == 12 and all("fa_cache_append_kernel" in n for n in names), names
     assert sum("Lb1EEEvNS" in n for n in names) == 8, names     # KV8 = true
     assert not any(scratch), dict(zip(names, scratch))

@@ -6,32 +6,19 @@ Every comparison is bit-exact; the feature has no tolerance.  16-bit caches
 are compared whole, as int16, with an expectation built by torch indexing on
 the CPU over a sentinel fill, so one assertion checks the written rows and
 that every other byte is untouched.  FP8 bytes are compared with the torch
-expression on the CPU (tests/test_cache_append_cpu.py pins it against an
-integer-only model of the contract), never with torch's device conversion.
+expression on the CPU (tests/fp8_contract.py; tests/test_cache_append_cpu.py
+pins it against an integer-only model of the contract), never with torch's
+device conversion.
 Shapes: B = 3, Hkv = 2 (one Hkv = 1 case), cap = 192; paged: page 64, a
 3-column table into a permuted pool with two pages no entry names.
 """
-import importlib.util
-import os
-
 import pytest
 import torch
 
 import fa_mi355x
+from fp8_contract import NAN_PATTERNS, all_patterns, torch_reference_bytes
 
 pytestmark = pytest.mark.gpu
-
-
-def _load(name, fname):
-    spec = importlib.util.spec_from_file_location(
-        name, os.path.join(os.path.dirname(os.path.abspath(__file__)), fname))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-_c = _load("_cache_append_cpu_helpers", "test_cache_append_cpu.py")
-torch_reference_bytes, all_patterns = _c.torch_reference_bytes, _c.all_patterns
 
 DEV = "cuda"
 FP8 = torch.float8_e4m3fn
@@ -159,7 +146,7 @@ def _check_bytes(got, src, scales, what):
     non-NaN input, NaN inputs hold a NaN code."""
     want = _quantise(src, scales)
     nan = torch.isnan(src.float())
-    assert int(nan.sum()) == _c.NAN_PATTERNS[src.dtype]
+    assert int(nan.sum()) == NAN_PATTERNS[src.dtype]
     bad = (got != want) & ~nan
     if bool(bad.any()):
         idx = bad.nonzero()[:8].tolist()
@@ -246,7 +233,7 @@ def test_out_of_pool_page_ids_write_nothing(kv8):
                            _expect(big_k[1:-1], src_k, lens, None, table))
 
 
-def _paginate(cache, table, npages):
+def _scatter_to_pool(cache, table, npages):
     """The pool holding `cache` ([B,Hkv,cap,D]) under `table`; other pages zero."""
     b, hkv, cap, d = cache.shape
     pool = torch.zeros((npages, hkv, PAGE, d), dtype=cache.dtype, device=cache.device)
@@ -280,7 +267,7 @@ def test_round_trip_append_then_decode(form, ns):
         for i, n in enumerate(lens):
             c[i, :, n:].view(torch.uint8 if kv8 else torch.int16).zero_()
         c = c.to(DEV)
-        return _paginate(c, table, npages) if paged else c
+        return _scatter_to_pool(c, table, npages) if paged else c
 
     def dec(kc, vc, lens):
         if paged:

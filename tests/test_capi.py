@@ -8,14 +8,10 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import capi_checks
+from capi_checks import ROOT, fa as _fa
+
 INCLUDE = os.path.join(ROOT, "include")
-
-
-def _fa():
-    import fa_mi355x
-
-    return fa_mi355x
 
 
 def _declared_functions(header):
@@ -27,13 +23,6 @@ def _declared_functions(header):
     return sorted(set(names))
 
 
-def _dynsyms():
-    lib = _fa().library_path()
-    out = subprocess.run(["nm", "-D", "--defined-only", lib], capture_output=True, text=True,
-                         check=True).stdout
-    return {line.split()[-1] for line in out.splitlines() if line.strip()}
-
-
 def test_library_loads():
     fa = _fa()
     assert os.path.exists(fa.library_path())
@@ -43,7 +32,7 @@ def test_library_loads():
 def test_exports_every_c_abi_symbol():
     declared = _declared_functions("fa_mi355x.h")
     assert "fa_fwd_f16" in declared and len(declared) >= 10
-    syms = _dynsyms()
+    syms = capi_checks.exported_symbols()
     missing = [d for d in declared if d not in syms]
     assert not missing, f"declared but not exported: {missing}"
     assert set(declared) == set(_fa().EXPORTED_SYMBOLS)
@@ -359,24 +348,16 @@ def test_split_plan_and_workspace_entry():
     assert lib.fa_fwd_f16_ws(None, p, p, p, 1, 4, 8192, 128, 1, 0, p, need, None) == fa.FA_ERR_NULL_POINTER
 
 
-@pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
+@pytest.mark.skipif(not os.path.exists(capi_checks.HIPCC), reason="needs hipcc")
 def test_no_kernel_uses_scratch():
     """Compile-time twin of test_fullsize_gpu.test_register_report: every
     kernel of the library -- the asm item programs included, whose statement
     leaves hipcc 20 VGPRs for whatever is live across it -- keeps all of its
     state in registers (ScratchSize 0), checked from hipcc's resource-usage
     remarks so a spill is caught without a GPU."""
-    pkg = os.path.join(ROOT, "flash-attention-cuda_amd")
-    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-honor-nans",
-           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(pkg, "csrc"), "-c",
-           os.path.join(pkg, "csrc", "fa_fwd.hip"), "-o", os.devnull,
-           "-Rpass-analysis=kernel-resource-usage"]
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    names = re.findall(r"Function Name: (\S+)", out.stderr)
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", out.stderr)]
-    assert names and len(names) == len(scratch), (len(names), len(scratch))
-    spills = {n: s for n, s in zip(names, scratch) if s}
+    (kernels,) = capi_checks.kernel_resource_usage(["fa_fwd.hip"])
+    assert kernels
+    spills = {n: s for n, s, _ in kernels if s}
     assert not spills, spills
 
 

@@ -13,26 +13,18 @@ import ctypes
 import os
 import subprocess
 
-import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
 
 import oracle  # noqa: E402  (test infrastructure)
+from fwd_helpers import rand_half as _rand, to_dev as _dev, to_host_bits as _bits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HARNESS = os.path.join(ROOT, "tests", "harness", "build", "flash_attention")
 V9_MANGLED = "_Z27flash_attention_v9_dispatchPK6__halfS1_S1_PS_PfS3_iiiibP12ihipStream_t"
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.int16)).view(torch.float16).cuda()
-
-
-def _bits(t):
-    return t.detach().cpu().view(torch.int16).numpy().view(np.uint16)
 
 
 def test_reference_harness_checks_pass():
@@ -78,12 +70,6 @@ def _v9(lib):
     fn.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, ctypes.c_bool, vp]
     fn.restype = None
     return fn
-
-
-def _rand(shape, seed):
-    g = torch.Generator(device="cuda")
-    g.manual_seed(seed)
-    return torch.empty(shape, dtype=torch.float16, device="cuda").uniform_(-0.5, 0.5, generator=g)
 
 
 # (B, H, S, causal, what the dispatcher runs): the shapes whose tier needs a

@@ -4,46 +4,20 @@ reference's cpu_attention restatement, which is head_dim-generic -- at the
 same 1e-3 gate as head_dim 128; bf16 against a torch fp32 reference at 5e-3
 (tests/test_bf16_gpu.py explains that bound).
 """
-import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
 
 import oracle  # noqa: E402  (test infrastructure)
+from fwd_helpers import bits as _bits, fa as _fa, rand_scaled_cast as _rand, ref_fp32 as _ref32  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 D = 64
 
 
-def _fa():
-    import fa_mi355x
-
-    return fa_mi355x
-
-
-def _rand(shape, seed, dtype=torch.float16, scale=1.0):
-    g = torch.Generator(device="cuda")
-    g.manual_seed(seed)
-    t = torch.empty(shape, dtype=torch.float32, device="cuda").uniform_(-0.5, 0.5, generator=g)
-    return (t * scale).to(dtype)
-
-
-def _bits(t):
-    return t.detach().cpu().contiguous().view(torch.int16).numpy().view(np.uint16)
-
-
 def _ids(dtype, causal):
     return [c.id for c in _fa().configs()
             if c.head_dim == D and c.dtype == dtype and c.causal == causal]
-
-
-def _ref32(q, k, v, causal):
-    q, k, v = q.float(), k.float(), v.float()
-    s = (q @ k.transpose(-1, -2)) / (D ** 0.5)
-    if causal:
-        n = q.shape[-2]
-        s = s.masked_fill(~torch.ones(n, n, device=q.device, dtype=torch.bool).tril(), float("-inf"))
-    return torch.softmax(s, -1) @ v
 
 
 @pytest.mark.parametrize("causal", [False, True])

@@ -4,78 +4,24 @@ torch.ops.fa_mi355x.decode): exports, the argument checks (all returned before
 any launch, so fake pointers do), the split plan, the workspace size, the
 Python wrapper's tensor checks, the op's registration and the kernels'
 compile-time resource usage -- no kernel is launched (no GPU here)."""
-import ctypes
 import os
-import re
-import subprocess
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import capi_checks
+from capi_checks import MAX_SPLITS, fa as _fa
+
 SYMBOLS = ("fa_decode_f16", "fa_decode_bf16", "fa_decode_num_splits", "fa_decode_ws_bytes")
-MAX_SPLITS = 64  # the plan's upper cap (csrc/fa_decode_host.hpp kDecodeMaxSplits)
-
-
-def _fa():
-    import fa_mi355x
-
-    return fa_mi355x
 
 
 def test_library_exports_decode_symbols():
-    fa = _fa()
-    out = subprocess.run(["nm", "-D", "--defined-only", fa.library_path()], capture_output=True,
-                         text=True, check=True).stdout
-    syms = {line.split()[-1] for line in out.splitlines() if line.strip()}
-    for s in SYMBOLS:
-        assert s in syms and s in fa.EXPORTED_SYMBOLS, s
-    header = open(os.path.join(ROOT, "include", "fa_mi355x.h")).read()
-    for s in SYMBOLS:
-        assert re.search(r"\b%s\s*\(" % s, header), s
-
-
-def _call(fn, q, k, v, o, b, hq, hkv, sq, cap, d, lens=None, causal=1, ns=0, ws=None, wsb=0):
-    return fn(q, k, v, o, None, b, hq, hkv, sq, cap, d, lens, causal, ns, ws, wsb, None)
+    capi_checks.assert_exported(SYMBOLS)
 
 
 def test_argument_checks():
     fa = _fa()
-    lib = fa.load_library()
-    p = ctypes.c_void_p(0x1000)
-    for fn in (lib.fa_decode_f16, lib.fa_decode_bf16):
-        for bad in range(4):  # each of q, k, v, o NULL in turn
-            ptrs = [None if i == bad else p for i in range(4)]
-            assert _call(fn, *ptrs, 1, 8, 2, 1, 1024, 128) == fa.FA_ERR_NULL_POINTER
-        for d in (0, 32, 96, 256):
-            assert _call(fn, p, p, p, p, 1, 8, 2, 1, 1024, d) == fa.FA_ERR_UNSUPPORTED_HEAD_DIM
-        for hq, hkv in ((8, 3), (7, 2), (4, 8)):
-            assert _call(fn, p, p, p, p, 1, hq, hkv, 1, 1024, 128) == fa.FA_ERR_BAD_SHAPE
-        for sq in (0, 17, -1):
-            assert _call(fn, p, p, p, p, 1, 8, 2, sq, 1024, 128) == fa.FA_ERR_BAD_SHAPE
-        assert _call(fn, p, p, p, p, -1, 8, 2, 1, 1024, 128) == fa.FA_ERR_BAD_SHAPE
-        assert _call(fn, p, p, p, p, 1, -8, 2, 1, 1024, 128) == fa.FA_ERR_BAD_SHAPE
-        assert _call(fn, p, p, p, p, 1, 8, -2, 1, 1024, 128) == fa.FA_ERR_BAD_SHAPE
-        assert _call(fn, p, p, p, p, 1, 8, 2, 1, -5, 128) == fa.FA_ERR_BAD_SHAPE
-        # cap * 2 * head_dim past INT_MAX
-        assert _call(fn, p, p, p, p, 1, 8, 2, 1, 8388608, 128) == fa.FA_ERR_BAD_SHAPE
-        assert _call(fn, p, p, p, p, 1, 8, 2, 1, 16777216, 64) == fa.FA_ERR_BAD_SHAPE
-        # no kv_lens, causal, fewer cache rows than query tokens
-        assert _call(fn, p, p, p, p, 1, 8, 2, 4, 3, 128, None, 1) == fa.FA_ERR_BAD_SHAPE
-        # splitting needs a workspace: present, long enough, 16-byte aligned
-        need = lib.fa_decode_ws_bytes(1, 8, 2, 1, 4096, 128, 4)
-        assert need > 65536
-        assert _call(fn, p, p, p, p, 1, 8, 2, 1, 4096, 128, ns=4) == fa.FA_ERR_WORKSPACE
-        assert _call(fn, p, p, p, p, 1, 8, 2, 1, 4096, 128, ns=4, ws=p, wsb=need - 1) == \
-            fa.FA_ERR_WORKSPACE
-        assert _call(fn, p, p, p, p, 1, 8, 2, 1, 4096, 128, ns=4, ws=ctypes.c_void_p(0x1008),
-                     wsb=need) == fa.FA_ERR_WORKSPACE
-        # more pieces than the cap
-        assert _call(fn, p, p, p, p, 1, 8, 2, 1, 4096, 128, ns=MAX_SPLITS + 1, ws=p,
-                     wsb=1 << 40) == fa.FA_ERR_BAD_CONFIG
-        # empty problems: nothing to do, nothing launched, no pointer looked at
-        assert _call(fn, None, None, None, None, 0, 8, 2, 1, 1024, 128) == fa.FA_OK
-        assert _call(fn, None, None, None, None, 1, 0, 0, 1, 1024, 128) == fa.FA_OK
+    capi_checks.decode_argument_checks(fa, fa.load_library())
 
 
 def test_eight_entries_answer_shared_arguments_alike():
@@ -213,21 +159,14 @@ def test_decode_op_registered_with_fake_impl():
                                    _t((1, 2, 8, 128)))
 
 
-@pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
+@pytest.mark.skipif(not os.path.exists(capi_checks.HIPCC), reason="needs hipcc")
 def test_no_decode_kernel_uses_scratch():
     """Twin of test_capi.test_no_kernel_uses_scratch for csrc/fa_decode.hip:
     every decode kernel (2 dtypes x 2 head dims x 1 / 2 / 4 row blocks) keeps
     its state in registers."""
-    pkg = os.path.join(ROOT, "flash-attention-cuda_amd")
-    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-honor-nans",
-           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(pkg, "csrc"), "-c",
-           os.path.join(pkg, "csrc", "fa_decode.hip"), "-o", os.devnull,
-           "-Rpass-analysis=kernel-resource-usage"]
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    names = re.findall(r"Function Name: (\S+)", out.stderr)
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", out.stderr)]
-    assert len(names) == 12 and len(names) == len(scratch), (len(names), len(scratch))
+    (kernels,) = capi_checks.kernel_resource_usage(["fa_decode.hip"])
+    names = [n for n, _, _ in kernels]
+    assert len(names) == 12, len(names)
     assert all("fa_decode_kernel" in n for n in names), names
-    spills = {n: s for n, s in zip(names, scratch) if s}
+    spills = {n: s for n, s, _ in kernels if s}
     assert not spills, spills

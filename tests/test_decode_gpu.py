@@ -3,160 +3,21 @@ fa_mi355x.flash_attention_decode, torch.ops.fa_mi355x.decode): a few query
 tokens per head over a K/V cache with per-batch lengths, grouped K/V heads and
 the in-launch split of the key range.
 
-References and gates:
-  * fp16 output: the CPU oracle (oracle.attention_rows) per query head, with
-    its K/V head's rows [0, len_b); the Sq query rows sit at positions
-    len_b - Sq .. len_b - 1 of an otherwise-zero [len_b, D] q.  Gate 1e-3 (the
-    project's).
-  * bf16 output: fp32 torch on the device, gate 5e-3 (the project's).
-  * LSE: float64 numpy log-sum-exp of the same 16-bit inputs, gate
-    2^-10 * max|scaled score| + 1e-5 with the maximum taken from the
-    reference: LSE is 1-Lipschitz in the scores, and the only score error
-    above fp32 noise the design allows is a 16-bit rounding of the pre-scaled
-    Q (2^-11 relative); the gate is twice that.
+The references and gates are those of tests/decode_refs.py: fp16 output
+against the CPU oracle at 1e-3, bf16 output against fp32 torch at 5e-3, LSE
+against a float64 reference at 2^-10 * max|scaled score| + 1e-5.
 """
-import math
-
 import numpy as np
 import pytest
 import torch
 
+import decode_refs as dr
 import fa_mi355x
 import oracle
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
-GATE_F16 = 1e-3
-GATE_BF16 = 5e-3
-
-
-def _dev(a):
-    return torch.from_numpy(np.array(a, dtype=np.uint16).view(np.int16)).view(torch.float16).to(DEV)
-
-
-def _bits(t):
-    return t.detach().cpu().contiguous().view(torch.int16).numpy().view(np.uint16)
-
-
-_INPUTS = {}
-
-
-def _inputs(b, hq, hkv, sq, cap, d, seed=42):
-    """(q, k, v) uint16 fp16 bits from the oracle's generator (cached, read-only)."""
-    key = (b, hq, hkv, sq, cap, d, seed)
-    if key not in _INPUTS:
-        _, k, v = oracle.gen_inputs(b, hkv, cap, d, seed)
-        q = oracle.gen_inputs(b, hq, sq, d, seed + 1)[0]
-        for a in (q, k, v):
-            a.setflags(write=False)
-        _INPUTS[key] = (q, k, v)
-    return _INPUTS[key]
-
-
-def _oracle_decode(q, k, v, lens, causal):
-    """CPU-oracle decode reference: uint16 [B, Hq, Sq, D]; rows that see no key are zeros."""
-    b, hq, sq, d = q.shape
-    g = hq // k.shape[1]
-    out = np.zeros((b, hq, sq, d), np.uint16)
-    for bi in range(b):
-        n = int(lens[bi])
-        if n == 0:
-            continue
-        for h in range(hq):
-            kh, vh = k[bi, h // g, :n], v[bi, h // g, :n]
-            if n >= sq:
-                qf = np.zeros((n, d), np.uint16)
-                qf[n - sq:] = q[bi, h]
-                out[bi, h] = oracle.attention_rows(qf, kh, vh, np.arange(n - sq, n), causal)
-                continue
-            for t in range(sq):
-                pos = n - sq + t if causal else 0
-                if pos < 0:
-                    continue
-                qf = np.zeros((n, d), np.uint16)
-                qf[pos] = q[bi, h, t]
-                out[bi, h, t] = oracle.attention_rows(qf, kh, vh, np.array([pos]), causal)[0]
-    return out
-
-
-def _lse_ref(q, k, v, lens, causal):
-    """float64 LSE [B, Hq, Sq] of the 16-bit inputs and the largest |scaled score|
-    (q, k: uint16 fp16 bits, or 16-bit torch tensors of either dtype)."""
-    if isinstance(q, torch.Tensor):
-        qf, kall = (t.detach().float().cpu().numpy().astype(np.float64) for t in (q, k))
-    else:
-        qf, kall = (a.view(np.float16).astype(np.float64) for a in (q, k))
-    b, hq, sq, d = qf.shape
-    g = hq // kall.shape[1]
-    lse = np.full((b, hq, sq), -np.inf)
-    smax = 0.0
-    for bi in range(b):
-        n = int(lens[bi])
-        if n == 0:
-            continue
-        for h in range(hq):
-            kf = kall[bi, h // g, :n]
-            s = qf[bi, h] @ kf.T / math.sqrt(d)
-            for t in range(sq):
-                vis = min(n, n - sq + t + 1) if causal else n
-                if vis <= 0:
-                    continue
-                row = s[t, :vis]
-                smax = max(smax, float(np.abs(row).max()))
-                mx = row.max()
-                lse[bi, h, t] = mx + np.log(np.exp(row - mx).sum())
-    return lse, smax
-
-
-def _check_lse(lse, ref, smax, what):
-    got = lse.detach().cpu().numpy().astype(np.float64)
-    empty = np.isneginf(ref)
-    assert np.array_equal(np.isneginf(got), empty), what
-    gate = 2.0 ** -10 * smax + 1e-5
-    err = float(np.abs(got[~empty] - ref[~empty]).max()) if (~empty).any() else 0.0
-    print(f"{what}: lse err {err:.3e} gate {gate:.3e}")
-    assert err <= gate, (what, err, gate)
-
-
-def _check_f16(out, ref, what, gate=GATE_F16):
-    d = oracle.max_abs_diff(_bits(out), ref)
-    print(f"{what}: max_abs_diff {d:.3e}")
-    assert d <= gate, (what, d)
-
-
-def _ref_torch(q, k, v, lens, causal):
-    """fp32 torch reference on the device: (O [B,Hq,Sq,D], LSE [B,Hq,Sq]); rows
-    past each length are never touched (they may hold NaN)."""
-    b, hq, sq, d = q.shape
-    hkv, cap = k.shape[1], k.shape[2]
-    g = hq // hkv
-    key = torch.arange(cap, device=q.device)
-    live = key[None, :] < lens[:, None].to(q.device)                      # [B, cap]
-    kf = torch.where(live[:, None, :, None], k.float(), 0.0).repeat_interleave(g, 1)
-    vf = torch.where(live[:, None, :, None], v.float(), 0.0).repeat_interleave(g, 1)
-    s = q.float() @ kf.transpose(-1, -2) / math.sqrt(d)                   # [B, Hq, Sq, cap]
-    lim = lens[:, None].to(q.device).expand(b, sq)
-    if causal:
-        lim = lim - sq + 1 + torch.arange(sq, device=q.device)[None, :]
-    vis = key[None, None, :] < lim[:, :, None]                            # [B, Sq, cap]
-    s = s.masked_fill(~vis[:, None], float("-inf"))
-    lse = torch.logsumexp(s, -1)
-    p = torch.nan_to_num(torch.exp(s - lse[..., None]), nan=0.0)
-    return p @ vf, lse
-
-
-def _lens(vals):
-    return torch.tensor(list(vals), dtype=torch.int32, device=DEV)
-
-
-def _ws_counters_zero():
-    dev = torch.cuda.current_device()
-    st = torch.cuda.current_stream().cuda_stream
-    buf = fa_mi355x._WS_BUF.get((dev, st))
-    assert buf is not None, "the split launch took no workspace"
-    torch.cuda.synchronize()
-    return int(torch.count_nonzero(buf[:65536]).item()) == 0
 
 
 # ---- wave and tile edges --------------------------------------------------------
@@ -170,15 +31,15 @@ EDGE_LENS = (1, 2, 63, 64, 65, 255, 256, 257, 300)
 def test_tile_edges(d, causal, n):
     """Fewer tiles than waves, the ragged last tile, one full wave round +-1
     (B = 1, one head, one query token; the cache's capacity is 300 rows)."""
-    q, k, v = _inputs(1, 1, 1, 1, 300, d)
+    q, k, v = dr.inputs(1, 1, 1, 1, 300, d)
     lens = np.array([n])
-    out, lse = fa_mi355x.flash_attention_decode(_dev(q), _dev(k), _dev(v), _lens(lens),
+    out, lse = fa_mi355x.flash_attention_decode(dr.dev(q), dr.dev(k), dr.dev(v), dr.lens(lens),
                                                 causal=causal, return_lse=True)
-    _check_f16(out, _oracle_decode(q, k, v, lens, causal), f"edges d={d} causal={causal} len={n}")
-    ref, smax = _lse_ref(q, k, v, lens, causal)
-    _check_lse(lse, ref, smax, f"edges d={d} causal={causal} len={n}")
+    dr.check_f16(out, dr.oracle_decode(q, k, v, lens, causal), f"edges d={d} causal={causal} len={n}")
+    ref, smax = dr.lse_ref(q, k, v, lens, causal)
+    dr.check_lse(lse, ref, smax, f"edges d={d} causal={causal} len={n}")
     if n == 1:  # one key: P = 1, O is V[0] exactly
-        assert np.array_equal(_bits(out)[0, 0, 0], v[0, 0, 0])
+        assert np.array_equal(dr.bits(out)[0, 0, 0], v[0, 0, 0])
 
 
 # ---- groups ---------------------------------------------------------------------
@@ -193,12 +54,12 @@ def test_groups(g, sq):
     row group; a query head's output depends on K/V head h // G only."""
     b, hkv, cap = 2, 2, 1000
     lens = np.array([300, 1000])
-    q, k, v = _inputs(b, hkv * g, hkv, sq, cap, 128)
-    tq, tk, tv, tl = _dev(q), _dev(k), _dev(v), _lens(lens)
+    q, k, v = dr.inputs(b, hkv * g, hkv, sq, cap, 128)
+    tq, tk, tv, tl = dr.dev(q), dr.dev(k), dr.dev(v), dr.lens(lens)
     out, lse = fa_mi355x.flash_attention_decode(tq, tk, tv, tl, causal=True, return_lse=True)
-    _check_f16(out, _oracle_decode(q, k, v, lens, True), f"groups G={g} Sq={sq}")
-    ref, smax = _lse_ref(q, k, v, lens, True)
-    _check_lse(lse, ref, smax, f"groups G={g} Sq={sq}")
+    dr.check_f16(out, dr.oracle_decode(q, k, v, lens, True), f"groups G={g} Sq={sq}")
+    ref, smax = dr.lse_ref(q, k, v, lens, True)
+    dr.check_lse(lse, ref, smax, f"groups G={g} Sq={sq}")
     # swap the K/V heads (and the query heads with them): outputs swap
     perm = [1, 0]
     q2 = tq.view(b, hkv, g, sq, 128)[:, perm].reshape(tq.shape).contiguous()
@@ -211,16 +72,16 @@ def test_groups(g, sq):
 @pytest.mark.parametrize("g,sq,d", [(4, 4, 128), (7, 3, 64), (16, 5, 128)])
 def test_groups_bf16(g, sq, d):
     b, hkv, cap = 2, 2, 1000
-    lens = _lens([300, 1000])
-    q, k, v = (_dev(a).to(torch.bfloat16) for a in _inputs(b, hkv * g, hkv, sq, cap, d))
+    lens = dr.lens([300, 1000])
+    q, k, v = (dr.dev(a).to(torch.bfloat16) for a in dr.inputs(b, hkv * g, hkv, sq, cap, d))
     out, lse = fa_mi355x.flash_attention_decode(q, k, v, lens, causal=True, return_lse=True)
-    ro, rl = _ref_torch(q, k, v, lens, True)
+    ro, rl = dr.ref_torch(q, k, v, lens, True)
     err = float((out.float() - ro).abs().max())
     print(f"bf16 G={g} Sq={sq} d={d}: max err {err:.3e}")
-    assert err <= GATE_BF16
+    assert err <= dr.GATE_BF16
     del rl
-    ref, smax = _lse_ref(q, k, v, [300, 1000], True)  # float64, of the bf16 inputs
-    _check_lse(lse, ref, smax, f"bf16 G={g} Sq={sq} d={d}")
+    ref, smax = dr.lse_ref(q, k, v, [300, 1000], True)  # float64, of the bf16 inputs
+    dr.check_lse(lse, ref, smax, f"bf16 G={g} Sq={sq} d={d}")
 
 
 # ---- causal with Sq > 1 ---------------------------------------------------------
@@ -232,25 +93,25 @@ CAUSAL_ROWS = [(sq, n) for sq in (2, 5, 16) for n in (sq, sq + 1, 64, 65, 200)]
 def test_causal_rows(sq, n):
     """Row t against the oracle row at position len - Sq + t (B = 1)."""
     lens = np.array([n])
-    q, k, v = _inputs(1, 2, 1, sq, 200, 128)
-    out, lse = fa_mi355x.flash_attention_decode(_dev(q), _dev(k), _dev(v), _lens(lens),
+    q, k, v = dr.inputs(1, 2, 1, sq, 200, 128)
+    out, lse = fa_mi355x.flash_attention_decode(dr.dev(q), dr.dev(k), dr.dev(v), dr.lens(lens),
                                                 causal=True, return_lse=True)
-    _check_f16(out, _oracle_decode(q, k, v, lens, True), f"causal Sq={sq} len={n}")
-    ref, smax = _lse_ref(q, k, v, lens, True)
-    _check_lse(lse, ref, smax, f"causal Sq={sq} len={n}")
+    dr.check_f16(out, dr.oracle_decode(q, k, v, lens, True), f"causal Sq={sq} len={n}")
+    ref, smax = dr.lse_ref(q, k, v, lens, True)
+    dr.check_lse(lse, ref, smax, f"causal Sq={sq} len={n}")
 
 
 def test_causal_short_cache():
     """kv_lens = 3 with Sq = 5: the first two rows see no key."""
     lens = np.array([3])
-    q, k, v = _inputs(1, 2, 1, 5, 64, 128)
-    out, lse = fa_mi355x.flash_attention_decode(_dev(q), _dev(k), _dev(v), _lens(lens),
+    q, k, v = dr.inputs(1, 2, 1, 5, 64, 128)
+    out, lse = fa_mi355x.flash_attention_decode(dr.dev(q), dr.dev(k), dr.dev(v), dr.lens(lens),
                                                 causal=True, return_lse=True)
     assert int(torch.count_nonzero(out[:, :, :2]).item()) == 0
     assert bool(torch.isneginf(lse[:, :, :2]).all())
-    _check_f16(out, _oracle_decode(q, k, v, lens, True), "short cache")
-    ref, smax = _lse_ref(q, k, v, lens, True)
-    _check_lse(lse, ref, smax, "short cache")
+    dr.check_f16(out, dr.oracle_decode(q, k, v, lens, True), "short cache")
+    ref, smax = dr.lse_ref(q, k, v, lens, True)
+    dr.check_lse(lse, ref, smax, "short cache")
 
 
 # ---- ragged batch ---------------------------------------------------------------
@@ -259,22 +120,22 @@ def test_causal_short_cache():
 def test_ragged_batch_nan_padding(splits):
     lens = np.array([0, 1, 64, 65, 777, 1100])
     b, hq, hkv, cap = 6, 8, 2, 1100
-    q, k, v = _inputs(b, hq, hkv, 1, cap, 128)
+    q, k, v = dr.inputs(b, hq, hkv, 1, cap, 128)
     k, v = k.copy(), v.copy()
     for i, n in enumerate(lens):  # capacity padding: NaN bit patterns
         k[i, :, n:] = 0x7e00
         v[i, :, n:] = 0xfe01
-    tq, tk, tv = _dev(q), _dev(k), _dev(v)
-    out, lse = fa_mi355x.flash_attention_decode(tq, tk, tv, _lens(lens), causal=True,
+    tq, tk, tv = dr.dev(q), dr.dev(k), dr.dev(v)
+    out, lse = fa_mi355x.flash_attention_decode(tq, tk, tv, dr.lens(lens), causal=True,
                                                 return_lse=True, num_splits=splits)
     assert bool(torch.isfinite(out).all())
-    _check_f16(out, _oracle_decode(q, k, v, lens, True), f"ragged splits={splits}")
-    ref, smax = _lse_ref(q, k, v, lens, True)
-    _check_lse(lse, ref, smax, f"ragged splits={splits}")
+    dr.check_f16(out, dr.oracle_decode(q, k, v, lens, True), f"ragged splits={splits}")
+    ref, smax = dr.lse_ref(q, k, v, lens, True)
+    dr.check_lse(lse, ref, smax, f"ragged splits={splits}")
     assert int(torch.count_nonzero(out[0]).item()) == 0
     # caches truncated to a common length, no kv_lens: the same bits
     for n in (65, 777):
-        explicit = fa_mi355x.flash_attention_decode(tq, tk, tv, _lens([n] * b), causal=True,
+        explicit = fa_mi355x.flash_attention_decode(tq, tk, tv, dr.lens([n] * b), causal=True,
                                                     num_splits=splits)
         trunc = fa_mi355x.flash_attention_decode(tq, tk[:, :, :n].contiguous(),
                                                  tv[:, :, :n].contiguous(), None, causal=True,
@@ -287,13 +148,13 @@ def test_ragged_batch_nan_padding(splits):
 
 def test_forced_splits():
     b, hq, hkv, n = 1, 8, 2, 1000
-    q, k, v = _inputs(b, hq, hkv, 1, n, 128)
-    tq, tk, tv = _dev(q), _dev(k), _dev(v)
+    q, k, v = dr.inputs(b, hq, hkv, 1, n, 128)
+    tq, tk, tv = dr.dev(q), dr.dev(k), dr.dev(v)
     lens = np.array([n])
-    ref = _oracle_decode(q, k, v, lens, True)
-    lref, smax = _lse_ref(q, k, v, lens, True)
+    ref = dr.oracle_decode(q, k, v, lens, True)
+    lref, smax = dr.lse_ref(q, k, v, lens, True)
     base = fa_mi355x.flash_attention_decode(tq, tk, tv, causal=True, num_splits=1)
-    _check_f16(base, ref, "splits=1")
+    dr.check_f16(base, ref, "splits=1")
     dev = torch.cuda.current_device()
     st = torch.cuda.current_stream().cuda_stream
     # len 1000 is 16 tiles: 16 pieces have one tile each (three waves idle), 32 pieces
@@ -301,43 +162,43 @@ def test_forced_splits():
     for ns in (2, 3, 7, 16, 32):
         out, lse = fa_mi355x.flash_attention_decode(tq, tk, tv, causal=True, num_splits=ns,
                                                     return_lse=True)
-        assert _ws_counters_zero(), ns
-        _check_f16(out, ref, f"splits={ns}")
-        _check_lse(lse, lref, smax, f"splits={ns}")
+        assert dr.ws_counters_zero(), ns
+        dr.check_f16(out, ref, f"splits={ns}")
+        dr.check_lse(lse, lref, smax, f"splits={ns}")
         diff = float((out.float() - base.float()).abs().max())
         print(f"splits={ns}: vs one piece {diff:.3e}")
         assert diff <= 2e-4, (ns, diff)
         again = fa_mi355x.flash_attention_decode(tq, tk, tv, causal=True, num_splits=ns)
         assert torch.equal(out, again), ns
-        assert _ws_counters_zero(), ns
+        assert dr.ws_counters_zero(), ns
         # poison the slabs: every slab the merge reads was written by this launch
         fa_mi355x._WS_BUF[(dev, st)][65536:].fill_(0xff)
         poisoned = fa_mi355x.flash_attention_decode(tq, tk, tv, causal=True, num_splits=ns)
         assert torch.equal(out, poisoned), ns
-        assert _ws_counters_zero(), ns
+        assert dr.ws_counters_zero(), ns
 
 
 def test_workspace_shared_with_forward():
     """One per-stream workspace serves decode and forward launches in any order."""
-    q, k, v = _inputs(1, 8, 2, 1, 1000, 128)
-    tq, tk, tv = _dev(q), _dev(k), _dev(v)
-    ref = _oracle_decode(q, k, v, np.array([1000]), True)
+    q, k, v = dr.inputs(1, 8, 2, 1, 1000, 128)
+    tq, tk, tv = dr.dev(q), dr.dev(k), dr.dev(v)
+    ref = dr.oracle_decode(q, k, v, np.array([1000]), True)
     fq, fk, fv = oracle.gen_inputs(1, 4, 8192, 128, 7)
     assert fa_mi355x.workspace_bytes(1, 4, 8192, 128, True) > 65536  # the split tier
     rows = np.array([0, 255, 4096, 8191])
     fref = oracle.attention_rows(fq[0, 3], fk[0, 3], fv[0, 3], rows, True)
-    sq_, sk_, sv_ = _inputs(1, 4, 2, 2, 520, 64)
-    sref = _oracle_decode(sq_, sk_, sv_, np.array([520]), True)
+    sq_, sk_, sv_ = dr.inputs(1, 4, 2, 2, 520, 64)
+    sref = dr.oracle_decode(sq_, sk_, sv_, np.array([520]), True)
 
     d1 = fa_mi355x.flash_attention_decode(tq, tk, tv, causal=True, num_splits=4)
-    fo = fa_mi355x.flash_attention_fwd(_dev(fq), _dev(fk), _dev(fv), causal=True)
+    fo = fa_mi355x.flash_attention_fwd(dr.dev(fq), dr.dev(fk), dr.dev(fv), causal=True)
     d2 = fa_mi355x.flash_attention_decode(tq, tk, tv, causal=True, num_splits=4)
-    d3 = fa_mi355x.flash_attention_decode(_dev(sq_), _dev(sk_), _dev(sv_), causal=True, num_splits=2)
-    assert _ws_counters_zero()
-    _check_f16(d1, ref, "decode before forward")
+    d3 = fa_mi355x.flash_attention_decode(dr.dev(sq_), dr.dev(sk_), dr.dev(sv_), causal=True, num_splits=2)
+    assert dr.ws_counters_zero()
+    dr.check_f16(d1, ref, "decode before forward")
     assert torch.equal(d1, d2)
-    _check_f16(fo[0, 3, rows], fref, "forward between decodes")
-    _check_f16(d3, sref, "smaller decode")
+    dr.check_f16(fo[0, 3, rows], fref, "forward between decodes")
+    dr.check_f16(d3, sref, "smaller decode")
 
 
 # ---- peaked softmax -------------------------------------------------------------
@@ -346,46 +207,46 @@ def test_workspace_shared_with_forward():
 def test_peaked_softmax(dtype):
     """q and k scaled by 3: the in-wave rescale, the in-CU merge and the
     cross-piece merge all see very different maxima."""
-    q, k, v = _inputs(1, 8, 2, 1, 1000, 128)
-    tq, tk, tv = (_dev(a) for a in (q, k, v))
+    q, k, v = dr.inputs(1, 8, 2, 1, 1000, 128)
+    tq, tk, tv = (dr.dev(a) for a in (q, k, v))
     tq, tk = tq * 3, tk * 3
     if dtype is torch.bfloat16:
         tq, tk, tv = (t.to(dtype) for t in (tq, tk, tv))
         out = fa_mi355x.flash_attention_decode(tq, tk, tv, causal=True, num_splits=4)
-        ro, _ = _ref_torch(tq, tk, tv, _lens([1000]), True)
+        ro, _ = dr.ref_torch(tq, tk, tv, dr.lens([1000]), True)
         err = float((out.float() - ro).abs().max())
         print(f"peaked bf16: {err:.3e}")
-        assert err <= GATE_BF16
+        assert err <= dr.GATE_BF16
         return
     out = fa_mi355x.flash_attention_decode(tq, tk, tv, causal=True, num_splits=4)
-    ref = _oracle_decode(_bits(tq), _bits(tk), v, np.array([1000]), True)
-    _check_f16(out, ref, "peaked fp16")
+    ref = dr.oracle_decode(dr.bits(tq), dr.bits(tk), v, np.array([1000]), True)
+    dr.check_f16(out, ref, "peaked fp16")
 
 
 # ---- agreement with the forward path -------------------------------------------
 
 def test_agrees_with_forward():
     q, k, v = oracle.gen_inputs(1, 4, 300, 128, 11)
-    tq, tk, tv = _dev(q), _dev(k), _dev(v)
+    tq, tk, tv = dr.dev(q), dr.dev(k), dr.dev(v)
     fwd = fa_mi355x.flash_attention_fwd(tq, tk, tv, causal=True)[:, :, -8:]
     dec = fa_mi355x.flash_attention_decode(tq[:, :, -8:].contiguous(), tk, tv, causal=True)
     assert float((fwd.float() - dec.float()).abs().max()) <= 2e-3
     ref = np.stack([oracle.attention_rows(q[0, h], k[0, h], v[0, h], np.arange(292, 300), True)
                     for h in range(4)])[None]
-    _check_f16(fwd, ref, "forward, last 8 rows")
-    _check_f16(dec, ref, "decode, last 8 rows")
+    dr.check_f16(fwd, ref, "forward, last 8 rows")
+    dr.check_f16(dec, ref, "decode, last 8 rows")
 
 
 # ---- long and large -------------------------------------------------------------
 
 def test_long_cache():
     n = 131072 + 17
-    q, k, v = _inputs(1, 8, 1, 1, n, 128)
-    out, lse = fa_mi355x.flash_attention_decode(_dev(q), _dev(k), _dev(v), causal=True,
+    q, k, v = dr.inputs(1, 8, 1, 1, n, 128)
+    out, lse = fa_mi355x.flash_attention_decode(dr.dev(q), dr.dev(k), dr.dev(v), causal=True,
                                                 return_lse=True)
-    _check_f16(out, _oracle_decode(q, k, v, np.array([n]), True), "long cache")
-    ref, smax = _lse_ref(q, k, v, np.array([n]), True)
-    _check_lse(lse, ref, smax, "long cache")
+    dr.check_f16(out, dr.oracle_decode(q, k, v, np.array([n]), True), "long cache")
+    ref, smax = dr.lse_ref(q, k, v, np.array([n]), True)
+    dr.check_lse(lse, ref, smax, "long cache")
 
 
 def test_cache_past_4gib():
@@ -401,10 +262,10 @@ def test_cache_past_4gib():
             t[i] = torch.rand((h, cap, d), generator=gen, device=DEV, dtype=torch.float16) * 2 - 1
     q = torch.rand((b, h, 1, d), generator=gen, device=DEV, dtype=torch.float16) * 2 - 1
     out = fa_mi355x.flash_attention_decode(q, k, v, causal=True)
-    ro, _ = _ref_torch(q[-1:, -1:], k[-1:, -1:], v[-1:, -1:], _lens([cap]), True)
+    ro, _ = dr.ref_torch(q[-1:, -1:], k[-1:, -1:], v[-1:, -1:], dr.lens([cap]), True)
     err = float((out[-1:, -1:].float() - ro).abs().max())
     print(f"4 GiB cache: {err:.3e}")
-    assert err <= GATE_F16
+    assert err <= dr.GATE_F16
     del k, v
     torch.cuda.empty_cache()
 
@@ -416,14 +277,14 @@ def test_wrapper_rejections_on_device():
     and nothing is launched (an int64 kv_lens would otherwise be read as int32)."""
     import fa_mi355x.torch_op  # noqa: F401
 
-    q, k, v = (_dev(a) for a in _inputs(2, 8, 2, 1, 600, 128))
+    q, k, v = (dr.dev(a) for a in dr.inputs(2, 8, 2, 1, 600, 128))
     err = fa_mi355x.FlashAttentionError
     with pytest.raises(err, match="kv_lens must be int32"):
         fa_mi355x.flash_attention_decode(q, k, v, torch.tensor([5, 600], device=DEV))
     with pytest.raises(err, match="kv_lens must be a tensor on"):
         fa_mi355x.flash_attention_decode(q, k, v, torch.tensor([5, 600], dtype=torch.int32))
     with pytest.raises(err, match="kv_lens must be a contiguous"):
-        fa_mi355x.flash_attention_decode(q, k, v, _lens([5, 600, 7]))
+        fa_mi355x.flash_attention_decode(q, k, v, dr.lens([5, 600, 7]))
     with pytest.raises(err, match="must have one shape"):
         fa_mi355x.flash_attention_decode(q, k, v[:, :, :500].contiguous())
     with pytest.raises(err, match="not a multiple of heads_kv"):
@@ -442,8 +303,8 @@ def test_wrapper_rejections_on_device():
 def test_torch_op_matches_python_entry():
     import fa_mi355x.torch_op  # noqa: F401
 
-    q, k, v = (_dev(a) for a in _inputs(2, 8, 2, 2, 600, 128))
-    lens = _lens([77, 600])
+    q, k, v = (dr.dev(a) for a in dr.inputs(2, 8, 2, 2, 600, 128))
+    lens = dr.lens([77, 600])
     want = fa_mi355x.flash_attention_decode(q, k, v, lens, causal=True)
     got = torch.ops.fa_mi355x.decode(q, k, v, lens, True)
     assert torch.equal(got, want)
@@ -461,8 +322,8 @@ def test_op_in_hip_graph_follows_lengths():
     """One linear capture, one replay; kv_lens changes between them."""
     import fa_mi355x.torch_op  # noqa: F401
 
-    q, k, v = (_dev(a) for a in _inputs(1, 8, 2, 1, 2048, 128))
-    lens = _lens([2048])
+    q, k, v = (dr.dev(a) for a in dr.inputs(1, 8, 2, 1, 2048, 128))
+    lens = dr.lens([2048])
     for n in (2048, 700):  # eager references (and the first-launch set-up) outside the capture
         lens.fill_(n)
         torch.ops.fa_mi355x.decode(q, k, v, lens, True)

@@ -6,51 +6,27 @@ entries, the wrapper's rejections, the ops' schemas and fake implementations,
 the exactness of E4M3 -> fp16 / bf16, and the kernels' compile-time resource
 usage -- no kernel is launched (no GPU here)."""
 import ctypes
-import importlib.util
 import os
-import re
-import subprocess
-import types
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import capi_checks
+from capi_checks import fa as _fa
+
 SYMBOLS = ("fa_decode_kv8_f16", "fa_decode_kv8_bf16", "fa_decode_paged_kv8_f16",
            "fa_decode_paged_kv8_bf16")
 FP8 = torch.float8_e4m3fn
 
 
-def _fa():
-    import fa_mi355x
-
-    return fa_mi355x
-
-
-def _load(name, fname):
-    spec = importlib.util.spec_from_file_location(
-        name, os.path.join(os.path.dirname(os.path.abspath(__file__)), fname))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 def test_library_exports_kv8_symbols():
-    fa = _fa()
-    out = subprocess.run(["nm", "-D", "--defined-only", fa.library_path()], capture_output=True,
-                         text=True, check=True).stdout
-    syms = {line.split()[-1] for line in out.splitlines() if line.strip()}
-    header = open(os.path.join(ROOT, "include", "fa_mi355x.h")).read()
-    for s in SYMBOLS:
-        assert s in syms, s
-        assert s in fa.EXPORTED_SYMBOLS, s
-        assert re.search(r"\b%s\s*\(" % s, header), s
+    capi_checks.assert_exported(SYMBOLS)
 
 
 class _Kv8Lib:
     """The loaded library with the 16-bit decode entries' names bound to the
     kv8 entries (the two scale pointers appended), everything else as it is:
-    the 16-bit tests' argument tables then run against the new entries."""
+    the 16-bit entries' argument tables then run against the new entries."""
 
     def __init__(self, lib, scales):
         self._lib = lib
@@ -65,20 +41,21 @@ class _Kv8Lib:
         return getattr(self._lib, name)
 
 
+ARGUMENT_TABLES = {"test_decode_cpu.py": capi_checks.decode_argument_checks,
+                   "test_decode_paged_cpu.py": capi_checks.decode_paged_argument_checks}
+
+
 @pytest.mark.parametrize("scales", [(None, None), (ctypes.c_void_p(0x2000), ctypes.c_void_p(0x3000)),
                                     (None, ctypes.c_void_p(0x3000))],
                          ids=["null-scales", "scales", "v-scale-only"])
-@pytest.mark.parametrize("fname", ["test_decode_cpu.py", "test_decode_paged_cpu.py"])
+@pytest.mark.parametrize("fname", list(ARGUMENT_TABLES))
 def test_argument_checks(fname, scales):
-    """The same status codes in the same order as the 16-bit twins, all before
-    any launch (fake pointers), whatever the scale pointers are."""
+    """The same status codes in the same order as the 16-bit twins (fname: the
+    file whose test_argument_checks runs the same table against the 16-bit
+    entries), all before any launch (fake pointers), whatever the scale
+    pointers are."""
     fa = _fa()
-    mod = _load("_kv8_args_" + fname[:-3], fname)
-    shim = types.SimpleNamespace(**{k: getattr(fa, k) for k in dir(fa) if k.startswith("FA_")})
-    kv8 = _Kv8Lib(fa.load_library(), scales)
-    shim.load_library = lambda: kv8
-    mod._fa = lambda: shim
-    mod.test_argument_checks()
+    ARGUMENT_TABLES[fname](fa, _Kv8Lib(fa.load_library(), scales))
 
 
 def _t(shape, dtype=torch.float16, device="meta"):
@@ -207,30 +184,19 @@ def test_e4m3_is_exact_in_fp16_and_bf16():
         assert bool(torch.isnan(mid[~finite].float()).all()), dt
 
 
-@pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
+@pytest.mark.skipif(not os.path.exists(capi_checks.HIPCC), reason="needs hipcc")
 def test_no_kv8_kernel_uses_scratch():
     """2 dtypes x 2 head dims x 1 / 2 / 4 row blocks x contiguous / paged = 24
     kv8 kernels, every one with its state in registers."""
-    pkg = os.path.join(ROOT, "flash-attention-cuda_amd")
-    procs = []
-    for unit in ("fa_decode_kv8.hip", "fa_decode_paged_kv8.hip"):
-        cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
-               "-fno-honor-nans", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(pkg, "csrc"),
-               "-c", os.path.join(pkg, "csrc", unit), "-o", os.devnull,
-               "-Rpass-analysis=kernel-resource-usage"]
-        procs.append((unit, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                                             text=True)))
+    units = ("fa_decode_kv8.hip", "fa_decode_paged_kv8.hip")
     total = 0
-    for unit, proc in procs:
-        _, err = proc.communicate(timeout=900)
-        assert proc.returncode == 0, err[-2000:]
-        names = re.findall(r"Function Name: (\S+)", err)
-        scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", err)]
-        assert len(names) == 12 and len(names) == len(scratch), (unit, len(names), len(scratch))
+    for unit, kernels in zip(units, capi_checks.kernel_resource_usage(units, timeout=900)):
+        names = [n for n, _, _ in kernels]
+        assert len(names) == 12, (unit, len(names))
         paged = "paged" in unit
         want = "DecodePagedKv8Params" if paged else "DecodeKv8Params"
         assert all("fa_decode_kernel" in n and want in n for n in names), names
-        spills = {n: s for n, s in zip(names, scratch) if s}
+        spills = {n: s for n, s, _ in kernels if s}
         assert not spills, spills
         total += len(names)
     assert total == 24

@@ -4,8 +4,7 @@ in {64, 128} x NB in {1, 2, 4} x {contiguous, paged} = 24 kernels).
 
 The references see the DEQUANTISED cache (K8.float() * k_scale), so the 3-bit
 mantissa of E4M3 is not in the comparison and the gates are the project's own
-(helpers of tests/test_decode_gpu.py and tests/test_decode_paged_gpu.py,
-loaded by file path), no new tolerance:
+(helpers of tests/decode_refs.py), no new tolerance:
   * fp16 O: the CPU oracle, 1e-3.
   * bf16 O: fp32 torch on the same inputs, 5e-3.
   * LSE: float64 reference, 2^-10 * max|scaled score| + 1e-5.
@@ -16,52 +15,23 @@ in fp16 and in bf16 (both asserted in _case8), so the CPU oracle takes them as
 fp16 bits.  Rows past each length hold the byte 0x7f (the E4M3 NaN).  Each K/V
 head has its own scales: a kernel that applies head 0's everywhere fails.
 """
-import importlib.util
-import os
-
 import numpy as np
 import pytest
 import torch
 
+import decode_refs as dr
 import fa_mi355x
 
 pytestmark = pytest.mark.gpu
 
-
-def _load(name, fname):
-    spec = importlib.util.spec_from_file_location(
-        name, os.path.join(os.path.dirname(os.path.abspath(__file__)), fname))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-_h = _load("_decode_gpu_helpers_kv8", "test_decode_gpu.py")
-_p = _load("_decode_paged_gpu_helpers_kv8", "test_decode_paged_gpu.py")
-_inputs, _oracle_decode, _lse_ref, _check_lse, _check_f16, _ref_torch = (
-    _h._inputs, _h._oracle_decode, _h._lse_ref, _h._check_lse, _h._check_f16, _h._ref_torch)
-_dev, _lens, _bits, _ws_counters_zero = _h._dev, _h._lens, _h._bits, _h._ws_counters_zero
-_paginate, _gather = _p._paginate, _p._gather
-
 DEV = "cuda"
 FP8 = torch.float8_e4m3fn
-GATE_F16, GATE_BF16 = _h.GATE_F16, _h.GATE_BF16
 PAD8 = 0x7f  # the E4M3 NaN
 K_SCALE = (2.0 ** -6, 2.0 ** -3)
 V_SCALE = (2.0 ** -4, 2.0 ** -8)
 
-DTYPES = [pytest.param(torch.float16, id="fp16"), pytest.param(torch.bfloat16, id="bf16")]
-
 decode = fa_mi355x.flash_attention_decode
 decode_paged = fa_mi355x.flash_attention_decode_paged
-
-
-def _nb(g, sq):
-    return 1 if g * sq <= 16 else (2 if g * sq <= 32 else 4)
-
-
-def _name(dtype):
-    return "fp16" if dtype is torch.float16 else "bf16"
 
 
 def _scale_t(vals):
@@ -91,60 +61,29 @@ def _case8(b, hq, hkv, sq, cap, d, lens, dtype, k_scale=K_SCALE, v_scale=V_SCALE
     dev:  (q, dequantised k, dequantised v) device tensors, q of `dtype`, k / v of
           `dtype` (exact=True: a lossless cast, asserted) or fp32;
     q8:   (q, k8, v8) for the entry, the caches' rows past each length 0x7f."""
-    q, k, v = _inputs(b, hq, hkv, sq, cap, d)
-    tq = _dev(q).to(dtype)
-    k8, kd = _quant(_dev(k).float(), k_scale)
-    v8, vd = _quant(_dev(v).float(), v_scale)
+    q, k, v = dr.inputs(b, hq, hkv, sq, cap, d)
+    tq = dr.dev(q).to(dtype)
+    k8, kd = _quant(dr.dev(k).float(), k_scale)
+    v8, vd = _quant(dr.dev(v).float(), v_scale)
     host = None
     if exact:
         for x in (kd, vd):  # the dequantised values are exact in fp16 and in bf16
             assert torch.equal(x.to(torch.float16).float(), x)
             assert torch.equal(x.to(torch.bfloat16).float(), x)
-        host = (q, _bits(kd.to(torch.float16)), _bits(vd.to(torch.float16)))
+        host = (q, dr.bits(kd.to(torch.float16)), dr.bits(vd.to(torch.float16)))
         kd, vd = kd.to(dtype), vd.to(dtype)
     return host, (tq, kd, vd), (tq, _pad8(k8, lens), _pad8(v8, lens))
 
 
-def _refs(host, dev, lens, causal, dtype):
-    """(O reference, float64 LSE, max |scaled score|) on the dequantised cache:
-    fp16 from the CPU oracle, bf16 from fp32 torch."""
-    if dtype is torch.float16 and host is not None:
-        ro = _oracle_decode(*host, lens, causal)
-        lref, smax = _lse_ref(host[0], host[1], host[2], lens, causal)
-    else:
-        ro = _ref_torch(*dev, _lens(lens), causal)[0]
-        lref, smax = _lse_ref(dev[0], dev[1], dev[2], lens, causal)
-    return ro, lref, smax
-
-
-def _check(out, lse, refs, dtype, what):
-    ro, lref, smax = refs
-    assert bool(torch.isfinite(out).all()), what
-    if isinstance(ro, np.ndarray):
-        _check_f16(out, ro, what)
-    else:
-        gate = GATE_F16 if dtype is torch.float16 else GATE_BF16
-        err = float((out.float() - ro).abs().max())
-        print(f"{what}: max_abs_diff {err:.3e}")
-        assert err <= gate, (what, err)
-    _check_lse(lse, lref, smax, what)
-    unseen = torch.from_numpy(np.isneginf(lref)).to(out.device)
-    assert int(torch.count_nonzero(out[unseen]).item()) == 0, what
-
-
 def _paginate8(k8, v8, page_size, lens, **kw):
-    """_paginate on the caches' bytes: FP8 pools whose unused pages and rows
+    """dr.paginate on the caches' bytes: FP8 pools whose unused pages and rows
     past each length are 0xff / 0x7f (both NaN in E4M3)."""
-    kp, vp, table = _paginate(k8.view(torch.uint8), v8.view(torch.uint8), page_size, lens, **kw)
+    kp, vp, table = dr.paginate(k8.view(torch.uint8), v8.view(torch.uint8), page_size, lens, **kw)
     return kp.view(FP8), vp.view(FP8), table
 
 
 def _gather8(pages, table):
-    return _gather(pages.view(torch.uint8), table).view(FP8)
-
-
-def _same(a, b):
-    return torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+    return dr.gather(pages.view(torch.uint8), table).view(FP8)
 
 
 # ---- 1. every variant, split and unsplit --------------------------------------------
@@ -154,7 +93,7 @@ MATRIX_LENS = (70, 300, 640)
 
 @pytest.mark.parametrize("g,sq", [(5, 1), (7, 3), (4, 16), (16, 5)])
 @pytest.mark.parametrize("d", [128, 64])
-@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("dtype", dr.DTYPES)
 def test_variant_split_matrix(dtype, d, g, sq):
     """The shapes of test_decode_matrix_gpu.test_variant_split_matrix: 5 / 21 /
     64 / 80 rows per K/V head (NB = 1 / 2 / 4 / 4 with a second row group), the
@@ -164,30 +103,30 @@ def test_variant_split_matrix(dtype, d, g, sq):
     lens = np.array(MATRIX_LENS)
     host, dev, (tq, k8, v8) = _case8(b, hkv * g, hkv, sq, cap, d, lens, dtype)
     ks, vs = _scale_t(K_SCALE), _scale_t(V_SCALE)
-    tl = _lens(lens)
-    tag = f"kv8 {_name(dtype)} d={d} NB={_nb(g, sq)} G={g} Sq={sq}"
+    tl = dr.lens(lens)
+    tag = f"kv8 {dr.name(dtype)} d={d} NB={dr.nb(g, sq)} G={g} Sq={sq}"
     refs = {}
     for causal in (True, False):
-        refs[causal] = _refs(host, dev, lens, causal, dtype)
+        refs[causal] = dr.refs(host, dev, lens, causal, dtype)
         for ns in (1, 2, 3, 7):
             out, lse = decode(tq, k8, v8, tl, causal=causal, return_lse=True, num_splits=ns,
                               k_scale=ks, v_scale=vs)
-            _check(out, lse, refs[causal], dtype, f"contig {tag} causal={causal} ns={ns}")
+            dr.check(out, lse, refs[causal], dtype, f"contig {tag} causal={causal} ns={ns}")
             if ns > 1:
-                assert _ws_counters_zero(), (tag, causal, ns)
+                assert dr.ws_counters_zero(), (tag, causal, ns)
     kp, vp, table = _paginate8(k8, v8, 128, lens)
     for ns in (1, 3):
         out, lse = decode_paged(tq, kp, vp, table, tl, causal=True, return_lse=True, num_splits=ns,
                                 k_scale=ks, v_scale=vs)
-        _check(out, lse, refs[True], dtype, f"paged {tag} causal=True ns={ns}")
+        dr.check(out, lse, refs[True], dtype, f"paged {tag} causal=True ns={ns}")
         if ns > 1:
-            assert _ws_counters_zero(), (tag, "paged", ns)
+            assert dr.ws_counters_zero(), (tag, "paged", ns)
 
 
 # ---- 2. scales that are no powers of two --------------------------------------------
 
 @pytest.mark.parametrize("g,sq,d", [(5, 1, 64), (4, 16, 128)], ids=["NB1", "NB4"])
-@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("dtype", dr.DTYPES)
 def test_scales_not_powers_of_two(dtype, g, sq, d):
     """The dequantised cache is then no 16-bit tensor: the reference is fp32
     torch on K8.float() * k_scale, the gate the dtype's own."""
@@ -196,17 +135,17 @@ def test_scales_not_powers_of_two(dtype, g, sq, d):
     ksc, vsc = (0.0371, 0.0519), (1.73, 0.613)
     _, dev, (tq, k8, v8) = _case8(b, hkv * g, hkv, sq, cap, d, lens, dtype, ksc, vsc, exact=False)
     assert dev[1].dtype is torch.float32
-    refs = _refs(None, dev, lens, True, dtype)
+    refs = dr.refs(None, dev, lens, True, dtype)
     for ns in (1, 3):
         for entry in ("contig", "paged"):
             if entry == "contig":
-                out, lse = decode(tq, k8, v8, _lens(lens), causal=True, return_lse=True, num_splits=ns,
+                out, lse = decode(tq, k8, v8, dr.lens(lens), causal=True, return_lse=True, num_splits=ns,
                                   k_scale=_scale_t(ksc), v_scale=_scale_t(vsc))
             else:
                 kp, vp, table = _paginate8(k8, v8, 64, lens, seed=4)
-                out, lse = decode_paged(tq, kp, vp, table, _lens(lens), causal=True, return_lse=True,
+                out, lse = decode_paged(tq, kp, vp, table, dr.lens(lens), causal=True, return_lse=True,
                                         num_splits=ns, k_scale=_scale_t(ksc), v_scale=_scale_t(vsc))
-            _check(out, lse, refs, dtype, f"{entry} kv8 odd scales {_name(dtype)} d={d} G={g} Sq={sq} ns={ns}")
+            dr.check(out, lse, refs, dtype, f"{entry} kv8 odd scales {dr.name(dtype)} d={d} G={g} Sq={sq} ns={ns}")
 
 
 # ---- 3. paged == contiguous, bit for bit ---------------------------------------------
@@ -226,17 +165,17 @@ def test_paged_bit_identical_to_contiguous(d, page_size):
     for i, n in enumerate(lens):  # the table describes this cache
         assert torch.equal(gk[i, :, :n].view(torch.uint8), k8[i, :, :n].view(torch.uint8))
     for ns in (1, 3):
-        want = decode(tq, gk, gv, _lens(lens), causal=True, return_lse=True, num_splits=ns,
+        want = decode(tq, gk, gv, dr.lens(lens), causal=True, return_lse=True, num_splits=ns,
                       k_scale=ks, v_scale=vs)
-        got = decode_paged(tq, kp, vp, table, _lens(lens), causal=True, return_lse=True, num_splits=ns,
+        got = decode_paged(tq, kp, vp, table, dr.lens(lens), causal=True, return_lse=True, num_splits=ns,
                            k_scale=ks, v_scale=vs)
-        assert _same(got, want), (d, page_size, ns)
+        assert dr.same(got, want), (d, page_size, ns)
         assert bool(torch.isfinite(got[0]).all())
 
 
 # ---- 4. no scales = scales of one ---------------------------------------------------
 
-@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("dtype", dr.DTYPES)
 def test_none_scales_equal_ones(dtype):
     b, hkv, g, sq, cap, d = 2, 2, 4, 2, 320, 128
     lens = np.array([320, 77])
@@ -245,13 +184,13 @@ def test_none_scales_equal_ones(dtype):
     ones = _scale_t(one)
     kp, vp, table = _paginate8(k8, v8, 64, lens, seed=9)
     for ns in (1, 2):
-        want = decode(tq, k8, v8, _lens(lens), return_lse=True, num_splits=ns, k_scale=ones, v_scale=ones)
-        assert _same(decode(tq, k8, v8, _lens(lens), return_lse=True, num_splits=ns), want)
-        assert _same(decode(tq, k8, v8, _lens(lens), return_lse=True, num_splits=ns, v_scale=ones), want)
-        pwant = decode_paged(tq, kp, vp, table, _lens(lens), return_lse=True, num_splits=ns,
+        want = decode(tq, k8, v8, dr.lens(lens), return_lse=True, num_splits=ns, k_scale=ones, v_scale=ones)
+        assert dr.same(decode(tq, k8, v8, dr.lens(lens), return_lse=True, num_splits=ns), want)
+        assert dr.same(decode(tq, k8, v8, dr.lens(lens), return_lse=True, num_splits=ns, v_scale=ones), want)
+        pwant = decode_paged(tq, kp, vp, table, dr.lens(lens), return_lse=True, num_splits=ns,
                              k_scale=ones, v_scale=ones)
-        assert _same(decode_paged(tq, kp, vp, table, _lens(lens), return_lse=True, num_splits=ns), pwant)
-        assert _same(pwant, want)
+        assert dr.same(decode_paged(tq, kp, vp, table, dr.lens(lens), return_lse=True, num_splits=ns), pwant)
+        assert dr.same(pwant, want)
 
 
 # ---- 5. short rows and rows that see nothing ----------------------------------------
@@ -267,20 +206,20 @@ UNSEEN = [
 
 
 @pytest.mark.parametrize("sq,n", UNSEEN)
-@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("dtype", dr.DTYPES)
 def test_short_and_unseen_rows(dtype, sq, n):
     lens = np.array([n])
     host, dev, (tq, k8, v8) = _case8(1, 2, 1, sq, 192, 128, lens, dtype, K_SCALE[1:], V_SCALE[1:])
-    refs = _refs(host, dev, lens, True, dtype)
+    refs = dr.refs(host, dev, lens, True, dtype)
     if (sq, n) == (5, 3):
         assert np.isneginf(refs[1][:, :, :2]).all() and np.isfinite(refs[1][:, :, 2:]).all()
     ks, vs = _scale_t(K_SCALE[1:]), _scale_t(V_SCALE[1:])
     for ns in (1, 2, 3):
-        out, lse = decode(tq, k8, v8, _lens(lens), causal=True, return_lse=True, num_splits=ns,
+        out, lse = decode(tq, k8, v8, dr.lens(lens), causal=True, return_lse=True, num_splits=ns,
                           k_scale=ks, v_scale=vs)
-        _check(out, lse, refs, dtype, f"kv8 short {_name(dtype)} Sq={sq} len={n} ns={ns}")
+        dr.check(out, lse, refs, dtype, f"kv8 short {dr.name(dtype)} Sq={sq} len={n} ns={ns}")
         if ns > 1:
-            assert _ws_counters_zero(), (sq, n, ns)
+            assert dr.ws_counters_zero(), (sq, n, ns)
 
 
 def test_zero_lengths():
@@ -288,7 +227,7 @@ def test_zero_lengths():
     lens = np.array([0, 130, 0])
     _, _, (tq, k8, v8) = _case8(3, 8, 2, 2, 192, 64, lens, torch.float16)
     for ns in (1, 3):
-        out, lse = decode(tq, k8, v8, _lens(lens), return_lse=True, num_splits=ns,
+        out, lse = decode(tq, k8, v8, dr.lens(lens), return_lse=True, num_splits=ns,
                           k_scale=_scale_t(K_SCALE), v_scale=_scale_t(V_SCALE))
         for bi in (0, 2):
             assert int(torch.count_nonzero(out[bi]).item()) == 0
@@ -305,7 +244,7 @@ def test_nan_pages_and_junk_entries_never_read(splits):
     lens = (0, 129, 700, 1)
     _, _, (tq, k8, v8) = _case8(4, 8, 2, 2, 768, 128, lens, torch.float16)
     ks, vs = _scale_t(K_SCALE), _scale_t(V_SCALE)
-    tl = _lens(lens)
+    tl = dr.lens(lens)
     kp, vp, zeros = _paginate8(k8, v8, 128, lens, seed=5, filler=0)
     kp2, vp2, junk = _paginate8(k8, v8, 128, lens, seed=5, filler="junk")
     assert torch.equal(kp.view(torch.uint8), kp2.view(torch.uint8)) and not torch.equal(zeros, junk)
@@ -317,7 +256,7 @@ def test_nan_pages_and_junk_entries_never_read(splits):
         got = decode_paged(tq, kp, vp, table, tl, causal=True, return_lse=True, num_splits=splits,
                            k_scale=ks, v_scale=vs)
         assert bool(torch.isfinite(got[0]).all())
-        assert _same(got, want)
+        assert dr.same(got, want)
 
 
 @pytest.mark.parametrize("splits", [1, 3])
@@ -329,7 +268,7 @@ def test_out_of_range_page_ids_read_as_zero_rows(splits):
     lens = (200, 320, 129)
     _, _, (tq, k8, v8) = _case8(3, 8, 2, 1, 320, 128, lens, torch.float16)
     ks, vs = _scale_t(K_SCALE), _scale_t(V_SCALE)
-    tl = _lens(lens)
+    tl = dr.lens(lens)
     kp0, vp0, table = _paginate8(k8, v8, 64, lens, seed=6)
     n = kp0.shape[0]
     zero_page = sorted(set(range(n)) - set(table.flatten().tolist()) - {0})[0]
@@ -351,7 +290,7 @@ def test_out_of_range_page_ids_read_as_zero_rows(splits):
     got = decode_paged(tq, kp, vp, bad, tl, causal=True, return_lse=True, num_splits=splits,
                        k_scale=ks, v_scale=vs)
     assert bool(torch.isfinite(got[0]).all()) and bool(torch.isfinite(got[1]).all())
-    assert _same(got, want)
+    assert dr.same(got, want)
     # all five tiles of element 1 are zero rows: O = 0, LSE = log(320)
     assert int(torch.count_nonzero(got[0][1]).item()) == 0
     assert float((got[1][1] - float(np.log(320.0))).abs().max()) <= 1e-5
@@ -365,7 +304,7 @@ def test_torch_ops_match_python_entries():
     lens = np.array([300, 640])
     _, _, (tq, k8, v8) = _case8(2, 8, 2, 3, 640, 128, lens, torch.bfloat16)
     ks, vs = _scale_t(K_SCALE), _scale_t(V_SCALE)
-    tl = _lens(lens)
+    tl = dr.lens(lens)
     kp, vp, table = _paginate8(k8, v8, 128, lens, seed=2)
     for causal in (True, False):
         want = decode(tq, k8, v8, tl, causal=causal, k_scale=ks, v_scale=vs)
@@ -385,9 +324,9 @@ def test_wrapper_rejects_host_scales():
     lens = np.array([64])
     _, _, (tq, k8, v8) = _case8(1, 2, 2, 1, 64, 64, lens, torch.float16)
     with pytest.raises(fa_mi355x.FlashAttentionError, match="k_scale must be a tensor on"):
-        decode(tq, k8, v8, _lens(lens), k_scale=torch.ones(2))
+        decode(tq, k8, v8, dr.lens(lens), k_scale=torch.ones(2))
     with pytest.raises(fa_mi355x.FlashAttentionError, match="go with a torch.float8_e4m3fn cache only"):
-        decode(tq, k8.to(torch.float16), v8.to(torch.float16), _lens(lens), k_scale=_scale_t((1.0, 1.0)))
+        decode(tq, k8.to(torch.float16), v8.to(torch.float16), dr.lens(lens), k_scale=_scale_t((1.0, 1.0)))
 
 
 def test_op_in_hip_graph_follows_lengths_and_scales():
@@ -398,7 +337,7 @@ def test_op_in_hip_graph_follows_lengths_and_scales():
 
     op = torch.ops.fa_mi355x.decode
     _, _, (tq, k8, v8) = _case8(1, 8, 2, 1, 2048, 128, np.array([2048]), torch.float16)
-    lens = _lens([2048])
+    lens = dr.lens([2048])
     ks, vs = _scale_t(K_SCALE), _scale_t(V_SCALE)
     settings = [(700, (2.0 ** -5, 2.0 ** -7), (0.75, 2.0 ** -3)), (1333, (0.011, 2.0 ** -4), (2.0 ** -6, 1.5))]
     wants = []
@@ -431,7 +370,7 @@ def test_non_default_stream():
     lens = np.array(MATRIX_LENS)
     _, _, (tq, k8, v8) = _case8(b, hkv * g, hkv, sq, cap, d, lens, torch.float16)
     ks, vs = _scale_t(K_SCALE), _scale_t(V_SCALE)
-    tl = _lens(lens)
+    tl = dr.lens(lens)
     want = decode(tq, k8, v8, tl, causal=True, return_lse=True, num_splits=3, k_scale=ks, v_scale=vs)
     s = torch.cuda.Stream()
     assert s.cuda_stream != torch.cuda.current_stream().cuda_stream
@@ -440,25 +379,25 @@ def test_non_default_stream():
     got = decode(tq, k8, v8, tl, causal=True, out=out, return_lse=True, num_splits=3, stream=s,
                  k_scale=ks, v_scale=vs)
     s.synchronize()
-    assert got[0] is out and _same(got, want)
+    assert got[0] is out and dr.same(got, want)
     with torch.cuda.stream(s):
-        assert _ws_counters_zero()
+        assert dr.ws_counters_zero()
 
 
 # ---- 8. informational: what the quantisation itself costs on this data --------------
 
-@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("dtype", dr.DTYPES)
 def test_report_quantisation_error(dtype):
     """Printed, not gated: kv8 output against the 16-bit entry on the
     UNQUANTISED cache at len 640 (the error of E4M3's 3-bit mantissa on the
     oracle generator's data, not the kernel's)."""
     b, hkv, g, sq, cap, d = 1, 2, 4, 1, 640, 128
     lens = np.array([640])
-    q, k, v = _inputs(b, hkv * g, hkv, sq, cap, d)
+    q, k, v = dr.inputs(b, hkv * g, hkv, sq, cap, d)
     _, _, (tq, k8, v8) = _case8(b, hkv * g, hkv, sq, cap, d, lens, dtype)
-    ref = decode(tq, _dev(k).to(dtype), _dev(v).to(dtype), _lens(lens), causal=True)
-    got = decode(tq, k8, v8, _lens(lens), causal=True, k_scale=_scale_t(K_SCALE), v_scale=_scale_t(V_SCALE))
+    ref = decode(tq, dr.dev(k).to(dtype), dr.dev(v).to(dtype), dr.lens(lens), causal=True)
+    got = decode(tq, k8, v8, dr.lens(lens), causal=True, k_scale=_scale_t(K_SCALE), v_scale=_scale_t(V_SCALE))
     err = float((got.float() - ref.float()).abs().max())
-    print(f"kv8 vs 16-bit cache, {_name(dtype)} d={d} len=640: max_abs_diff {err:.3e} "
+    print(f"kv8 vs 16-bit cache, {dr.name(dtype)} d={d} len=640: max_abs_diff {err:.3e} "
           f"(max |O| {float(ref.float().abs().max()):.3e})")
     assert bool(torch.isfinite(got).all())

@@ -2,8 +2,8 @@
 reference that is not this kernel (fa_decode_* and fa_decode_paged_*:
 T in {fp16, bf16} x HDIM in {64, 128} x NB in {1, 2, 4} x {contiguous, paged}).
 
-Helpers, references and gates are those of tests/test_decode_gpu.py and
-tests/test_decode_paged_gpu.py (loaded by file path); no new tolerance:
+Helpers, references and gates are those of tests/decode_refs.py; no new
+tolerance:
   * fp16 O: the CPU oracle, 1e-3.
   * bf16 O: fp32 torch on the same bf16 inputs, 5e-3.
   * LSE: float64 reference, 2^-10 * max|scaled score| + 1e-5.
@@ -46,90 +46,35 @@ cannot see (test_rows_unseen_by_pieces), the kv_lens clamp of both entries
 (test_kv_lens_clamp_*), stores outside O, LSE and the promised workspace
 (test_no_write_outside_*) and a non-default stream (test_non_default_stream).
 """
-import importlib.util
-import os
-
 import numpy as np
 import pytest
 import torch
 
+import decode_refs as dr
 import fa_mi355x
 
 pytestmark = pytest.mark.gpu
 
-
-def _load(name, fname):
-    spec = importlib.util.spec_from_file_location(
-        name, os.path.join(os.path.dirname(os.path.abspath(__file__)), fname))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-_h = _load("_decode_gpu_helpers", "test_decode_gpu.py")
-_p = _load("_decode_paged_gpu_helpers", "test_decode_paged_gpu.py")
-_inputs, _oracle_decode, _lse_ref, _check_lse, _check_f16, _ref_torch = (
-    _h._inputs, _h._oracle_decode, _h._lse_ref, _h._check_lse, _h._check_f16, _h._ref_torch)
-_dev, _lens, _bits, _ws_counters_zero = _h._dev, _h._lens, _h._bits, _h._ws_counters_zero
-_paginate, _gather, _nan_fill = _p._paginate, _p._gather, _p._nan_fill
-
 DEV = "cuda"
-GATE_BF16 = _h.GATE_BF16
 K_PAD, V_PAD = 0x7fff, -1   # int16 bit patterns (0x7fff, 0xffff): NaN in fp16 and in bf16
 O_SENTINEL = 0x7fff         # 16-bit guard pattern around O
 LSE_SENTINEL = 0x7fa5a5a5   # 32-bit guard pattern around LSE (a NaN: never a result)
 GUARD = 64                  # guard rows of O / guard floats of LSE on either side
 WS_GUARD = 4096             # bytes of 0xA5 behind the promised workspace
 
-DTYPES = [pytest.param(torch.float16, id="fp16"), pytest.param(torch.bfloat16, id="bf16")]
-
 decode = fa_mi355x.flash_attention_decode
 decode_paged = fa_mi355x.flash_attention_decode_paged
-
-
-def _nb(g, sq):
-    return 1 if g * sq <= 16 else (2 if g * sq <= 32 else 4)
-
-
-def _name(dtype):
-    return "fp16" if dtype is torch.float16 else "bf16"
 
 
 def _case(b, hq, hkv, sq, cap, d, lens, dtype):
     """The oracle generator's inputs as (numpy fp16 bits, device tensors of
     `dtype`); the device caches' rows past each length hold NaN bit patterns."""
-    q, k, v = _inputs(b, hq, hkv, sq, cap, d)
-    tq, tk, tv = (_dev(a).to(dtype) for a in (q, k, v))
+    q, k, v = dr.inputs(b, hq, hkv, sq, cap, d)
+    tq, tk, tv = (dr.dev(a).to(dtype) for a in (q, k, v))
     for i, n in enumerate(lens):
         tk[i, :, int(n):].view(torch.int16).fill_(K_PAD)
         tv[i, :, int(n):].view(torch.int16).fill_(V_PAD)
     return (q, k, v), (tq, tk, tv)
-
-
-def _refs(host, dev, lens, causal, dtype):
-    """(O reference, float64 LSE, max |scaled score|): fp16 from the CPU oracle,
-    bf16 from fp32 torch on the bf16 inputs."""
-    if dtype is torch.float16:
-        ro = _oracle_decode(*host, lens, causal)
-        lref, smax = _lse_ref(host[0], host[1], host[2], lens, causal)
-    else:
-        ro = _ref_torch(*dev, _lens(lens), causal)[0]
-        lref, smax = _lse_ref(dev[0], dev[1], dev[2], lens, causal)
-    return ro, lref, smax
-
-
-def _check(out, lse, refs, dtype, what):
-    ro, lref, smax = refs
-    assert bool(torch.isfinite(out).all()), what
-    if dtype is torch.float16:
-        _check_f16(out, ro, what)
-    else:
-        err = float((out.float() - ro).abs().max())
-        print(f"{what}: max_abs_diff {err:.3e}")
-        assert err <= GATE_BF16, (what, err)
-    _check_lse(lse, lref, smax, what)
-    unseen = torch.from_numpy(np.isneginf(lref)).to(out.device)
-    assert int(torch.count_nonzero(out[unseen]).item()) == 0, what
 
 
 # ---- 1. every variant, split and unsplit --------------------------------------------
@@ -139,7 +84,7 @@ MATRIX_LENS = (70, 300, 640)
 
 @pytest.mark.parametrize("g,sq", [(5, 1), (7, 3), (4, 16), (16, 5)])
 @pytest.mark.parametrize("d", [128, 64])
-@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("dtype", dr.DTYPES)
 def test_variant_split_matrix(dtype, d, g, sq):
     """5 / 21 / 64 / 80 rows per K/V head (NB = 1 / 2 / 4 / 4 with a second row
     group).  70 keys are 2 tiles (7 pieces: five are empty; Sq = 16 causal: rows
@@ -148,23 +93,23 @@ def test_variant_split_matrix(dtype, d, g, sq):
     b, hkv, cap = 3, 2, 640
     lens = np.array(MATRIX_LENS)
     host, dev = _case(b, hkv * g, hkv, sq, cap, d, lens, dtype)
-    tl = _lens(lens)
-    tag = f"{_name(dtype)} d={d} NB={_nb(g, sq)} G={g} Sq={sq}"
+    tl = dr.lens(lens)
+    tag = f"{dr.name(dtype)} d={d} NB={dr.nb(g, sq)} G={g} Sq={sq}"
     refs = {}
     for causal in (True, False):
-        refs[causal] = _refs(host, dev, lens, causal, dtype)
+        refs[causal] = dr.refs(host, dev, lens, causal, dtype)
         for ns in (1, 2, 3, 7):
             out, lse = decode(*dev, tl, causal=causal, return_lse=True, num_splits=ns)
-            _check(out, lse, refs[causal], dtype, f"contig {tag} causal={causal} ns={ns}")
+            dr.check(out, lse, refs[causal], dtype, f"contig {tag} causal={causal} ns={ns}")
             if ns > 1:
-                assert _ws_counters_zero(), (tag, causal, ns)
-    kp, vp, table = _paginate(dev[1], dev[2], 128, lens)
+                assert dr.ws_counters_zero(), (tag, causal, ns)
+    kp, vp, table = dr.paginate(dev[1], dev[2], 128, lens)
     for ns in (1, 3):
         out, lse = decode_paged(dev[0], kp, vp, table, tl, causal=True, return_lse=True,
                                 num_splits=ns)
-        _check(out, lse, refs[True], dtype, f"paged {tag} causal=True ns={ns}")
+        dr.check(out, lse, refs[True], dtype, f"paged {tag} causal=True ns={ns}")
         if ns > 1:
-            assert _ws_counters_zero(), (tag, "paged", ns)
+            assert dr.ws_counters_zero(), (tag, "paged", ns)
 
 
 # ---- 2. rows that no piece, or only some pieces, can see ----------------------------
@@ -179,17 +124,17 @@ UNSEEN = [
 
 
 @pytest.mark.parametrize("sq,n", UNSEEN)
-@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("dtype", dr.DTYPES)
 def test_rows_unseen_by_pieces(dtype, sq, n):
     lens = np.array([n])
     host, dev = _case(1, 2, 1, sq, 192, 128, lens, dtype)
-    refs = _refs(host, dev, lens, True, dtype)
+    refs = dr.refs(host, dev, lens, True, dtype)
     if (sq, n) == (5, 3):
         assert np.isneginf(refs[1][:, :, :2]).all() and np.isfinite(refs[1][:, :, 2:]).all()
     for ns in (2, 3):
-        out, lse = decode(*dev, _lens(lens), causal=True, return_lse=True, num_splits=ns)
-        _check(out, lse, refs, dtype, f"unseen {_name(dtype)} Sq={sq} len={n} ns={ns}")
-        assert _ws_counters_zero(), (sq, n, ns)
+        out, lse = decode(*dev, dr.lens(lens), causal=True, return_lse=True, num_splits=ns)
+        dr.check(out, lse, refs, dtype, f"unseen {dr.name(dtype)} Sq={sq} len={n} ns={ns}")
+        assert dr.ws_counters_zero(), (sq, n, ns)
 
 
 # ---- 3. the kv_lens clamp -----------------------------------------------------------
@@ -200,21 +145,21 @@ def test_kv_lens_clamp_contiguous(ns):
     caches are the middle elements of a larger allocation whose outer elements
     are NaN: an unclamped length reads the next head or NaN, nothing else."""
     b, hq, hkv, sq, cap, d = 4, 8, 2, 2, 192, 128
-    q, k, v = _inputs(b, hq, hkv, sq, cap, d)
-    tq = _dev(q)
-    bigk = _nan_fill(torch.empty((b + 2, hkv, cap, d), dtype=torch.float16, device=DEV))
-    bigv = _nan_fill(torch.empty_like(bigk))
+    q, k, v = dr.inputs(b, hq, hkv, sq, cap, d)
+    tq = dr.dev(q)
+    bigk = dr.nan_fill(torch.empty((b + 2, hkv, cap, d), dtype=torch.float16, device=DEV))
+    bigv = dr.nan_fill(torch.empty_like(bigk))
     tk, tv = bigk[1:1 + b], bigv[1:1 + b]
-    tk.copy_(_dev(k))
-    tv.copy_(_dev(v))
+    tk.copy_(dr.dev(k))
+    tv.copy_(dr.dev(v))
     assert tk.is_contiguous() and tv.is_contiguous()
     clamped = np.array([0, 0, 192, 192])
-    want = decode(tq, tk, tv, _lens(clamped), causal=True, return_lse=True, num_splits=ns)
-    got = decode(tq, tk, tv, _lens([-1, -64, 193, 256]), causal=True, return_lse=True,
+    want = decode(tq, tk, tv, dr.lens(clamped), causal=True, return_lse=True, num_splits=ns)
+    got = decode(tq, tk, tv, dr.lens([-1, -64, 193, 256]), causal=True, return_lse=True,
                  num_splits=ns)
     assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
-    refs = (_oracle_decode(q, k, v, clamped, True),) + _lse_ref(q, k, v, clamped, True)
-    _check(want[0], want[1], refs, torch.float16, f"clamp contig ns={ns}")
+    refs = (dr.oracle_decode(q, k, v, clamped, True),) + dr.lse_ref(q, k, v, clamped, True)
+    dr.check(want[0], want[1], refs, torch.float16, f"clamp contig ns={ns}")
 
 
 @pytest.mark.parametrize("ns", [1, 2])
@@ -223,23 +168,23 @@ def test_kv_lens_clamp_paged(ns):
     the middle rows of a larger one whose outer rows name NaN pages: an
     unclamped length reads the next row's first entry."""
     b, hq, hkv, sq, cap, d = 4, 8, 2, 2, 192, 128
-    q, k, v = _inputs(b, hq, hkv, sq, cap, d)
-    tq, tk, tv = _dev(q), _dev(k), _dev(v)
+    q, k, v = dr.inputs(b, hq, hkv, sq, cap, d)
+    tq, tk, tv = dr.dev(q), dr.dev(k), dr.dev(v)
     clamped = np.array([0, 192, 192, 192])
-    kp, vp, table = _paginate(tk, tv, 64, clamped, seed=21)
+    kp, vp, table = dr.paginate(tk, tv, 64, clamped, seed=21)
     free = sorted(set(range(kp.shape[0])) - set(table[1:].flatten().tolist()))
     assert len(free) >= 3 and bool(torch.isnan(kp[free[-3:]]).all())  # pages no sequence uses
     big = torch.tensor([free[-3:]] * (b + 2), dtype=torch.int32, device=DEV)
     big[1:1 + b] = table
     tab = big[1:1 + b]
     assert tab.is_contiguous()
-    want = decode_paged(tq, kp, vp, tab, _lens(clamped), causal=True, return_lse=True,
+    want = decode_paged(tq, kp, vp, tab, dr.lens(clamped), causal=True, return_lse=True,
                         num_splits=ns)
-    got = decode_paged(tq, kp, vp, tab, _lens([-1, 193, 256, 192]), causal=True, return_lse=True,
+    got = decode_paged(tq, kp, vp, tab, dr.lens([-1, 193, 256, 192]), causal=True, return_lse=True,
                        num_splits=ns)
     assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
-    refs = (_oracle_decode(q, k, v, clamped, True),) + _lse_ref(q, k, v, clamped, True)
-    _check(want[0], want[1], refs, torch.float16, f"clamp paged ns={ns}")
+    refs = (dr.oracle_decode(q, k, v, clamped, True),) + dr.lse_ref(q, k, v, clamped, True)
+    dr.check(want[0], want[1], refs, torch.float16, f"clamp paged ns={ns}")
 
 
 # ---- 4. nothing is written outside O, LSE or the promised workspace -----------------
@@ -287,8 +232,8 @@ def test_no_write_outside_outputs_or_workspace(dtype, d, g, sq):
     hq = hkv * g
     lens = np.array([n] * b)
     _, (tq, tk, tv) = _case(b, hq, hkv, sq, cap, d, lens, dtype)
-    tl = _lens(lens)
-    kp, vp, table = _paginate(tk, tv, 64, lens, seed=31)
+    tl = dr.lens(lens)
+    kp, vp, table = dr.paginate(tk, tv, 64, lens, seed=31)
     lib = fa_mi355x.load_library()
     bf16 = dtype is torch.bfloat16
     st = torch.cuda.current_stream().cuda_stream
@@ -296,7 +241,7 @@ def test_no_write_outside_outputs_or_workspace(dtype, d, g, sq):
         need = lib.fa_decode_ws_bytes(b, hq, hkv, sq, cap, d, ns)
         assert (need == 0) == (ns == 1)
         for entry in ("contig", "paged"):
-            what = f"guards {entry} {_name(dtype)} d={d} G={g} Sq={sq} ns={ns}"
+            what = f"guards {entry} {dr.name(dtype)} d={d} G={g} Sq={sq} ns={ns}"
             if entry == "contig":
                 want = decode(tq, tk, tv, tl, causal=True, return_lse=True, num_splits=ns)
             else:
@@ -339,7 +284,7 @@ def test_non_default_stream():
     b, hkv, g, sq, cap, d = 3, 2, 7, 3, 640, 128
     lens = np.array(MATRIX_LENS)
     _, (tq, tk, tv) = _case(b, hkv * g, hkv, sq, cap, d, lens, torch.float16)
-    tl = _lens(lens)
+    tl = dr.lens(lens)
     want = decode(tq, tk, tv, tl, causal=True, return_lse=True, num_splits=3)
     s = torch.cuda.Stream()
     assert s.cuda_stream != torch.cuda.current_stream().cuda_stream
@@ -351,4 +296,4 @@ def test_non_default_stream():
     assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
     assert (torch.cuda.current_device(), s.cuda_stream) in fa_mi355x._WS_BUF
     with torch.cuda.stream(s):
-        assert _ws_counters_zero()
+        assert dr.ws_counters_zero()

@@ -4,103 +4,24 @@ torch.ops.fa_mi355x.decode_paged): exports, the argument checks (all returned
 before any launch, so fake pointers do), the Python wrapper's tensor checks,
 the op's registration and the kernels' compile-time resource usage -- no
 kernel is launched (no GPU here)."""
-import ctypes
 import os
-import re
-import subprocess
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import capi_checks
+from capi_checks import fa as _fa
+
 SYMBOLS = ("fa_decode_paged_f16", "fa_decode_paged_bf16")
-MAX_SPLITS = 64  # the plan's upper cap (csrc/fa_decode_host.hpp kDecodeMaxSplits)
-INT_MAX = 2 ** 31 - 1
-
-
-def _fa():
-    import fa_mi355x
-
-    return fa_mi355x
 
 
 def test_library_exports_paged_symbols():
-    fa = _fa()
-    out = subprocess.run(["nm", "-D", "--defined-only", fa.library_path()], capture_output=True,
-                         text=True, check=True).stdout
-    syms = {line.split()[-1] for line in out.splitlines() if line.strip()}
-    header = open(os.path.join(ROOT, "include", "fa_mi355x.h")).read()
-    for s in SYMBOLS:
-        assert s in syms, s
-        assert s in fa.EXPORTED_SYMBOLS, s
-        assert re.search(r"\b%s\s*\(" % s, header), s
-
-
-def _call(fn, q, k, v, o, b, hq, hkv, sq, d, npages, psz, table, mpp, lens=None, causal=1, ns=0,
-          ws=None, wsb=0):
-    return fn(q, k, v, o, None, b, hq, hkv, sq, d, npages, psz, table, mpp, lens, causal, ns, ws, wsb,
-              None)
+    capi_checks.assert_exported(SYMBOLS)
 
 
 def test_argument_checks():
     fa = _fa()
-    lib = fa.load_library()
-    p = ctypes.c_void_p(0x1000)
-    for fn in (lib.fa_decode_paged_f16, lib.fa_decode_paged_bf16):
-        # a good call's arguments: B=1 Hq=8 Hkv=2 Sq=1 D=128, 100 pages of 128 keys, 32 per sequence
-        for bad in range(4):  # each of q, k_pages, v_pages, o NULL in turn
-            ptrs = [None if i == bad else p for i in range(4)]
-            assert _call(fn, *ptrs, 1, 8, 2, 1, 128, 100, 128, p, 32) == fa.FA_ERR_NULL_POINTER
-        # a NULL table with a non-zero capacity
-        assert _call(fn, p, p, p, p, 1, 8, 2, 1, 128, 100, 128, None, 32) == fa.FA_ERR_NULL_POINTER
-        for psz in (0, 32, 96, -64, 1, 63, 65):
-            assert _call(fn, p, p, p, p, 1, 8, 2, 1, 128, 100, psz, p, 32) == fa.FA_ERR_BAD_SHAPE, psz
-        for npages in (0, -1):
-            assert _call(fn, p, p, p, p, 1, 8, 2, 1, 128, npages, 128, p, 32) == fa.FA_ERR_BAD_SHAPE
-        assert _call(fn, p, p, p, p, 1, 8, 2, 1, 128, 100, 128, p, -1) == fa.FA_ERR_BAD_SHAPE
-        # logical capacity past INT_MAX - 64 (the last one at or below it is accepted as a shape:
-        # it fails later, on the missing workspace of its split)
-        assert (INT_MAX - 64) // 64 * 64 == 2147483520
-        assert _call(fn, p, p, p, p, 1, 8, 2, 1, 128, 100, 64, p, 2147483520 // 64 + 1) == \
-            fa.FA_ERR_BAD_SHAPE
-        assert _call(fn, p, p, p, p, 1, 8, 2, 1, 128, 100, 64, p, 2147483520 // 64) == \
-            fa.FA_ERR_WORKSPACE
-        assert _call(fn, p, p, p, p, 1, 8, 2, 1, 128, 100, 1 << 20, p, 1 << 12) == fa.FA_ERR_BAD_SHAPE
-        # one page's rows of a head past a 32-bit byte range
-        assert _call(fn, p, p, p, p, 1, 8, 2, 1, 128, 1, 1 << 23, p, 1) == fa.FA_ERR_BAD_SHAPE
-        # the contiguous entry's checks
-        for d in (0, 32, 96, 256):
-            assert _call(fn, p, p, p, p, 1, 8, 2, 1, d, 100, 128, p, 32) == \
-                fa.FA_ERR_UNSUPPORTED_HEAD_DIM
-        for hq, hkv in ((8, 3), (7, 2), (4, 8)):
-            assert _call(fn, p, p, p, p, 1, hq, hkv, 1, 128, 100, 128, p, 32) == fa.FA_ERR_BAD_SHAPE
-        for sq in (0, 17, -1):
-            assert _call(fn, p, p, p, p, 1, 8, 2, sq, 128, 100, 128, p, 32) == fa.FA_ERR_BAD_SHAPE
-        assert _call(fn, p, p, p, p, -1, 8, 2, 1, 128, 100, 128, p, 32) == fa.FA_ERR_BAD_SHAPE
-        assert _call(fn, p, p, p, p, 1, -8, 2, 1, 128, 100, 128, p, 32) == fa.FA_ERR_BAD_SHAPE
-        assert _call(fn, p, p, p, p, 1, 8, -2, 1, 128, 100, 128, p, 32) == fa.FA_ERR_BAD_SHAPE
-        assert _call(fn, p, p, p, p, 1, 8, 2, 1, 128, 100, 128, p, 32, ns=-1) == fa.FA_ERR_BAD_SHAPE
-        # splitting needs a workspace: present, long enough (fa_decode_ws_bytes with the
-        # logical capacity 32 * 128), 16-byte aligned
-        need = lib.fa_decode_ws_bytes(1, 8, 2, 1, 32 * 128, 128, 4)
-        assert need > 65536
-        assert _call(fn, p, p, p, p, 1, 8, 2, 1, 128, 100, 128, p, 32, ns=4) == fa.FA_ERR_WORKSPACE
-        assert _call(fn, p, p, p, p, 1, 8, 2, 1, 128, 100, 128, p, 32, ns=4, ws=p, wsb=need - 1) == \
-            fa.FA_ERR_WORKSPACE
-        assert _call(fn, p, p, p, p, 1, 8, 2, 1, 128, 100, 128, p, 32, ns=4,
-                     ws=ctypes.c_void_p(0x1008), wsb=need) == fa.FA_ERR_WORKSPACE
-        # the plan's own split (num_splits = 0) of this shape needs one too
-        assert lib.fa_decode_num_splits(1, 8, 2, 1, 32 * 128, 128) > 1
-        assert _call(fn, p, p, p, p, 1, 8, 2, 1, 128, 100, 128, p, 32) == fa.FA_ERR_WORKSPACE
-        # more pieces than the cap
-        assert _call(fn, p, p, p, p, 1, 8, 2, 1, 128, 100, 128, p, 32, ns=MAX_SPLITS + 1, ws=p,
-                     wsb=1 << 40) == fa.FA_ERR_BAD_CONFIG
-        # empty problems: nothing to do, nothing launched, no pointer looked at
-        assert _call(fn, None, None, None, None, 0, 8, 2, 1, 128, 100, 128, None, 32) == fa.FA_OK
-        assert _call(fn, None, None, None, None, 1, 0, 0, 1, 128, 100, 128, None, 32) == fa.FA_OK
-        # ... but the page geometry is still checked
-        assert _call(fn, None, None, None, None, 0, 8, 2, 1, 128, 100, 96, None, 32) == \
-            fa.FA_ERR_BAD_SHAPE
+    capi_checks.decode_paged_argument_checks(fa, fa.load_library())
 
 
 def _t(shape, dtype=torch.float16, device="meta"):
@@ -179,21 +100,14 @@ def test_decode_paged_op_registered_with_fake_impl():
                                          _t((2, 2, 64, 128)), _t((1, 1), torch.int32))
 
 
-@pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
+@pytest.mark.skipif(not os.path.exists(capi_checks.HIPCC), reason="needs hipcc")
 def test_no_paged_decode_kernel_uses_scratch():
     """Twin of test_decode_cpu.test_no_decode_kernel_uses_scratch for
     csrc/fa_decode_paged.hip: every paged decode kernel (2 dtypes x 2 head
     dims x 1 / 2 / 4 row blocks) keeps its state in registers."""
-    pkg = os.path.join(ROOT, "flash-attention-cuda_amd")
-    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-honor-nans",
-           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(pkg, "csrc"), "-c",
-           os.path.join(pkg, "csrc", "fa_decode_paged.hip"), "-o", os.devnull,
-           "-Rpass-analysis=kernel-resource-usage"]
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    names = re.findall(r"Function Name: (\S+)", out.stderr)
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", out.stderr)]
-    assert len(names) == 12 and len(names) == len(scratch), (len(names), len(scratch))
+    (kernels,) = capi_checks.kernel_resource_usage(["fa_decode_paged.hip"])
+    names = [n for n, _, _ in kernels]
+    assert len(names) == 12, len(names)
     assert all("fa_decode_kernel" in n and "DecodePagedParams" in n for n in names), names
-    spills = {n: s for n, s in zip(names, scratch) if s}
+    spills = {n: s for n, s, _ in kernels if s}
     assert not spills, spills

@@ -8,111 +8,42 @@ num_splits the paged entry's O and LSE equal (torch.equal) those of the
 contiguous entry (fa_mi355x.flash_attention_decode) on the cache gathered from
 the pool through the table.  Correctness does not rest on the contiguous
 kernel alone: an independent reference is checked at the project's gates
-(helpers and gates of tests/test_decode_gpu.py: fp16 vs the CPU oracle 1e-3,
+(helpers and gates of tests/decode_refs.py: fp16 vs the CPU oracle 1e-3,
 bf16 vs fp32 torch 5e-3, LSE 2^-10 max|score| + 1e-5).
 
-Pools are built by _paginate(): a contiguous cache cut into pages, scattered
-under a seeded random permutation that interleaves the batch elements' pages
-into a pool larger than needed; pages no sequence uses, and the rows past each
-length inside the last used page, hold a NaN bit pattern.
+Pools are built by decode_refs.paginate(): a contiguous cache cut into pages,
+scattered under a seeded random permutation that interleaves the batch
+elements' pages into a pool larger than needed; pages no sequence uses, and the
+rows past each length inside the last used page, hold a NaN bit pattern.
 """
-import importlib.util
-import os
-
 import numpy as np
 import pytest
 import torch
 
+import decode_refs as dr
 import fa_mi355x
 
 pytestmark = pytest.mark.gpu
 
-_spec = importlib.util.spec_from_file_location(
-    "_decode_gpu_helpers", os.path.join(os.path.dirname(os.path.abspath(__file__)), "test_decode_gpu.py"))
-_h = importlib.util.module_from_spec(_spec)
-_spec.loader.exec_module(_h)
-_inputs, _oracle_decode, _lse_ref, _check_lse, _ref_torch = (
-    _h._inputs, _h._oracle_decode, _h._lse_ref, _h._check_lse, _h._ref_torch)
-_dev, _lens, _check_f16, _ws_counters_zero = _h._dev, _h._lens, _h._check_f16, _h._ws_counters_zero
-
 DEV = "cuda"
-GATE_F16 = 1e-3
-GATE_BF16 = 5e-3
-NAN_BITS = 0x7fff  # a NaN in fp16 and in bf16
 
 paged = fa_mi355x.flash_attention_decode_paged
 contig = fa_mi355x.flash_attention_decode
 
 
-def _nan_fill(t):
-    t.view(torch.int16).fill_(NAN_BITS)
-    return t
-
-
-def _paginate(k, v, page_size, lens, seed=0, spare=5, filler=0):
-    """(k_pages, v_pages, table) from contiguous [B][Hkv][cap][D] device caches
-    with cap % page_size == 0.  Element b's pages that hold a key below
-    lens[b] go to pool pages drawn from a seeded permutation of
-    range(num_pages), the elements' pages interleaved; num_pages = used +
-    spare.  Everything else in the pool is NaN, the rows past each length in
-    the last used page included.  Table entries past the used ones are
-    `filler` (an int, or "junk" for arbitrary ids, out-of-pool ones among
-    them)."""
-    b, hkv, cap, d = k.shape
-    assert cap % page_size == 0
-    mpp = cap // page_size
-    used = [-(-int(n) // page_size) for n in lens]
-    slots = sorted((j, bi) for bi in range(b) for j in range(used[bi]))  # interleaved
-    num_pages = len(slots) + spare
-    perm = np.random.default_rng(seed).permutation(num_pages)
-    kp = _nan_fill(torch.empty((num_pages, hkv, page_size, d), dtype=k.dtype, device=k.device))
-    vp = _nan_fill(torch.empty_like(kp))
-    if filler == "junk":
-        table = np.random.default_rng(seed + 1).integers(-3, num_pages + 3, size=(b, mpp))
-        table[:, -1:] = np.array([2 ** 31 - 1])[None, :]
-    else:
-        table = np.full((b, mpp), filler, dtype=np.int64)
-    for i, (j, bi) in enumerate(slots):
-        pg = int(perm[i])
-        table[bi, j] = pg
-        live = min(page_size, int(lens[bi]) - j * page_size)
-        kp[pg, :, :live] = k[bi, :, j * page_size:j * page_size + live]
-        vp[pg, :, :live] = v[bi, :, j * page_size:j * page_size + live]
-    return kp, vp, torch.tensor(table, dtype=torch.int32, device=k.device)
-
-
-def _gather(pages, table):
-    """The contiguous [B][Hkv][max_pages * page_size][D] cache the table describes
-    (entries outside the pool read page 0: they lie past every length)."""
-    n, hkv, ps, d = pages.shape
-    t = table.long()
-    t = torch.where((t >= 0) & (t < n), t, torch.zeros_like(t))
-    return pages[t].permute(0, 2, 1, 3, 4).reshape(table.shape[0], hkv, table.shape[1] * ps, d).contiguous()
-
-
-def _rand(shape, dtype, seed):
-    gen = torch.Generator(device=DEV).manual_seed(seed)
-    return (torch.rand(shape, generator=gen, device=DEV, dtype=torch.float32) * 2 - 1).to(dtype)
-
-
-def _same(a, b):
-    """Bit-equal outputs and LSEs (LSE -inf == -inf; no NaN is expected in either)."""
-    return torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
-
-
 def _identity_case(b, hq, hkv, sq, d, dtype, page_size, lens, mpp, splits=(1, 3, 0), seed=3):
     cap = mpp * page_size
-    q = _rand((b, hq, sq, d), dtype, seed)
-    k = _rand((b, hkv, cap, d), dtype, seed + 1)
-    v = _rand((b, hkv, cap, d), dtype, seed + 2)
-    kp, vp, table = _paginate(k, v, page_size, lens, seed=seed)
-    kg, vg = _gather(kp, table), _gather(vp, table)
-    tl = _lens(lens)
+    q = dr.rand((b, hq, sq, d), dtype, seed)
+    k = dr.rand((b, hkv, cap, d), dtype, seed + 1)
+    v = dr.rand((b, hkv, cap, d), dtype, seed + 2)
+    kp, vp, table = dr.paginate(k, v, page_size, lens, seed=seed)
+    kg, vg = dr.gather(kp, table), dr.gather(vp, table)
+    tl = dr.lens(lens)
     for ns in splits:
         got = paged(q, kp, vp, table, tl, causal=True, return_lse=True, num_splits=ns)
         want = contig(q, kg, vg, tl, causal=True, return_lse=True, num_splits=ns)
         assert torch.isfinite(got[0]).all(), (lens, ns)
-        assert _same(got, want), (b, hq, hkv, sq, d, dtype, page_size, tuple(lens), ns)
+        assert dr.same(got, want), (b, hq, hkv, sq, d, dtype, page_size, tuple(lens), ns)
 
 
 # ---- 1. bit-identity with the contiguous entry -------------------------------------
@@ -148,10 +79,10 @@ def _ref_f16(sq, causal):
     oracle's O / float64 LSE for lens (300, 1000); computed once, read-only."""
     key = (sq, causal)
     if key not in _REFS:
-        q, k, v = _inputs(2, 8, 2, sq, 1152, 128)
+        q, k, v = dr.inputs(2, 8, 2, sq, 1152, 128)
         lens = np.array([300, 1000])
-        _REFS[key] = (q, k, v, lens, _oracle_decode(q, k, v, lens, causal),
-                      _lse_ref(q, k, v, lens, causal))
+        _REFS[key] = (q, k, v, lens, dr.oracle_decode(q, k, v, lens, causal),
+                      dr.lse_ref(q, k, v, lens, causal))
     return _REFS[key]
 
 
@@ -160,39 +91,39 @@ def _ref_f16(sq, causal):
 @pytest.mark.parametrize("page_size", [64, 192])
 def test_against_references(page_size, causal, sq):
     q, k, v, lens, ref, (lref, smax) = _ref_f16(sq, causal)
-    tq, tk, tv, tl = _dev(q), _dev(k), _dev(v), _lens(lens)
-    kp, vp, table = _paginate(tk, tv, page_size, lens, seed=11)
+    tq, tk, tv, tl = dr.dev(q), dr.dev(k), dr.dev(v), dr.lens(lens)
+    kp, vp, table = dr.paginate(tk, tv, page_size, lens, seed=11)
     what = f"paged ps={page_size} causal={causal} Sq={sq}"
     out, lse = paged(tq, kp, vp, table, tl, causal=causal, return_lse=True)
-    _check_f16(out, ref, "fp16 " + what)
-    _check_lse(lse, lref, smax, "fp16 " + what)
+    dr.check_f16(out, ref, "fp16 " + what)
+    dr.check_lse(lse, lref, smax, "fp16 " + what)
     # bf16 against fp32 torch on the gathered cache
     bq, bk, bv = (t.to(torch.bfloat16) for t in (tq, tk, tv))
-    kp, vp, table = _paginate(bk, bv, page_size, lens, seed=12)
+    kp, vp, table = dr.paginate(bk, bv, page_size, lens, seed=12)
     out, lse = paged(bq, kp, vp, table, tl, causal=causal, return_lse=True)
-    ro, _ = _ref_torch(bq, _gather(kp, table), _gather(vp, table), tl, causal)
+    ro, _ = dr.ref_torch(bq, dr.gather(kp, table), dr.gather(vp, table), tl, causal)
     err = float((out.float() - ro).abs().max())
     print(f"bf16 {what}: {err:.3e}")
-    assert err <= GATE_BF16, (what, err)
-    bref, bsmax = _lse_ref(bq, bk, bv, lens, causal)
-    _check_lse(lse, bref, bsmax, "bf16 " + what)
+    assert err <= dr.GATE_BF16, (what, err)
+    bref, bsmax = dr.lse_ref(bq, bk, bv, lens, causal)
+    dr.check_lse(lse, bref, bsmax, "bf16 " + what)
 
 
 def test_one_key_and_unseen_rows():
-    q, k, v = _inputs(1, 8, 2, 5, 128, 128)
-    tq, tk, tv = _dev(q), _dev(k), _dev(v)
+    q, k, v = dr.inputs(1, 8, 2, 5, 128, 128)
+    tq, tk, tv = dr.dev(q), dr.dev(k), dr.dev(v)
     # one key: P = 1, O is that V row exactly
-    kp, vp, table = _paginate(tk, tv, 64, (1,), seed=1)
-    out = paged(tq[:, :, :1].contiguous(), kp, vp, table, _lens([1]), causal=True)
-    got = _h._bits(out)
+    kp, vp, table = dr.paginate(tk, tv, 64, (1,), seed=1)
+    out = paged(tq[:, :, :1].contiguous(), kp, vp, table, dr.lens([1]), causal=True)
+    got = dr.bits(out)
     for h in range(8):
         assert np.array_equal(got[0, h, 0], v[0, h // 4, 0]), h
     # three keys, five causal query tokens: the first two see no key
-    kp, vp, table = _paginate(tk, tv, 64, (3,), seed=2)
-    out, lse = paged(tq, kp, vp, table, _lens([3]), causal=True, return_lse=True)
+    kp, vp, table = dr.paginate(tk, tv, 64, (3,), seed=2)
+    out, lse = paged(tq, kp, vp, table, dr.lens([3]), causal=True, return_lse=True)
     assert int(torch.count_nonzero(out[:, :, :2])) == 0
     assert torch.isneginf(lse[:, :, :2]).all() and torch.isfinite(lse[:, :, 2:]).all()
-    _check_f16(out, _oracle_decode(q, k, v, np.array([3]), True), "three keys, Sq=5")
+    dr.check_f16(out, dr.oracle_decode(q, k, v, np.array([3]), True), "three keys, Sq=5")
 
 
 # ---- 3. padding and unused entries ------------------------------------------------
@@ -202,17 +133,17 @@ def test_nan_padding_and_junk_entries(splits):
     """Unused pages and the rows past each length are NaN; table entries past
     each length are arbitrary ids (out-of-pool ones among them): never read."""
     lens = (0, 129, 700, 1)
-    q = _rand((4, 8, 2, 128), torch.float16, 20)
-    k = _rand((4, 2, 768, 128), torch.float16, 21)
-    v = _rand((4, 2, 768, 128), torch.float16, 22)
-    tl = _lens(lens)
-    kp, vp, zeros = _paginate(k, v, 128, lens, seed=5, filler=0)
-    kp2, vp2, junk = _paginate(k, v, 128, lens, seed=5, filler="junk")
+    q = dr.rand((4, 8, 2, 128), torch.float16, 20)
+    k = dr.rand((4, 2, 768, 128), torch.float16, 21)
+    v = dr.rand((4, 2, 768, 128), torch.float16, 22)
+    tl = dr.lens(lens)
+    kp, vp, zeros = dr.paginate(k, v, 128, lens, seed=5, filler=0)
+    kp2, vp2, junk = dr.paginate(k, v, 128, lens, seed=5, filler="junk")
     assert torch.equal(kp.view(torch.int16), kp2.view(torch.int16)) and not torch.equal(zeros, junk)
     want = paged(q, kp, vp, zeros, tl, causal=True, return_lse=True, num_splits=splits)
     got = paged(q, kp, vp, junk, tl, causal=True, return_lse=True, num_splits=splits)
     assert torch.isfinite(got[0]).all()
-    assert _same(got, want)
+    assert dr.same(got, want)
 
 
 # ---- 4. out-of-range ids ----------------------------------------------------------
@@ -223,14 +154,14 @@ def test_out_of_range_page_ids(splits):
     is a slice of a larger NaN-filled allocation, two pages in from either end,
     so even a missing clamp reads only this test's memory -- and then NaN."""
     lens = (200, 300, 129)
-    q = _rand((3, 8, 1, 128), torch.float16, 30)
-    k = _rand((3, 2, 320, 128), torch.float16, 31)
-    v = _rand((3, 2, 320, 128), torch.float16, 32)
-    tl = _lens(lens)
-    kp0, vp0, table = _paginate(k, v, 64, lens, seed=6)
+    q = dr.rand((3, 8, 1, 128), torch.float16, 30)
+    k = dr.rand((3, 2, 320, 128), torch.float16, 31)
+    v = dr.rand((3, 2, 320, 128), torch.float16, 32)
+    tl = dr.lens(lens)
+    kp0, vp0, table = dr.paginate(k, v, 64, lens, seed=6)
     n = kp0.shape[0]
-    bigk = _nan_fill(torch.empty((n + 4,) + tuple(kp0.shape[1:]), dtype=kp0.dtype, device=DEV))
-    bigv = _nan_fill(torch.empty_like(bigk))
+    bigk = dr.nan_fill(torch.empty((n + 4,) + tuple(kp0.shape[1:]), dtype=kp0.dtype, device=DEV))
+    bigv = dr.nan_fill(torch.empty_like(bigk))
     kp, vp = bigk[2:2 + n], bigv[2:2 + n]
     kp.copy_(kp0)
     vp.copy_(vp0)
@@ -248,39 +179,39 @@ def test_out_of_range_page_ids(splits):
 # ---- 5. sharing and repeats -------------------------------------------------------
 
 def test_shared_and_repeated_pages():
-    q = _rand((2, 8, 2, 128), torch.float16, 40)
+    q = dr.rand((2, 8, 2, 128), torch.float16, 40)
     q[1] = q[0]
-    k = _rand((1, 2, 512, 128), torch.float16, 41)
-    v = _rand((1, 2, 512, 128), torch.float16, 42)
-    kp, vp, table = _paginate(k, v, 128, (500,), seed=7)
+    k = dr.rand((1, 2, 512, 128), torch.float16, 41)
+    v = dr.rand((1, 2, 512, 128), torch.float16, 42)
+    kp, vp, table = dr.paginate(k, v, 128, (500,), seed=7)
     # two elements naming the same pages, same length: equal outputs
     both = table.repeat(2, 1).contiguous()
-    out, lse = paged(q, kp, vp, both, _lens([500, 500]), causal=True, return_lse=True)
+    out, lse = paged(q, kp, vp, both, dr.lens([500, 500]), causal=True, return_lse=True)
     assert torch.equal(out[0], out[1]) and torch.equal(lse[0], lse[1])
-    one = paged(q[:1].contiguous(), kp, vp, table, _lens([500]), causal=True)
+    one = paged(q[:1].contiguous(), kp, vp, table, dr.lens([500]), causal=True)
     assert torch.equal(out[:1], one)
     # one page listed twice: the contiguous run on the cache with those rows repeated
     rep = table[:, [0, 1, 1, 2]].contiguous()
-    tl = _lens([512])
+    tl = dr.lens([512])
     got = paged(q[:1].contiguous(), kp, vp, rep, tl, causal=True, return_lse=True, num_splits=2)
-    want = contig(q[:1].contiguous(), _gather(kp, rep), _gather(vp, rep), tl, causal=True,
+    want = contig(q[:1].contiguous(), dr.gather(kp, rep), dr.gather(vp, rep), tl, causal=True,
                   return_lse=True, num_splits=2)
-    assert _same(got, want)
+    assert dr.same(got, want)
 
 
 # ---- 6. permutation invariance ----------------------------------------------------
 
 def test_placement_does_not_matter():
     lens = (700, 65, 384)
-    q = _rand((3, 8, 1, 64), torch.bfloat16, 50)
-    k = _rand((3, 2, 768, 64), torch.bfloat16, 51)
-    v = _rand((3, 2, 768, 64), torch.bfloat16, 52)
-    tl = _lens(lens)
-    a = _paginate(k, v, 192, lens, seed=8)
-    b = _paginate(k, v, 192, lens, seed=9, spare=11)
+    q = dr.rand((3, 8, 1, 64), torch.bfloat16, 50)
+    k = dr.rand((3, 2, 768, 64), torch.bfloat16, 51)
+    v = dr.rand((3, 2, 768, 64), torch.bfloat16, 52)
+    tl = dr.lens(lens)
+    a = dr.paginate(k, v, 192, lens, seed=8)
+    b = dr.paginate(k, v, 192, lens, seed=9, spare=11)
     assert not torch.equal(a[2], b[2])
     for ns in (0, 2):
-        assert _same(paged(q, *a, tl, causal=True, return_lse=True, num_splits=ns),
+        assert dr.same(paged(q, *a, tl, causal=True, return_lse=True, num_splits=ns),
                      paged(q, *b, tl, causal=True, return_lse=True, num_splits=ns))
 
 
@@ -296,45 +227,45 @@ def test_pool_past_4gib():
     except RuntimeError as e:  # torch.cuda.OutOfMemoryError is one
         pytest.skip(f"cannot allocate two pools of {npages * hkv * ps * d * 2 >> 20} MiB: {e}")
     n = 4 * ps - 3
-    q = _rand((1, hkv, 1, d), torch.float16, 60)
-    k = _rand((1, hkv, 4 * ps, d), torch.float16, 61)
-    v = _rand((1, hkv, 4 * ps, d), torch.float16, 62)
+    q = dr.rand((1, hkv, 1, d), torch.float16, 60)
+    k = dr.rand((1, hkv, 4 * ps, d), torch.float16, 61)
+    v = dr.rand((1, hkv, 4 * ps, d), torch.float16, 62)
     ids = [npages - 2, npages - 4, npages - 1, npages - 3]  # the top of the pool
     for j, pg in enumerate(ids):
         kp[pg] = k[0, :, j * ps:(j + 1) * ps]
         vp[pg] = v[0, :, j * ps:(j + 1) * ps]
     table = torch.tensor([ids], dtype=torch.int32, device=DEV)
-    tl = _lens([n])
+    tl = dr.lens([n])
     out = paged(q, kp, vp, table, tl, causal=True)
-    ro, _ = _ref_torch(q, k, v, tl, True)
+    ro, _ = dr.ref_torch(q, k, v, tl, True)
     err = float((out.float() - ro).abs().max())
     print(f"4 GiB pool: {err:.3e}")
     del kp, vp
     torch.cuda.empty_cache()
-    assert err <= GATE_F16
+    assert err <= dr.GATE_F16
 
 
 # ---- 8. workspace -----------------------------------------------------------------
 
 def test_forced_splits_workspace():
-    q, k, v = (_dev(a) for a in _inputs(1, 8, 2, 1, 1024, 128))
+    q, k, v = (dr.dev(a) for a in dr.inputs(1, 8, 2, 1, 1024, 128))
     lens = (1000,)
-    tl = _lens(lens)
-    kp, vp, table = _paginate(k, v, 64, lens, seed=13)
+    tl = dr.lens(lens)
+    kp, vp, table = dr.paginate(k, v, 64, lens, seed=13)
     dev = torch.cuda.current_device()
     st = torch.cuda.current_stream().cuda_stream
     for ns in (2, 7, 16):
         out = paged(q, kp, vp, table, tl, causal=True, num_splits=ns)
-        assert _ws_counters_zero(), ns
+        assert dr.ws_counters_zero(), ns
         assert torch.equal(out, contig(q, k, v, tl, causal=True, num_splits=ns)), ns
         again = paged(q, kp, vp, table, tl, causal=True, num_splits=ns)
         assert torch.equal(out, again), ns
-        assert _ws_counters_zero(), ns
+        assert dr.ws_counters_zero(), ns
         # poison the slabs: every slab the merge reads was written by this launch
         fa_mi355x._WS_BUF[(dev, st)][65536:].fill_(0xff)
         poisoned = paged(q, kp, vp, table, tl, causal=True, num_splits=ns)
         assert torch.equal(out, poisoned), ns
-        assert _ws_counters_zero(), ns
+        assert dr.ws_counters_zero(), ns
 
 
 def test_workspace_shared_with_forward_and_contiguous():
@@ -342,24 +273,24 @@ def test_workspace_shared_with_forward_and_contiguous():
     decode launches in any order."""
     import oracle
 
-    q, k, v = _inputs(1, 8, 2, 1, 1024, 128)
-    tq, tk, tv = _dev(q), _dev(k), _dev(v)
+    q, k, v = dr.inputs(1, 8, 2, 1, 1024, 128)
+    tq, tk, tv = dr.dev(q), dr.dev(k), dr.dev(v)
     lens = np.array([1000])
-    tl = _lens(lens)
-    ref = _oracle_decode(q, k, v, lens, True)
-    kp, vp, table = _paginate(tk, tv, 64, lens, seed=14)
+    tl = dr.lens(lens)
+    ref = dr.oracle_decode(q, k, v, lens, True)
+    kp, vp, table = dr.paginate(tk, tv, 64, lens, seed=14)
     fq, fk, fv = oracle.gen_inputs(1, 4, 8192, 128, 7)
     assert fa_mi355x.workspace_bytes(1, 4, 8192, 128, True) > 65536  # the split tier
     rows = np.array([0, 255, 4096, 8191])
     fref = oracle.attention_rows(fq[0, 3], fk[0, 3], fv[0, 3], rows, True)
 
     p1 = paged(tq, kp, vp, table, tl, causal=True, num_splits=4)
-    fo = fa_mi355x.flash_attention_fwd(_dev(fq), _dev(fk), _dev(fv), causal=True)
+    fo = fa_mi355x.flash_attention_fwd(dr.dev(fq), dr.dev(fk), dr.dev(fv), causal=True)
     c1 = contig(tq, tk, tv, tl, causal=True, num_splits=4)
     p2 = paged(tq, kp, vp, table, tl, causal=True, num_splits=4)
-    assert _ws_counters_zero()
-    _check_f16(p1, ref, "paged decode before forward")
-    _check_f16(fo[0, 3, rows], fref, "forward between decodes")
+    assert dr.ws_counters_zero()
+    dr.check_f16(p1, ref, "paged decode before forward")
+    dr.check_f16(fo[0, 3, rows], fref, "forward between decodes")
     assert torch.equal(p1, c1) and torch.equal(p1, p2)
 
 
@@ -368,14 +299,14 @@ def test_workspace_shared_with_forward_and_contiguous():
 def test_torch_op_matches_python_entry():
     import fa_mi355x.torch_op  # noqa: F401
 
-    q, k, v = (_dev(a) for a in _inputs(2, 8, 2, 2, 640, 128))
+    q, k, v = (dr.dev(a) for a in dr.inputs(2, 8, 2, 2, 640, 128))
     lens = (77, 600)
-    tl = _lens(lens)
-    kp, vp, table = _paginate(k, v, 128, lens, seed=15)
+    tl = dr.lens(lens)
+    kp, vp, table = dr.paginate(k, v, 128, lens, seed=15)
     want = paged(q, kp, vp, table, tl, causal=True)
     assert torch.equal(torch.ops.fa_mi355x.decode_paged(q, kp, vp, table, tl, True), want)
     # no kv_lens: every length is the table's capacity
-    kp2, vp2, table2 = _paginate(k, v, 128, (640, 640), seed=16)
+    kp2, vp2, table2 = dr.paginate(k, v, 128, (640, 640), seed=16)
     assert torch.equal(torch.ops.fa_mi355x.decode_paged(q, kp2, vp2, table2),
                        paged(q, kp2, vp2, table2))
 
@@ -392,8 +323,8 @@ def test_wrapper_rejections_on_device():
     and nothing is launched (an int64 table would otherwise be read as int32)."""
     import fa_mi355x.torch_op  # noqa: F401
 
-    q, k, v = (_dev(a) for a in _inputs(2, 8, 2, 1, 640, 128))
-    kp, vp, table = _paginate(k, v, 128, (600, 5), seed=17)
+    q, k, v = (dr.dev(a) for a in dr.inputs(2, 8, 2, 1, 640, 128))
+    kp, vp, table = dr.paginate(k, v, 128, (600, 5), seed=17)
     err = fa_mi355x.FlashAttentionError
     with pytest.raises(err, match="block_table must be a tensor on"):
         paged(q, kp, vp, table.cpu())
@@ -422,8 +353,8 @@ def test_op_in_hip_graph_follows_lengths_and_table():
     import fa_mi355x.torch_op  # noqa: F401
 
     op = torch.ops.fa_mi355x.decode_paged
-    q, k, v = (_dev(a) for a in _inputs(1, 8, 2, 1, 2048, 128))
-    kp, vp, table_a = _paginate(k, v, 128, (2048,), seed=18, spare=16)
+    q, k, v = (dr.dev(a) for a in dr.inputs(1, 8, 2, 1, 2048, 128))
+    kp, vp, table_a = dr.paginate(k, v, 128, (2048,), seed=18, spare=16)
     # the same pages once more, at the places the first placement left free
     free = sorted(set(range(kp.shape[0])) - set(table_a[0].tolist()))
     table_b = torch.tensor([free], dtype=torch.int32, device=DEV)
@@ -431,7 +362,7 @@ def test_op_in_hip_graph_follows_lengths_and_table():
     vp[table_b[0].long()] = vp[table_a[0].long()]
     assert not (set(table_a[0].tolist()) & set(table_b[0].tolist()))
     table = table_a.clone()
-    lens = _lens([2048])
+    lens = dr.lens([2048])
     for n in (2048, 700):  # eager references (and the first-launch set-up) outside the capture
         lens.fill_(n)
         op(q, kp, vp, table, lens, True)

@@ -20,14 +20,9 @@ import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
+from fwd_helpers import BOUNDARY, fa as _fa, ref_fp32_by_head as _ref  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-
-def _fa():
-    import fa_mi355x
-
-    return fa_mi355x
 
 
 def _random_shapes(n, seed):
@@ -43,42 +38,6 @@ def _random_shapes(n, seed):
         while b * h * s * s * d > 4e9 and s > 1:
             s //= 2
         out.append((b, h, s, d, causal, bf16))
-    return out
-
-
-# tier boundaries of the dispatcher (fa_fwd.hip select_tier / launch_auto):
-# config 1 and its ragged neighbours (W4P pairs), few-head long causal (W4P
-# pairs vs the workspace split tier), two rounds of pairs (quads), W4
-# persistent from two rounds of 256-row items, the S <= 256 loop, the KV-quad
-# under-filled non-causal case, the tail-pool shape class (>= 64 rounds per
-# XCD, a reduced copy), d64 twins
-BOUNDARY = [
-    (1, 32, 1024, 128, True, False), (1, 32, 1023, 128, True, False), (1, 32, 1025, 128, True, False),
-    (1, 32, 1024, 128, False, False), (1, 8, 4096, 128, True, False), (1, 4, 8192, 128, True, False),
-    (2, 32, 1024, 128, True, False), (1, 16, 4096, 128, True, False), (4, 32, 1024, 128, True, False),
-    (1, 32, 256, 128, True, False), (1, 32, 257, 128, False, False), (1, 32, 512, 128, False, False),
-    (1, 32, 512, 128, True, False), (3, 5, 77, 128, True, False), (1, 1, 1, 128, False, False),
-    (1, 32, 1024, 64, True, False), (1, 8, 4096, 64, True, False), (2, 16, 2048, 64, False, False),
-    (1, 32, 1024, 128, True, True), (1, 4, 8192, 128, True, True), (1, 32, 2048, 64, True, True),
-    # round 6: the singles / mixed edges (<= 1 block per CU; 1-2 per CU)
-    (1, 32, 513, 128, True, False), (1, 32, 576, 128, True, False), (1, 17, 1024, 128, True, False),
-    (1, 65, 256, 128, True, False), (1, 16, 1024, 64, False, False), (1, 16, 1088, 64, False, False),
-    (1, 32, 768, 64, True, True), (1, 4, 4096, 128, False, True),
-]
-
-
-def _ref(q, k, v, causal):
-    """fp32 attention of the 16-bit inputs"""
-    b, h, s, d = q.shape
-    qf = q.float()
-    out = torch.empty((b, h, s, d), dtype=torch.float32, device=q.device)
-    mask = torch.ones((s, s), dtype=torch.bool, device=q.device).tril() if causal else None
-    for bi in range(b):
-        for hi in range(h):
-            sc = (qf[bi, hi] @ k[bi, hi].float().t()) / math.sqrt(d)
-            if causal:
-                sc = sc.masked_fill(~mask, float("-inf"))
-            out[bi, hi] = torch.softmax(sc, dim=-1) @ v[bi, hi].float()
     return out
 
 

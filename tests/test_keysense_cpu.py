@@ -43,24 +43,14 @@ on 64 columns): there a whole tile read twice shows in the LSEs only.  Every
 forward shape of tests/test_keysense_gpu.py has ceil(S / 64) <= D, and the
 decode entries return the LSE.
 """
-import importlib.util
 import math
-import os
 
 import numpy as np
 import pytest
 import torch
 
+import keysense_inputs as ks
 
-def _load(name, fname):
-    spec = importlib.util.spec_from_file_location(
-        name, os.path.join(os.path.dirname(os.path.abspath(__file__)), fname))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-ks = _load("_keysense_inputs_cpu", "keysense_inputs.py")
 TILE = ks.TILE
 
 SHAPES = [(1000, 64), (1000, 128), (4160, 64), (4160, 128)]

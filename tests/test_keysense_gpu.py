@@ -10,8 +10,9 @@ Every forward tier and every decode variant runs them:
     S = 1000 (16 key tiles, a 40-key tail, the last query block mostly past S)
     and S = 2112 (33 tiles: an odd count for the two-tiles-per-barrier
     programs, more than one item per head);
-  * forward, dispatched: the BOUNDARY shapes of test_dispatch_sweep_gpu.py
-    with S >= 256 through flash_attention_fwd (workspace path: split tier,
+  * forward, dispatched: the BOUNDARY shapes of tests/fwd_helpers.py (those
+    of test_dispatch_sweep_gpu.py) with S >= 256 through
+    flash_attention_fwd (workspace path: split tier,
     pool eligibility) and the workspace-free C entry, and
     flash_attention_fwd_splitkv at num_splits 3 and 8 on (1, 8, 2112);
   * decode: the (G, Sq) x D x dtype matrix of test_decode_matrix_gpu.py at
@@ -35,41 +36,22 @@ and 6.8e-3 bf16, because its pieces store 16-bit normalised partials
 roundings stay inside the gate of twice the bound.  Needle: |O - V[pi]| = 0
 everywhere; LSE within 2.4e-6 (census within 1.0e-6).
 """
-import importlib.util
-import os
-
 import numpy as np
 import pytest
 import torch
 
+import decode_refs as dr
 import fa_mi355x
+import keysense_inputs as ks
+from fwd_helpers import BOUNDARY
 
 pytestmark = pytest.mark.gpu
-
-
-def _load(name, fname):
-    spec = importlib.util.spec_from_file_location(
-        name, os.path.join(os.path.dirname(os.path.abspath(__file__)), fname))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-ks = _load("_keysense_inputs_gpu", "keysense_inputs.py")
-_sweep = _load("_dispatch_sweep_gpu_keysense", "test_dispatch_sweep_gpu.py")
-_p = _load("_decode_paged_gpu_keysense", "test_decode_paged_gpu.py")
-_paginate = _p._paginate
 
 DEV = "cuda"
 FP8 = torch.float8_e4m3fn
 TILE = ks.TILE
-DTYPES = [pytest.param(torch.float16, id="fp16"), pytest.param(torch.bfloat16, id="bf16")]
 NAN16 = 0x7fff   # int16 bit pattern: NaN in fp16 and in bf16
 NAN8 = 0x7f      # the E4M3 NaN
-
-
-def _name(dtype):
-    return "fp16" if dtype is torch.float16 else "bf16"
 
 
 class _Report:
@@ -141,7 +123,7 @@ FORCED_S = (1000, 2112)
 @pytest.mark.parametrize("family", ["census", "needle"])
 @pytest.mark.parametrize("s", FORCED_S)
 @pytest.mark.parametrize("d", [128, 64])
-@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("dtype", dr.DTYPES)
 def test_forward_forced(dtype, d, s, family):
     """Every forceable tile config of this dtype and head_dim, with its own mask."""
     b, h = 2, 3
@@ -153,7 +135,7 @@ def test_forward_forced(dtype, d, s, family):
         runs = [(c.name, (lambda q, k, v, c=c: fa_mi355x.flash_attention_fwd(q, k, v, causal=c.causal,
                                                                             config=c.id)))
                 for c in cfgs if c.causal == causal]
-        tag = f"{_name(dtype)} d={d} S={s} causal={causal}"
+        tag = f"{dr.name(dtype)} d={d} S={s} causal={causal}"
         (_fwd_census if family == "census" else _fwd_needle)(rep, runs, b, h, s, d, causal, dtype, tag)
     rep.finish()
 
@@ -169,7 +151,7 @@ def _c_entry(q, k, v, causal):
     return o
 
 
-DISPATCHED = [sh for sh in _sweep.BOUNDARY if sh[2] >= 256]
+DISPATCHED = [sh for sh in BOUNDARY if sh[2] >= 256]
 
 
 @pytest.mark.parametrize("shape", DISPATCHED, ids=lambda sh: "x".join(map(str, sh)))
@@ -252,10 +234,10 @@ def _launchers(k, v, lens, cache, contig_ns, paged_ns, pages=(64, 128)):
         pcap = -(-cap // ps) * ps
         kg, vg = (_pad_rows(_grow(x, pcap), lens, pattern) for x in (kc, vc))
         if cache == "kv8":
-            kp, vp, table = _paginate(kg.view(torch.uint8), vg.view(torch.uint8), ps, lens, seed=ps)
+            kp, vp, table = dr.paginate(kg.view(torch.uint8), vg.view(torch.uint8), ps, lens, seed=ps)
             kp, vp = kp.view(FP8), vp.view(FP8)
         else:
-            kp, vp, table = _paginate(kg, vg, ps, lens, seed=ps)
+            kp, vp, table = dr.paginate(kg, vg, ps, lens, seed=ps)
         for ns in paged_ns:
             out.append((f"paged{ps} ns={ns}", True,
                         lambda q, kp=kp, vp=vp, table=table, ns=ns: fa_mi355x.flash_attention_decode_paged(
@@ -266,8 +248,8 @@ def _launchers(k, v, lens, cache, contig_ns, paged_ns, pages=(64, 128)):
 def _decode_case(rep, dtype, d, g, sq, cache, cap, lens, contig_ns, paged_ns, pages=(64, 128)):
     b, hkv = len(lens), 2
     hq = hkv * g
-    nb = 1 if g * sq <= 16 else (2 if g * sq <= 32 else 4)
-    base = f"decode {cache} {_name(dtype)} d={d} NB={nb}"
+    nb = dr.nb(g, sq)
+    base = f"decode {cache} {dr.name(dtype)} d={d} NB={nb}"
     tag = f"G={g} Sq={sq} cap={cap}"
 
     def tier(variant):
@@ -324,7 +306,7 @@ DECODE_LENS = (70, 1000, 4160)
 
 @pytest.mark.parametrize("g,sq", [(5, 1), (7, 3), (4, 16), (16, 5)])
 @pytest.mark.parametrize("d", [128, 64])
-@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("dtype", dr.DTYPES)
 @pytest.mark.parametrize("cache", ["kv16", "kv8"])
 def test_decode(cache, dtype, d, g, sq):
     """5 / 21 / 64 / 80 rows per K/V head over 2, 16 and 65 key tiles; rows past
@@ -335,7 +317,7 @@ def test_decode(cache, dtype, d, g, sq):
 
 
 @pytest.mark.parametrize("d", [128, 64])
-@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("dtype", dr.DTYPES)
 @pytest.mark.parametrize("cache", ["kv16", "kv8"])
 def test_decode_default_split(cache, dtype, d):
     """num_splits = 0 at the smallest capacity (in key tiles) that the plan cuts

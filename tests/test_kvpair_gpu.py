@@ -12,15 +12,10 @@ import pytest
 torch = pytest.importorskip("torch")
 
 import oracle  # noqa: E402  (test infrastructure)
+from fwd_helpers import bits as _bits, fa as _fa, to_dev as _dev  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-3
-
-
-def _fa():
-    import fa_mi355x
-
-    return fa_mi355x
 
 
 def _kvpair(causal, dtype="float16", head_dim=128, kind="kvpair"):
@@ -31,14 +26,6 @@ def _kvpair(causal, dtype="float16", head_dim=128, kind="kvpair"):
 # kvpair: two waves per 32 query rows (2-way key split, 128-row blocks);
 # kvquad: four waves per 32 rows (4-way split, 64-row blocks, 128-key stages)
 KINDS = ["kvpair", "kvquad"]
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.int16)).view(torch.float16).cuda()
-
-
-def _bits(t):
-    return t.detach().cpu().contiguous().view(torch.int16).numpy().view(np.uint16)
 
 
 def _check(b, h, s, causal, seed, qk_scale=1.0, kind="kvpair"):

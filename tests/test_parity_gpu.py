@@ -11,24 +11,11 @@ import pytest
 torch = pytest.importorskip("torch")
 
 import oracle  # noqa: E402  (test infrastructure)
+from fwd_helpers import fa as _fa, to_dev as _to_dev, to_host_bits as _to_host_bits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-3
-
-
-def _fa():
-    import fa_mi355x
-
-    return fa_mi355x
-
-
-def _to_dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.int16)).view(torch.float16).cuda()
-
-
-def _to_host_bits(t):
-    return t.detach().cpu().view(torch.int16).numpy().view(np.uint16)
 
 
 def _run(q, k, v, causal, config=None, splitkv=False, num_splits=0):

@@ -15,33 +15,15 @@ workspace checks.
 """
 import ctypes
 
-import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
 
 import oracle  # noqa: E402  (test infrastructure)
+from fwd_helpers import bits as _bits, fa as _fa, rand_cast as _rand  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-3
-
-
-def _fa():
-    import fa_mi355x
-
-    return fa_mi355x
-
-
-def _rand(shape, seed, scale=1.0, dtype=torch.float16):
-    g = torch.Generator(device="cuda")
-    g.manual_seed(seed)
-    t = torch.empty(shape, dtype=torch.float32, device="cuda")
-    t.uniform_(-0.5 * scale, 0.5 * scale, generator=g)
-    return t.to(dtype)
-
-
-def _bits(t):
-    return t.detach().cpu().contiguous().view(torch.int16).numpy().view(np.uint16)
 
 
 def _torch_ref(q, k, v):

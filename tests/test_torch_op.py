@@ -5,12 +5,12 @@ refuses CPU tensors (no CPU path).  GPU: it is the product kernel (bit-equal
 to the ctypes entry point), agrees with PyTorch SDPA and the oracle, works
 under torch.compile and inside a captured HIP graph.
 """
-import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
 
 import oracle  # noqa: E402  (test infrastructure)
+from fwd_helpers import bits as _bits, rand_half as _rand  # noqa: E402
 
 
 def _op():
@@ -43,16 +43,6 @@ def test_op_is_forward_only():
     with torch.no_grad():
         assert op(q, q, q, True).shape == q.shape
     assert op(q.detach(), q.detach(), q.detach(), False).shape == q.shape
-
-
-def _rand(shape, seed):
-    g = torch.Generator(device="cuda")
-    g.manual_seed(seed)
-    return torch.empty(shape, dtype=torch.float16, device="cuda").uniform_(-0.5, 0.5, generator=g)
-
-
-def _bits(t):
-    return t.detach().cpu().contiguous().view(torch.int16).numpy().view(np.uint16)
 
 
 @pytest.mark.gpu

@@ -18,27 +18,10 @@ import pytest
 torch = pytest.importorskip("torch")
 
 import oracle  # noqa: E402  (test infrastructure)
+from fwd_helpers import bits as _bits, fa as _fa, rand_half as _rand  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-3
-
-
-def _fa():
-    import fa_mi355x
-
-    return fa_mi355x
-
-
-def _rand(shape, seed, scale=1.0):
-    g = torch.Generator(device="cuda")
-    g.manual_seed(seed)
-    t = torch.empty(shape, dtype=torch.float16, device="cuda")
-    t.uniform_(-0.5 * scale, 0.5 * scale, generator=g)
-    return t
-
-
-def _bits(t):
-    return t.detach().cpu().contiguous().view(torch.int16).numpy().view(np.uint16)
 
 
 def _ids(prefix):

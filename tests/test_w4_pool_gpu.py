@@ -11,34 +11,16 @@ oracle as well.
 """
 import ctypes
 
-import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
 
 import oracle  # noqa: E402  (test infrastructure)
+from fwd_helpers import bits as _bits, fa as _fa, rand_cast as _rand  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-3
 CTR = 65536
-
-
-def _fa():
-    import fa_mi355x
-
-    return fa_mi355x
-
-
-def _rand(shape, seed, dtype=torch.float16):
-    g = torch.Generator(device="cuda")
-    g.manual_seed(seed)
-    t = torch.empty(shape, dtype=torch.float32, device="cuda")
-    t.uniform_(-0.5, 0.5, generator=g)
-    return t.to(dtype)
-
-
-def _bits(t):
-    return t.detach().cpu().contiguous().view(torch.int16).numpy().view(np.uint16)
 
 
 def _static(q, k, v, causal):
@@ -105,7 +87,7 @@ def test_pool_bf16_and_shape_change_on_one_workspace():
     ws = torch.zeros(CTR, dtype=torch.uint8, device="cuda")
     for (b, h, s, causal), dt in (((32, 32, 4096, True), torch.bfloat16), ((16, 32, 8192, False), torch.float16),
                                   ((128, 24, 2048, True), torch.bfloat16)):
-        q, k, v = (_rand((b, h, s, 128), 950 + i, dt) for i in range(3))
+        q, k, v = (_rand((b, h, s, 128), 950 + i, dtype=dt) for i in range(3))
         ref = _static(q, k, v, causal)
         out = _pooled(q, k, v, causal, ws)
         torch.cuda.synchronize()

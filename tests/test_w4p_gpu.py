@@ -19,6 +19,7 @@ import pytest
 torch = pytest.importorskip("torch")
 
 import oracle  # noqa: E402  (test infrastructure)
+from fwd_helpers import bits as _bits, fa as _fa, rand_cast as _rand, ref_fp32_by_head as _torch_ref  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-3
@@ -27,41 +28,9 @@ QUAD = "bm256_bn64_w4x64_m16_asm_quad"
 SINGLE = "bm64_bn64_w4x16_m16_asm_single"
 
 
-def _fa():
-    import fa_mi355x
-
-    return fa_mi355x
-
-
 def _ids(prefix):
     out = {c.causal: c.id for c in _fa().configs() if c.name in (f"{prefix}_noncausal", f"{prefix}_causal")}
     assert set(out) == {False, True}, prefix
-    return out
-
-
-def _rand(shape, seed, scale=1.0, dtype=torch.float16):
-    g = torch.Generator(device="cuda")
-    g.manual_seed(seed)
-    t = torch.empty(shape, dtype=torch.float32, device="cuda")
-    t.uniform_(-0.5 * scale, 0.5 * scale, generator=g)
-    return t.to(dtype)
-
-
-def _bits(t):
-    return t.detach().cpu().contiguous().view(torch.int16).numpy().view(np.uint16)
-
-
-def _torch_ref(q, k, v, causal):
-    """fp32 attention of the 16-bit inputs, head by head (bounded memory)"""
-    b, h, s, d = q.shape
-    out = torch.empty((b, h, s, d), dtype=torch.float32, device=q.device)
-    mask = torch.ones((s, s), dtype=torch.bool, device=q.device).tril() if causal else None
-    for bi in range(b):
-        for hi in range(h):
-            sc = (q[bi, hi].float() @ k[bi, hi].float().t()) / math.sqrt(d)
-            if causal:
-                sc = sc.masked_fill(~mask, float("-inf"))
-            out[bi, hi] = torch.softmax(sc, dim=-1) @ v[bi, hi].float()
     return out
 
 
