@@ -266,7 +266,13 @@ struct Elem {
   }
 };
 
-template <int BN_, class T = f16, int HDIM_ = 128, int QB_ = 2>
+// L32_ (the prefill kernel's bf16 instantiations, fa_prefill_kernel.hpp): the
+// row sums l are fp32 sums of the unrounded exponentials on the VALU (each
+// lane its 16 keys of a tile, the four lanes of a row added up in row_sum())
+// and the ones . P MFMAs are not issued: l then carries none of T's rounding
+// of P, which an LSE of a row with few keys would show.  The default keeps
+// the matrix-pipe sums; no other instantiation changes.
+template <int BN_, class T = f16, int HDIM_ = 128, int QB_ = 2, bool L32_ = false>
 struct M16 {
   static_assert(QB_ == 2, "two 16-row query blocks per wave (the merge layouts assume it)");
   static_assert(HDIM_ == 64 || HDIM_ == 128, "head_dim 64 or 128");
@@ -298,6 +304,7 @@ struct M16 {
   f32x4 negm[QB];     // C operand of the QK^T chains: -m_ref broadcast
   float m_ref[QB];    // reference max, log2 units (x = s*c - m_ref)
   f32x4 lacc[QB];     // running row sums l (ones . P on the matrix pipe, in the PV chain)
+  float l32[QB];      // L32_: this lane's share of l (fp32 exponentials)
   bool have_ref;     // wave-uniform: a tile has set m_ref
   float c;
 
@@ -322,6 +329,7 @@ struct M16 {
       negm[b] = f32x4{};
       m_ref[b] = 0.f;
       lacc[b] = f32x4{};
+      l32[b] = 0.f;
     }
     have_ref = false;
   }
@@ -433,9 +441,16 @@ struct M16 {
 #pragma unroll
     for (int b = 0; b < QB; ++b)
 #pragma unroll
-      for (int cb = 0; cb < NKB; ++cb)
+      for (int cb = 0; cb < NKB; ++cb) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) pf[b][cb >> 1][4 * (cb & 1) + i] = (T)__builtin_amdgcn_exp2f(s[b][cb][i]);
+        for (int i = 0; i < 4; ++i) {
+          const float ex = __builtin_amdgcn_exp2f(s[b][cb][i]);
+          pf[b][cb >> 1][4 * (cb & 1) + i] = (T)ex;
+          if constexpr (L32_) l32[b] += ex;
+        }
+        // 16 keys at a time: the exponentials die as they are summed (register pressure)
+        if constexpr (L32_) asm volatile("" : "+v"(l32[b]));
+      }
   }
   template <bool CAUSAL>
   __device__ __forceinline__ void softmax(int kv0, int kv_hi, int qw, float /*c*/, bool need_mask) {
@@ -490,6 +505,7 @@ struct M16 {
 #pragma unroll
           for (int e = 0; e < NE; ++e) acc[b][e] *= alpha;
           lacc[b] *= alpha;
+          if constexpr (L32_) l32[b] *= alpha;
         }
 #pragma unroll
         for (int cb = 0; cb < NKB; ++cb) s[b][cb] -= sh;
@@ -516,9 +532,11 @@ struct M16 {
           acc[b][e] = Elem<T>::mfma(vf, pf[b][u], acc[b][e]);
       }
       // row sums of the same fp16 P: every register of lacc[b] = l for q = lane&15
+      if constexpr (!L32_) {
 #pragma unroll
-      for (int b = 0; b < QB; ++b)
-        lacc[b] = Elem<T>::mfma(ones, pf[b][u], lacc[b]);
+        for (int b = 0; b < QB; ++b)
+          lacc[b] = Elem<T>::mfma(ones, pf[b][u], lacc[b]);
+      }
     }
   }
   // the ping-pong MFMA block: PV(V_{k-1}) then QK^T(K_k); the barrier keeps the
@@ -561,6 +579,7 @@ struct M16 {
   }
 
   __device__ __forceinline__ float row_sum(int b) const {
+    if constexpr (L32_) return sum_xor32(sum_xor16(l32[b]));
     return lacc[b][0];  // already the full row sum (MFMA over all keys)
   }
   // Epilogue: lane (g, r16) holds d = 16e + 4g + 0..3 of row r16 for every e.
@@ -571,12 +590,13 @@ struct M16 {
   // (dwordx4 instead of dwordx2) at the same bytes; the store tail is
   // issue-bound (guide T21).
   // row blocks [B0, B1), d-block pairs [EP0, EP1) (symmetric merges store a part each)
+  // osc: a factor on the normalisation (the FP8 cache's V scale, fa_prefill_kernel.hpp)
   template <int B0 = 0, int B1 = QB, int EP0 = 0, int EP1 = NE / 2>
-  __device__ __forceinline__ void store_o(__amdgpu_buffer_rsrc_t ro, int qw) {
+  __device__ __forceinline__ void store_o(__amdgpu_buffer_rsrc_t ro, int qw, float osc = 1.0f) {
 #pragma unroll
     for (int b = B0; b < B1; ++b) {
       const float lt = row_sum(b);  // already the full row sum (MFMA over all keys)
-      const float inv = lt > 0.f ? 1.0f / lt : 0.f;
+      const float inv = (lt > 0.f ? 1.0f / lt : 0.f) * osc;
       const int rowb = (qw + 16 * b + r16) * ROW;
       const int dlane = 16 * (g & 1) + 8 * (g >> 1);
 #pragma unroll

@@ -1,0 +1,305 @@
+// Prefill attention over a K/V cache for gfx950: any number of query tokens
+// per head (a prompt, or a chunk of one behind a cached prefix) against the
+// cache decode reads, with grouped K/V heads (GQA / MQA), per-element key and
+// query lengths read on the device, bottom-right causal alignment, and the
+// four cache forms (contiguous or paged, 16-bit or FP8 E4M3).
+//
+//   n_b   = q_lens ? clamp(q_lens[b], 0, Sq) : Sq      valid leading query tokens
+//   len_b = kv_lens ? clamp(kv_lens[b], 0, cap) : cap  keys, the chunk's own included
+//   off_b = len_b - n_b                                 keys that precede the chunk
+//   O[b,hq,t,:] = softmax(Q[b,hq,t,:] . K[b,hkv,0:vis,:]^T / sqrt(D)) V[b,hkv,0:vis,:],  t < n_b
+//   hkv = hq / (Hq / Hkv);  vis = causal ? clamp(off_b + t + 1, 0, len_b) : len_b
+//
+// Unlike decode, a key tile is reused by many query rows, so K and V go
+// through shared LDS: the kernel is the 4-wave tile loop of fa_fwd_kernel.hpp
+// (attention_tile_loop: 128 query rows per workgroup, 32 per wave, 64-key
+// tiles, register-staged double buffer, one barrier per tile) around the same
+// M16 policy (Q in registers, S^T = K . Q^T and O^T = V^T . P^T on
+// v_mfma_f32_16x16x32, image B for K, image A for V read with
+// ds_read_b64_tr_b16, exp2-domain softmax with lazy rescale).  What differs:
+//  * Workgroup = (batch element, query head, 128-row query block).  A block at
+//    or past n_b returns at once; its key range is [0, causal ? min(len_b,
+//    off_b + q0 + 128) : len_b).  The policy's mask compares a key with
+//    qw + row: it is given qw + off_b (non-causal: a row past every key), the
+//    Q loads and O stores the unshifted row.  The wave-uniform "tile lies
+//    wholly above this wave's rows" skip is taken against the shifted row.
+//  * The Q, O and LSE descriptors start at the block's first row and end at
+//    row n_b: rows past it read as zeros and their stores are dropped by the
+//    hardware range check, so nothing past n_b is written.
+//  * K/V source.  Contiguous: head hkv's rows of element b, the range ending
+//    at the block's last visible key.  Paged: a 64-key tile never straddles a
+//    page, so the descriptor is rebuilt per tile from the block table as
+//    tile_at() of fa_decode_kernel.hpp does (64-bit base, the range ending at
+//    the tile's last live row, an out-of-pool id a zero range); the page id of
+//    the tile after the one being loaded is fetched one tile ahead (a scalar
+//    load), so the table is off the critical path.  Only entries of pages
+//    holding a visible key are read.
+//  * FP8 cache (KV = unsigned char): converted in staging, between the global
+//    load and the LDS write; one 16-byte load is 16 elements and becomes two
+//    16-byte writes into the same images (cvt_fp8x8), so the images and every
+//    MFMA operand are those of the 16-bit kernel.  k_scale[hkv] rides on the
+//    score scale (the policy's c), v_scale[hkv] on the final normalisation.
+//    All of it sits under `if constexpr (KV8)`.
+//  * bf16 keeps the fp32 score scaling (kScaleS) and takes the row sums from
+//    the fp32 exponentials (M16's L32): a sum of bf16-rounded P would put
+//    2^-9 relative into the LSE of a row with few keys (as in decode).
+//  * Epilogue: O = acc / l (times v_scale), LSE = (m_ref + log2 l) ln 2.
+#pragma once
+
+#include "fa_decode_kernel.hpp"
+
+namespace fa {
+
+// LDS of every instantiation: two buffers of one K and one V image (64 rows of
+// 256-B slots each) -- what the 4-wave loop of fa_fwd_kernel.hpp uses.
+constexpr int kPrefillLdsBytes = 65536;
+constexpr int kPrefillBM = 128;  // query rows per workgroup
+
+struct PrefillParams {
+  const void* q;
+  const void* k;
+  const void* v;
+  void* o;
+  float* lse;          // [B][Hq][Sq] natural-log LSE, or nullptr
+  const int* kv_lens;  // device int32[B], or nullptr (= cap)
+  const int* q_lens;   // device int32[B], or nullptr (= sq)
+  int hq, hkv, sq, cap;
+  int group;           // hq / hkv
+  int nqb;             // 128-row query blocks per head
+  unsigned bhk;        // batch * hkv
+  int causal;
+  float c;             // log2(e) / sqrt(D)
+};
+// the page pool and block table of fa_decode_kernel.hpp's DecodePagedParams
+struct PrefillPagedParams : PrefillParams {
+  const int* table;
+  int max_pages;
+  int num_pages;
+  int tpp;                        // 64-key tiles per page
+  unsigned long long page_bytes;  // Hkv * page_size * row bytes
+  unsigned long long head_bytes;  // page_size * row bytes
+};
+struct PrefillKv8Params : PrefillParams {
+  const float* k_scale;
+  const float* v_scale;
+};
+struct PrefillPagedKv8Params : PrefillPagedParams {
+  const float* k_scale;
+  const float* v_scale;
+};
+
+template <class T, int HDIM, bool PAGED = false, class P = PrefillParams, class KV = T>
+__global__ __launch_bounds__(256, 2) void fa_prefill_kernel(P p) {
+  __shared__ __attribute__((aligned(16))) char smem[kPrefillLdsBytes];
+  constexpr bool KV8 = !std::is_same<KV, T>::value;
+  static_assert(!KV8 || std::is_same<KV, unsigned char>::value, "the cache holds T or E4M3 bytes");
+  using Pol = M16<64, T, HDIM, 2, std::is_same<T, __bf16>::value>;
+  constexpr int BN = 64, WAVES = 4, RW = Pol::RW, BM = kPrefillBM;
+  static_assert(WAVES * RW == BM, "four waves of 32 rows");
+  constexpr int ROW = 2 * HDIM;                // bytes per Q/O row
+  constexpr int CROW = KV8 ? HDIM : 2 * HDIM;  // bytes per K/V cache row
+  constexpr int TILE_BYTES = BN * 256;         // LDS image: 256-B row slots at any head_dim
+  static_assert(4 * TILE_BYTES == kPrefillLdsBytes, "two (K, V) buffers");
+  // 16-byte loads per thread per tile (K and V each) and the tile rows the
+  // workgroup covers per load instruction
+  constexpr int NCH = (BN * CROW / 16) / (WAVES * 64);
+  constexpr int RPP = BN / NCH;
+  typedef typename Elem<T>::x8 tx8;
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+
+  // workgroup -> (query block, batch, kv head, head of the group): the G query
+  // heads of one K/V head and block are adjacent (they stream the same K/V),
+  // causal blocks heaviest first
+  const unsigned gi = blockIdx.x % (unsigned)p.group;
+  const unsigned rest = blockIdx.x / (unsigned)p.group;
+  const unsigned bhk = rest % p.bhk;
+  const int qbr = (int)(rest / p.bhk);
+  const int qb = p.causal ? p.nqb - 1 - qbr : qbr;
+  const int b = (int)(bhk / (unsigned)p.hkv), hk = (int)(bhk - (unsigned)b * p.hkv);
+  const int hq = hk * p.group + (int)gi;
+
+  int nq = p.q_lens ? p.q_lens[b] : p.sq;
+  nq = __builtin_amdgcn_readfirstlane(min(max(nq, 0), p.sq));
+  const int q0 = qb * BM;
+  if (q0 >= nq) return;  // nothing of this block is valid: nothing is written
+  int len = p.kv_lens ? p.kv_lens[b] : p.cap;
+  len = __builtin_amdgcn_readfirstlane(min(max(len, 0), p.cap));
+  const int off = len - nq;  // keys before the chunk (negative: the leading rows see nothing)
+  const int kv_hi = p.causal ? max(0, min(len, off + q0 + BM)) : len;
+  const int ntiles = (kv_hi + BN - 1) / BN;
+  // the row the mask compares keys with; non-causal: past every key
+  const int qwm = p.causal ? off + q0 + wave * RW : 0x3fffffff;
+  const int qwl = wave * RW;  // this wave's first row within the block's descriptors
+
+  const size_t qrow0 = ((size_t)b * p.hq + hq) * (size_t)p.sq + q0;
+  const int qrows = nq - q0;  // valid rows from the block's first on (may exceed 128)
+  const __amdgpu_buffer_rsrc_t rq = make_rsrc(static_cast<const char*>(p.q) + qrow0 * ROW, qrows * ROW);
+  const __amdgpu_buffer_rsrc_t ro = make_rsrc(static_cast<char*>(p.o) + qrow0 * ROW, qrows * ROW);
+
+  // score scale: the cache's K scale rides on it (a wave-uniform load)
+  float csc = p.c;
+  [[maybe_unused]] float vsc = 1.0f;
+  if constexpr (KV8) {
+    if (p.k_scale) csc *= p.k_scale[hk];
+    if (p.v_scale) vsc = p.v_scale[hk];
+  }
+
+  Pol pol;
+  pol.init(lane, csc);
+  pol.issue_q(rq, qwl);  // scaled once tile 0's loads are in flight
+
+  // Staging.  16-bit: the policy's lanes (K natural row-major, V two rows of
+  // opposite parity x 4 chunks per 8 lanes).  FP8: a lane holds a 16-byte
+  // piece (16 elements) that becomes chunks 2 piece and 2 piece + 1 of its
+  // row's slot; per 8 lanes K takes two rows of opposite parity x 4 pieces and
+  // V the lanes of fa_decode_kernel.hpp's FP8 V staging, so each of the two
+  // writes of 8 consecutive lanes covers the 8 distinct 16-B slots of a bank
+  // row in image B / image A.
+  int kr0, kc, vr0, vc;
+  if constexpr (KV8) {
+    if constexpr (HDIM == 128) {
+      kr0 = 8 * wave + ((lane >> 2) & 1) + 2 * ((lane >> 4) & 3);
+      kc = (lane & 3) + 4 * ((lane >> 3) & 1);
+      vr0 = 8 * wave + ((lane >> 1) & 1) + 2 * ((lane >> 5) & 1) + 4 * ((lane >> 2) & 1);
+      vc = (lane & 1) + 2 * ((lane >> 3) & 3);
+    } else {
+      kr0 = 16 * wave + ((lane >> 2) & 1) + 2 * ((lane >> 3) & 7);
+      kc = lane & 3;
+      vr0 = 16 * wave + ((lane >> 1) & 1) + 2 * ((lane >> 4) & 1) + 4 * ((lane >> 2) & 1) +
+            8 * ((lane >> 5) & 1);
+      vc = (lane & 1) + 2 * ((lane >> 3) & 1);
+    }
+  } else {
+    kr0 = pol.k_stage_row(wave), kc = pol.k_stage_ch();
+    vr0 = pol.v_stage_row(wave), vc = pol.v_stage_ch();
+  }
+  static_assert(KV8 || RPP == Pol::RPW * WAVES, "the policy's staging covers RPW rows per wave");
+  const int kvo = kr0 * CROW + kc * 16, vvo = vr0 * CROW + vc * 16;
+
+  // The descriptors of the tile whose loads are issued next: its 64 rows start
+  // at the base and the range ends at its last visible row (a tile past the
+  // range: zero bytes, no memory traffic).
+  const size_t kvoff = PAGED ? 0 : (size_t)bhk * (size_t)p.cap * CROW;
+  const char* Kh = static_cast<const char*>(p.k) + kvoff;
+  const char* Vh = static_cast<const char*>(p.v) + kvoff;
+  __amdgpu_buffer_rsrc_t rk, rv;
+  // pg: the tile's pool page, r: its 64-row block within head hk's part of the page (paged only)
+  auto tile_at = [&](int tl, [[maybe_unused]] int pg, [[maybe_unused]] int r) {
+    const int live = max(0, min(kv_hi - BN * tl, BN));
+    if constexpr (PAGED) {
+      // a page id outside the pool: zero rows, the base stays inside the pool
+      const bool ok = (unsigned)pg < (unsigned)p.num_pages;
+      const size_t o = (size_t)(ok ? pg : 0) * p.page_bytes + (size_t)hk * p.head_bytes +
+                       (size_t)(BN * r) * CROW;
+      rk = make_rsrc(Kh + o, ok ? live * CROW : 0);
+      rv = make_rsrc(Vh + o, ok ? live * CROW : 0);
+    } else {
+      // a tile past the range keeps the base inside the cache (tl <= ntiles)
+      const size_t o = (size_t)min(BN * tl, kv_hi) * CROW;
+      rk = make_rsrc(Kh + o, live * CROW);
+      rv = make_rsrc(Vh + o, live * CROW);
+    }
+  };
+  u32x4 kst[NCH], vst[NCH];
+  auto issue_loads = [&]() {
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+      kst[i] = __builtin_amdgcn_raw_buffer_load_b128(rk, kvo + RPP * i * CROW, 0, 0);
+      vst[i] = __builtin_amdgcn_raw_buffer_load_b128(rv, vvo + RPP * i * CROW, 0, 0);
+    }
+  };
+  auto write_lds = [&](char* kb) {
+    char* vb = kb + TILE_BYTES;
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+      if constexpr (KV8) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          *reinterpret_cast<tx8*>(kb + Pol::k_lds(kr0 + RPP * i, 2 * kc + j)) =
+              cvt_fp8x8<T>(kst[i][2 * j], kst[i][2 * j + 1]);
+          *reinterpret_cast<tx8*>(vb + Pol::v_lds(vr0 + RPP * i, 2 * vc + j)) =
+              cvt_fp8x8<T>(vst[i][2 * j], vst[i][2 * j + 1]);
+        }
+      } else {
+        *reinterpret_cast<u32x4*>(kb + Pol::k_lds(kr0 + RPP * i, kc)) = kst[i];
+        *reinterpret_cast<u32x4*>(vb + Pol::v_lds(vr0 + RPP * i, vc)) = vst[i];
+      }
+    }
+  };
+
+  // Paged: pgN / rN are the page id and block of the tile loaded next, (jF,
+  // rF) the table index and block of the tile after it, whose id is fetched
+  // while the next tile's loads are in flight.  Only tiles below ntiles
+  // (pages holding a visible key) have their entries read.
+  [[maybe_unused]] int pgN = 0, rN = 0, jF = 0, rF = 0;
+  typedef const __attribute__((address_space(4))) int* tab_t;  // scalar loads
+  [[maybe_unused]] tab_t tab = nullptr;
+  if constexpr (PAGED) {
+    tab = (tab_t)(p.table + (size_t)b * p.max_pages);
+    const int pg0 = ntiles > 0 ? tab[0] : 0;
+    tile_at(0, pg0, 0);
+    rN = p.tpp > 1 ? 1 : 0;
+    pgN = ntiles > 1 ? tab[p.tpp > 1 ? 0 : 1] : 0;
+    jF = 2 / p.tpp, rF = 2 - jF * p.tpp;
+  } else {
+    tile_at(0, 0, 0);
+  }
+
+  // prologue: unconditional, so every earlier load (Q included) has retired
+  // before the loop and no in-loop MFMA waits on the prefetch
+  issue_loads();
+  // every prologue load is issued before the first VALU that waits on one
+  // (else the scheduler hoists Q's scaling above the K/V loads)
+  __builtin_amdgcn_sched_barrier(0);
+  pol.scale_q();
+  write_lds(smem);
+  // vmcnt(0): else the compiler's waitcnt analysis keeps Q "pending" at the
+  // loop header and every iteration's first MFMAs wait for the prefetch
+  __builtin_amdgcn_s_waitcnt(0x0F70);
+  __syncthreads();
+
+  auto step = [&](int j, auto buf_c) {
+    constexpr int BUF = decltype(buf_c)::value;
+    char* kb = smem + BUF * 2 * TILE_BYTES;
+    char* kb_next = smem + (BUF ^ 1) * 2 * TILE_BYTES;
+    const int kv0 = j * BN;
+    tile_at(j + 1, pgN, rN);
+    issue_loads();  // past kv_hi: zero bytes, no memory traffic
+    if constexpr (PAGED) {
+      if (j + 2 < ntiles) pgN = tab[jF];
+      rN = rF;
+      if (++rF == p.tpp) rF = 0, ++jF;
+    }
+    // wave-uniform: does any key of this tile lie at/below some row of this wave?
+    if (kv0 <= qwm + RW - 1) {
+      const bool need_mask = (kv0 + BN > kv_hi) || (kv0 + BN - 1 > qwm);
+      pol.template tile<true>(kb, kb + TILE_BYTES, kv0, kv_hi, qwm, csc, need_mask);
+    }
+    write_lds(kb_next);
+    __syncthreads();
+  };
+  int j = 0;
+  for (; j + 1 < ntiles; j += 2) {
+    step(j, std::integral_constant<int, 0>{});
+    step(j + 1, std::integral_constant<int, 1>{});
+  }
+  if (j < ntiles) step(j, std::integral_constant<int, 0>{});
+
+  pol.store_o(ro, qwl, vsc);
+  if (p.lse) {
+    const __amdgpu_buffer_rsrc_t rl = make_rsrc(p.lse + qrow0, qrows * 4);
+#pragma unroll
+    for (int bb = 0; bb < Pol::QB; ++bb) {
+      const float l = pol.row_sum(bb);
+      const float lse = l > 0.f ? (pol.m_ref[bb] + __builtin_log2f(l)) * 0.6931471805599453f : ninf();
+      if (pol.g == 0)
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, lse), rl,
+                                              (qwl + 16 * bb + pol.r16) * 4, 0, 0);
+    }
+  }
+}
+
+}  // namespace fa

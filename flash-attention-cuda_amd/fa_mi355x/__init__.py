@@ -64,6 +64,14 @@ EXPORTED_SYMBOLS = (
     "fa_cache_append_kv8_bf16",
     "fa_cache_append_paged_kv8_f16",
     "fa_cache_append_paged_kv8_bf16",
+    "fa_prefill_f16",
+    "fa_prefill_bf16",
+    "fa_prefill_paged_f16",
+    "fa_prefill_paged_bf16",
+    "fa_prefill_kv8_f16",
+    "fa_prefill_kv8_bf16",
+    "fa_prefill_paged_kv8_f16",
+    "fa_prefill_paged_kv8_bf16",
     "fa_select_config",
     "fa_num_configs",
     "fa_config_info",
@@ -185,6 +193,17 @@ def load_library() -> ctypes.CDLL:
         fn.argtypes = lib.fa_cache_append_paged_16.argtypes + [vp, vp]
     for name in EXPORTED_SYMBOLS:
         if name.startswith("fa_cache_append"):
+            getattr(lib, name).restype = i
+    for fn in (lib.fa_prefill_f16, lib.fa_prefill_bf16):
+        fn.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, vp, vp, i, vp]
+    for fn in (lib.fa_prefill_paged_f16, lib.fa_prefill_paged_bf16):
+        fn.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, vp, i, vp, vp, i, vp]
+    for fn in (lib.fa_prefill_kv8_f16, lib.fa_prefill_kv8_bf16):
+        fn.argtypes = lib.fa_prefill_f16.argtypes + [vp, vp]
+    for fn in (lib.fa_prefill_paged_kv8_f16, lib.fa_prefill_paged_kv8_bf16):
+        fn.argtypes = lib.fa_prefill_paged_f16.argtypes + [vp, vp]
+    for name in EXPORTED_SYMBOLS:
+        if name.startswith("fa_prefill"):
             getattr(lib, name).restype = i
     lib.fa_decode_num_splits.argtypes = [i, i, i, i, i, i]
     lib.fa_decode_num_splits.restype = i
@@ -506,24 +525,46 @@ def _check_decode_tail(q, kname, k, vname, v, out, k_scale, v_scale, block_table
     _check_scales_device(q, k_scale, v_scale)
 
 
-def _check_decode(q, k_cache, v_cache, kv_lens, out, k_scale=None, v_scale=None):
+def _check_q_lens(q, q_lens, where):
+    """The prefill wrappers' q_lens, worded like the append wrappers' new_lens:
+    dtype and shape (`where` false, before the tensors' devices are looked at),
+    then its device (`where` true)."""
+    if q_lens is None:
+        return
+    if where:
+        if not q_lens.is_cuda or q_lens.device != q.device:
+            raise FlashAttentionError(FA_ERR_NULL_POINTER, f"q_lens must be a tensor on {q.device}")
+        return
+    import torch
+
+    if q_lens.dtype != torch.int32:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"q_lens must be int32, got {q_lens.dtype}")
+    if q_lens.dim() != 1 or q_lens.shape[0] != q.shape[0] or not q_lens.is_contiguous():
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, "q_lens must be a contiguous [B] tensor")
+
+
+def _check_decode(q, k_cache, v_cache, kv_lens, out, k_scale=None, v_scale=None, q_lens=None):
     """Raise FlashAttentionError unless q/out are contiguous [B,Hq,Sq,D] and
     k_cache/v_cache contiguous [B,Hkv,cap,D] device tensors of one 16-bit dtype
     (or both torch.float8_e4m3fn beside a 16-bit q, with optional float32
     [Hkv] scales: returns True then) and device with Hq % Hkv == 0, and
     kv_lens (if given) is int32 [B] there.
     Dtypes, ranks and shapes are checked before where the tensors live, so
-    each rejection names its own cause whatever the device."""
+    each rejection names its own cause whatever the device.  q_lens (the
+    prefill wrappers only): int32 [B], checked like kv_lens."""
     kv8 = _check_decode_head(q, "k_cache", k_cache, "v_cache", v_cache, out, k_scale, v_scale, " (BHSD)")
     if k_cache.shape != v_cache.shape:
         raise FlashAttentionError(FA_ERR_BAD_SHAPE, "k_cache and v_cache must have one shape")
     if k_cache.shape[0] != q.shape[0] or k_cache.shape[3] != q.shape[3]:
         raise FlashAttentionError(FA_ERR_BAD_SHAPE, "q and the caches must agree in batch and head_dim")
+    _check_q_lens(q, q_lens, False)
     _check_decode_tail(q, "k_cache", k_cache, "v_cache", v_cache, out, k_scale, v_scale, None, kv_lens)
+    _check_q_lens(q, q_lens, True)
     return kv8
 
 
-def _check_decode_paged(q, k_pages, v_pages, block_table, kv_lens, out, k_scale=None, v_scale=None):
+def _check_decode_paged(q, k_pages, v_pages, block_table, kv_lens, out, k_scale=None, v_scale=None,
+                        q_lens=None):
     """Raise FlashAttentionError unless q/out are contiguous [B,Hq,Sq,D],
     k_pages/v_pages contiguous [num_pages,Hkv,page_size,D] pools of q's 16-bit
     dtype (or both torch.float8_e4m3fn, with optional float32 [Hkv] scales:
@@ -542,8 +583,10 @@ def _check_decode_paged(q, k_pages, v_pages, block_table, kv_lens, out, k_scale=
     if k_pages.shape[2] == 0 or k_pages.shape[2] % 64 != 0:
         raise FlashAttentionError(FA_ERR_BAD_SHAPE,
                                   f"page_size {k_pages.shape[2]} is not a positive multiple of 64")
+    _check_q_lens(q, q_lens, False)
     _check_decode_tail(q, "k_pages", k_pages, "v_pages", v_pages, out, k_scale, v_scale, block_table,
                        kv_lens)
+    _check_q_lens(q, q_lens, True)
     return kv8
 
 
@@ -662,6 +705,106 @@ def flash_attention_decode_paged(q, k_pages, v_pages, block_table, kv_lens=None,
     kv8 = _check_decode_paged(q, k_pages, v_pages, block_table, kv_lens, out, k_scale, v_scale)
     return _decode_call(kv8, q, k_pages, v_pages, out, block_table, kv_lens, causal, return_lse,
                         num_splits, stream, k_scale, v_scale)
+
+
+_PRE_ENTRY = {}  # (paged, kv8, bf16) -> the C entry
+
+
+def _prefill_call(kv8, q, k, v, out, block_table, kv_lens, q_lens, causal, return_lse, stream, k_scale,
+                  v_scale):
+    """The call of both prefill functions after their checks (the twin of
+    :func:`_decode_call`, without a workspace): the stream, the optional LSE
+    and the C entry of the cache form and q's dtype.  The LSE is allocated
+    with empty(): rows past q_lens are not written."""
+    import torch
+
+    b, hq, sq, d = q.shape
+    hkv = k.shape[1]
+    paged = block_table is not None
+    if paged:
+        cache = (d, k.shape[0], k.shape[2], block_table.data_ptr(), block_table.shape[1])
+    else:
+        cache = (k.shape[2], d)
+    lib = _lib or load_library()
+    which = (paged, kv8, q.dtype is torch.bfloat16)
+    fn = _PRE_ENTRY.get(which)
+    if fn is None:
+        fn = _PRE_ENTRY[which] = getattr(lib, "fa_prefill" + ("_paged" if paged else "")
+                                         + ("_kv8" if kv8 else "") + ("_bf16" if which[2] else "_f16"))
+    tail = ()
+    if kv8:
+        tail = (k_scale.data_ptr() if k_scale is not None else None,
+                v_scale.data_ptr() if v_scale is not None else None)
+    dev = q.device.index
+    if stream is None:
+        st = torch._C._cuda_getCurrentRawStream(dev)
+    else:
+        st = stream if isinstance(stream, int) else stream.cuda_stream
+    lse = torch.empty((b, hq, sq), dtype=torch.float32, device=q.device) if return_lse else None
+    with torch.cuda.device(dev):
+        rc = fn(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
+                lse.data_ptr() if return_lse else None, b, hq, hkv, sq, *cache,
+                kv_lens.data_ptr() if kv_lens is not None else None,
+                q_lens.data_ptr() if q_lens is not None else None, int(bool(causal)), st, *tail)
+    _check(rc)
+    return (out, lse) if return_lse else out
+
+
+def flash_attention_prefill(q, k_cache, v_cache, kv_lens=None, q_lens=None, causal: bool = True,
+                            out=None, return_lse: bool = False, stream=None, k_scale=None,
+                            v_scale=None):
+    """Prefill attention over a K/V cache (fa_prefill_f16 / fa_prefill_bf16, or
+    fa_prefill_kv8_* over an FP8 cache): a prompt, or a chunk of one behind a
+    cached prefix, against the cache :func:`flash_attention_cache_append` wrote
+    and :func:`flash_attention_decode` reads.
+
+    q: [B, Hq, Sq, D] (Sq >= 1, any length); k_cache, v_cache: [B, Hkv, cap, D]
+    with Hq % Hkv == 0 (GQA / MQA); fp16 or bf16 contiguous device tensors of
+    one dtype (or the caches both torch.float8_e4m3fn, with k_scale / v_scale
+    as for decode), D = 128 or 64.  kv_lens: int32 [B], the lengths AFTER the
+    chunk was appended (None: cap).  q_lens: int32 [B], the tensor the append
+    took as new_lens (None: Sq): element b uses its first n_b = clamp(q_lens[b],
+    0, Sq) rows.  causal: bottom-right aligned, row t of element b sees keys
+    < kv_lens[b] - n_b + t + 1.  A row that sees no key gives zeros and LSE =
+    -inf.  Rows t >= n_b of out and lse are not written: with out=None (an
+    empty_like(q)) they are unspecified.  Cache rows past a length are never
+    read.  Returns out, or (out, lse) with lse fp32 [B, Hq, Sq] (natural log)
+    when return_lse.  Lengths and scales are read on the device: no sync, no
+    workspace, graph-capturable; enqueued on ``stream`` (default: torch's
+    current stream).
+    """
+    if out is None:
+        import torch
+
+        out = torch.empty_like(q)
+    kv8 = _check_decode(q, k_cache, v_cache, kv_lens, out, k_scale, v_scale, q_lens)
+    return _prefill_call(kv8, q, k_cache, v_cache, out, None, kv_lens, q_lens, causal, return_lse,
+                         stream, k_scale, v_scale)
+
+
+def flash_attention_prefill_paged(q, k_pages, v_pages, block_table, kv_lens=None, q_lens=None,
+                                  causal: bool = True, out=None, return_lse: bool = False, stream=None,
+                                  k_scale=None, v_scale=None):
+    """:func:`flash_attention_prefill` over the page pools
+    :func:`flash_attention_decode_paged` reads (fa_prefill_paged_f16 / _bf16, or
+    fa_prefill_paged_kv8_* over an FP8 pool).
+
+    k_pages, v_pages: [num_pages, Hkv, page_size, D] with page_size % 64 == 0;
+    block_table: int32 [B, max_pages_per_seq]; kv_lens None: max_pages_per_seq
+    * page_size.  Only table entries and rows below a length are read, and a
+    page id outside the pool reads as zero rows.  The result equals
+    :func:`flash_attention_prefill` on the gathered cache bit for bit.  Rows
+    t >= n_b of out and lse are not written (unspecified with out=None).
+    """
+    if block_table is None:
+        raise FlashAttentionError(FA_ERR_NULL_POINTER, "block_table is required")
+    if out is None:
+        import torch
+
+        out = torch.empty_like(q)
+    kv8 = _check_decode_paged(q, k_pages, v_pages, block_table, kv_lens, out, k_scale, v_scale, q_lens)
+    return _prefill_call(kv8, q, k_pages, v_pages, out, block_table, kv_lens, q_lens, causal,
+                         return_lse, stream, k_scale, v_scale)
 
 
 def _check_append(k_new, v_new, kname, k, vname, v, block_table, kv_lens, new_lens, k_scale, v_scale):

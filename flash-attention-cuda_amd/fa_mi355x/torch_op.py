@@ -8,6 +8,8 @@ rank 3: the wrapper that puts the kernel beside PyTorch SDPA on one box).
     o = torch.ops.fa_mi355x.decode(q, k8_cache, v8_cache, kv_lens, k_scale=ks, v_scale=vs)  # FP8 cache
     torch.ops.fa_mi355x.cache_append(k_new, v_new, k_cache, v_cache, kv_lens)  # writes the caches
     torch.ops.fa_mi355x.cache_append_paged(k_new, v_new, k_pages, v_pages, block_table, kv_lens)
+    o = torch.ops.fa_mi355x.prefill(q, k_cache, v_cache, kv_lens, q_lens, causal=True)  # any Sq
+    o = torch.ops.fa_mi355x.prefill_paged(q, k_pages, v_pages, block_table, kv_lens, q_lens)
 
 ``q, k, v``: fp16 or bf16 ``[B, H, S, D]`` (D = 128 or 64) tensors on the GPU (BHSD, the
 reference layout, flash_attention.cu:119-122); returns a new tensor of the same shape and dtype.
@@ -28,7 +30,8 @@ from __future__ import annotations
 import torch
 
 from . import (flash_attention_cache_append, flash_attention_cache_append_paged,
-               flash_attention_decode, flash_attention_decode_paged, flash_attention_fwd)
+               flash_attention_decode, flash_attention_decode_paged, flash_attention_fwd,
+               flash_attention_prefill, flash_attention_prefill_paged)
 
 OP_NAME = "fa_mi355x::fwd"
 
@@ -225,3 +228,80 @@ _LIB.impl("cache_append_paged", _cache_append_paged_cpu, "CPU")
 torch.library.register_fake(CACHE_APPEND_PAGED_OP_NAME, _cache_append_paged_fake, lib=_LIB)
 
 cache_append_paged = torch.ops.fa_mi355x.cache_append_paged
+
+# prefill(q [B,Hq,Sq,D] of any Sq, k_cache / v_cache [B,Hkv,cap,D], kv_lens and
+# q_lens int32 [B] or None) and prefill_paged (the pools and the block table):
+# fa_mi355x.flash_attention_prefill[_paged] behind the same kind of
+# registration as decode.  The caches are taken as they are (a strided cache
+# raises); an FP8 cache takes k_scale / v_scale.  Rows past q_lens of the
+# returned tensor are unspecified.
+PREFILL_OP_NAME = "fa_mi355x::prefill"
+_LIB.define("prefill(Tensor q, Tensor k_cache, Tensor v_cache, Tensor? kv_lens=None, "
+            "Tensor? q_lens=None, bool causal=True, Tensor? k_scale=None, "
+            "Tensor? v_scale=None) -> Tensor")
+
+
+def _prefill_gpu(q, k_cache, v_cache, kv_lens=None, q_lens=None, causal: bool = True, k_scale=None,
+                 v_scale=None) -> torch.Tensor:
+    _no_grad_needed(q, k_cache, v_cache)
+    return flash_attention_prefill(q.contiguous(), k_cache, v_cache,
+                                   None if kv_lens is None else kv_lens.contiguous(),
+                                   None if q_lens is None else q_lens.contiguous(), causal=causal,
+                                   k_scale=k_scale, v_scale=v_scale)
+
+
+def _prefill_cpu(q, k_cache, v_cache, kv_lens=None, q_lens=None, causal: bool = True, k_scale=None,
+                 v_scale=None) -> torch.Tensor:
+    raise ValueError("fa_mi355x::prefill needs GPU tensors (no CPU path)")
+
+
+def _prefill_fake(q, k_cache, v_cache, kv_lens=None, q_lens=None, causal: bool = True, k_scale=None,
+                  v_scale=None) -> torch.Tensor:
+    _no_grad_needed(q, k_cache, v_cache)
+    torch._check(q.dim() == 4 and q.shape[-1] in (64, 128), lambda: "expected [B, Hq, Sq, 64|128]")
+    torch._check(q.dtype in (torch.float16, torch.bfloat16), lambda: "expected fp16 or bf16")
+    return torch.empty_like(q, memory_format=torch.contiguous_format)
+
+
+_LIB.impl("prefill", _prefill_gpu, "CUDA")
+_LIB.impl("prefill", torch.library.fallthrough_kernel, "Autograd")
+_LIB.impl("prefill", _prefill_cpu, "CPU")
+torch.library.register_fake(PREFILL_OP_NAME, _prefill_fake, lib=_LIB)
+
+prefill = torch.ops.fa_mi355x.prefill
+
+PREFILL_PAGED_OP_NAME = "fa_mi355x::prefill_paged"
+_LIB.define("prefill_paged(Tensor q, Tensor k_pages, Tensor v_pages, Tensor block_table, "
+            "Tensor? kv_lens=None, Tensor? q_lens=None, bool causal=True, Tensor? k_scale=None, "
+            "Tensor? v_scale=None) -> Tensor")
+
+
+def _prefill_paged_gpu(q, k_pages, v_pages, block_table, kv_lens=None, q_lens=None, causal: bool = True,
+                       k_scale=None, v_scale=None) -> torch.Tensor:
+    _no_grad_needed(q, k_pages, v_pages)
+    return flash_attention_prefill_paged(q.contiguous(), k_pages, v_pages, block_table.contiguous(),
+                                         None if kv_lens is None else kv_lens.contiguous(),
+                                         None if q_lens is None else q_lens.contiguous(),
+                                         causal=causal, k_scale=k_scale, v_scale=v_scale)
+
+
+def _prefill_paged_cpu(q, k_pages, v_pages, block_table, kv_lens=None, q_lens=None, causal: bool = True,
+                       k_scale=None, v_scale=None) -> torch.Tensor:
+    raise ValueError("fa_mi355x::prefill_paged needs GPU tensors (no CPU path)")
+
+
+def _prefill_paged_fake(q, k_pages, v_pages, block_table, kv_lens=None, q_lens=None, causal: bool = True,
+                        k_scale=None, v_scale=None) -> torch.Tensor:
+    _no_grad_needed(q, k_pages, v_pages)
+    torch._check(q.dim() == 4 and q.shape[-1] in (64, 128), lambda: "expected [B, Hq, Sq, 64|128]")
+    torch._check(q.dtype in (torch.float16, torch.bfloat16), lambda: "expected fp16 or bf16")
+    torch._check(block_table.dim() == 2, lambda: "expected a [B, max_pages_per_seq] block table")
+    return torch.empty_like(q, memory_format=torch.contiguous_format)
+
+
+_LIB.impl("prefill_paged", _prefill_paged_gpu, "CUDA")
+_LIB.impl("prefill_paged", torch.library.fallthrough_kernel, "Autograd")
+_LIB.impl("prefill_paged", _prefill_paged_cpu, "CPU")
+torch.library.register_fake(PREFILL_PAGED_OP_NAME, _prefill_paged_fake, lib=_LIB)
+
+prefill_paged = torch.ops.fa_mi355x.prefill_paged

@@ -1,0 +1,209 @@
+#!/usr/bin/env python3
+"""Prefill-attention benchmark: fa_mi355x.flash_attention_prefill[_paged] over
+the four cache forms against what a caller had before it, arms alternated in
+one process (modelled on tools/decode_bench.py).
+
+One invocation = one shape and one dtype (run it under `timeout`), one JSON
+line per cache form.  Per form, interleaved round by round after a warm-up:
+
+  prefill   the new entry on the cache as it is (kv_lens / q_lens on the device);
+  (a) fwd   flash_attention_fwd at Hq = Hkv = heads_q and S = Skv on 16-bit
+            tensors: the asm tiers' kernel-only yardstick, reported as a ratio of
+            TFLOP/s -- NOT a bar (a plain-C++ 4-wave loop sits below W4);
+  (b) expand_fwd   no-prefix shapes only: what a caller must do without the
+            entry -- gather pages / dequantise / repeat_interleave K and V to
+            Hq heads into a scratch copy, then flash_attention_fwd -- timed
+            whole, with the scratch bytes it allocates;
+  (c) sdpa  prefix shapes only: PyTorch SDPA (enable_gqa, explicit bottom-right
+            mask) on the gathered, dequantised cache (the gather and
+            dequantisation are NOT in its time: it is charged the kernel only).
+
+TFLOP/s uses the reference's convention extended to the contract:
+4 * Hq * D * sum_b sum_t vis(b, t).
+
+    timeout 300 python3 tools/prefill_bench.py --shape headline --dtype fp16 \\
+        [--forms contig,paged,contig_kv8,paged_kv8] [--out profiles/prefill_bench.jsonl]
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+import torch.nn.functional as F
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+import fa_mi355x  # noqa: E402
+
+FP8 = torch.float8_e4m3fn
+PAGE = 256
+SHAPES = {
+    # name: (B, Hq, Hkv, Sq, prefix)
+    "headline": (8, 32, 8, 4096, 0),
+    "prefix": (8, 32, 8, 2048, 6144),
+    "long": (1, 32, 8, 8192, 0),
+    "short_chunk": (16, 32, 8, 512, 8192),
+}
+FORMS = ("contig", "paged", "contig_kv8", "paged_kv8")
+
+
+def flops(b, hq, d, sq, prefix):
+    vis = sum(prefix + t + 1 for t in range(sq))
+    return 4.0 * hq * d * b * vis
+
+
+def time_arms(fns, iters, rounds, warm=2):
+    """Median ms per call of each arm; the arms alternate round by round."""
+    ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+           for _ in range(rounds)] for _ in fns]
+    for fn in fns:
+        for _ in range(warm):
+            fn()
+    torch.cuda.synchronize()
+    for r in range(rounds):
+        for j, fn in enumerate(fns):
+            ev[j][r][0].record()
+            for _ in range(iters):
+                fn()
+            ev[j][r][1].record()
+    torch.cuda.synchronize()
+    out = []
+    for j in range(len(fns)):
+        ts = sorted(a.elapsed_time(b) / iters for a, b in ev[j])
+        out.append((ts[len(ts) // 2], ts[0], ts[-1]))
+    return out
+
+
+def run(shape, dt, form, rounds, iters):
+    b, hq, hkv, sq, prefix = SHAPES[shape]
+    d, g = 128, hq // hkv
+    skv = prefix + sq
+    gen = torch.Generator(device="cuda").manual_seed(1)
+
+    def rnd(*s):
+        return (torch.rand(s, generator=gen, device="cuda", dtype=torch.float32) * 2 - 1).to(dt)
+
+    q = rnd(b, hq, sq, d)
+    k16, v16 = rnd(b, hkv, skv, d), rnd(b, hkv, skv, d)
+    kv_lens = torch.full((b,), skv, dtype=torch.int32, device="cuda")
+    q_lens = torch.full((b,), sq, dtype=torch.int32, device="cuda")
+    kv8, paged = form.endswith("kv8"), form.startswith("paged")
+    scales = {}
+    k, v = k16, v16
+    if kv8:
+        ks = torch.tensor([2.0 ** -(3 - (h & 1)) for h in range(hkv)], dtype=torch.float32, device="cuda")
+        vs = torch.tensor([2.0 ** -(2 + (h & 1)) for h in range(hkv)], dtype=torch.float32, device="cuda")
+        k = (k16.float() / ks[None, :, None, None]).to(FP8)
+        v = (v16.float() / vs[None, :, None, None]).to(FP8)
+        scales = dict(k_scale=ks, v_scale=vs)
+    table = None
+    if paged:
+        mpp = skv // PAGE
+        perm = torch.randperm(b * mpp, generator=gen, device="cuda")
+
+        def pool(x):
+            out = torch.empty((b * mpp, hkv, PAGE, d), dtype=x.dtype, device="cuda")
+            src = x.view(b, hkv, mpp, PAGE, d).permute(0, 2, 1, 3, 4).reshape(b * mpp, hkv, PAGE, d)
+            out.view(torch.uint8)[perm] = src.contiguous().view(torch.uint8)
+            return out
+
+        k, v = pool(k), pool(v)
+        table = perm.view(b, mpp).to(torch.int32).contiguous()
+    out = torch.empty_like(q)
+
+    def prefill():
+        if paged:
+            return fa_mi355x.flash_attention_prefill_paged(q, k, v, table, kv_lens, q_lens, out=out, **scales)
+        return fa_mi355x.flash_attention_prefill(q, k, v, kv_lens, q_lens, out=out, **scales)
+
+    def expanded():
+        """The contiguous 16-bit Hq-head K and V a caller without the entry builds."""
+        kk, vv = k, v
+        if paged:
+            kk = kk[table.long()].permute(0, 2, 1, 3, 4).reshape(b, hkv, skv, d)
+            vv = vv[table.long()].permute(0, 2, 1, 3, 4).reshape(b, hkv, skv, d)
+        if kv8:
+            kk = (kk.float() * scales["k_scale"][None, :, None, None]).to(dt)
+            vv = (vv.float() * scales["v_scale"][None, :, None, None]).to(dt)
+        return kk, vv
+
+    # (a): the forward kernel alone at Hq = Hkv and S = Skv
+    fq, fk, fv = rnd(b, hq, skv, d), rnd(b, hq, skv, d), rnd(b, hq, skv, d)
+    fo = torch.empty_like(fq)
+
+    def fwd():
+        return fa_mi355x.flash_attention_fwd(fq, fk, fv, causal=True, out=fo)
+
+    arms, names = [prefill, fwd], ["prefill", "fwd"]
+    rec = dict(shape=shape, form=form, dtype=str(dt).split(".")[-1], batch=b, heads_q=hq, heads_kv=hkv,
+               seqlen_q=sq, prefix=prefix, head_dim=d, page_size=PAGE if paged else None, rounds=rounds,
+               iters=iters)
+    if prefix == 0:
+        def expand_fwd():
+            kk, vv = expanded()
+            return fa_mi355x.flash_attention_fwd(q, kk.repeat_interleave(g, 1), vv.repeat_interleave(g, 1),
+                                                 causal=True)
+
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        ref = expand_fwd()
+        rec["expand_scratch_bytes"] = int(torch.cuda.max_memory_allocated() - base - ref.numel() * 2)
+        arms.append(expand_fwd)
+        names.append("expand_fwd")
+    else:
+        gk, gv = (x.contiguous() for x in expanded())
+        key = torch.arange(skv, device="cuda")[None, :]
+        mask = (key <= prefix + torch.arange(sq, device="cuda")[:, None])[None, None]
+
+        def sdpa():
+            return F.scaled_dot_product_attention(q, gk, gv, attn_mask=mask, enable_gqa=g > 1)
+
+        ref = sdpa()
+        arms.append(sdpa)
+        names.append("sdpa")
+    rec["max_abs_diff_vs_" + names[2]] = float((prefill().float() - ref.float()).abs().max())
+    del ref
+    ts = time_arms(arms, iters, rounds)
+    fl = flops(b, hq, d, sq, prefix)
+    fl_fwd = 4.0 * b * hq * d * skv * (skv + 1) / 2
+    for name, (med, lo, hi) in zip(names, ts):
+        rec[name + "_ms"] = round(med, 4)
+        rec[name + "_min_ms"] = round(lo, 4)
+        rec[name + "_max_ms"] = round(hi, 4)
+    rec["prefill_tflops"] = round(fl / (ts[0][0] * 1e-3) / 1e12, 1)
+    rec["fwd_tflops"] = round(fl_fwd / (ts[1][0] * 1e-3) / 1e12, 1)
+    rec["prefill_over_fwd_rate"] = round(rec["prefill_tflops"] / rec["fwd_tflops"], 4)
+    rec[names[2] + "_over_prefill"] = round(ts[2][0] / ts[0][0], 4)
+    return rec
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shape", choices=sorted(SHAPES), required=True)
+    ap.add_argument("--dtype", choices=("fp16", "bf16"), default="fp16")
+    ap.add_argument("--forms", default=",".join(FORMS))
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--iters", type=int, default=2)
+    ap.add_argument("--out", default=None, help="appended to; default profiles/prefill_bench.jsonl")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("prefill_bench.py needs a GPU")
+    if args.out is None:
+        args.out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "profiles",
+                                "prefill_bench.jsonl")
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    dt = torch.bfloat16 if args.dtype == "bf16" else torch.float16
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    with open(args.out, "a") as f:
+        for form in args.forms.split(","):
+            assert form in FORMS, form
+            rec = run(args.shape, dt, form, args.rounds, args.iters)
+            rec["cus"] = cus
+            f.write(json.dumps(rec) + "\n")
+            f.flush()
+            print(json.dumps(rec), flush=True)
+            torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()

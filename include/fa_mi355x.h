@@ -384,6 +384,94 @@ int fa_cache_append_paged_kv8_bf16(const void* k_new, const void* v_new, void* k
                                    const int* kv_lens, const int* new_lens, void* hip_stream,
                                    const float* k_scale, const float* v_scale);
 
+/* Prefill attention over the same K/V caches: any number of query tokens per
+ * head (a whole prompt, or a chunk of one behind a cached prefix) against the
+ * cache fa_cache_append_* wrote and fa_decode_* reads, in all four cache forms
+ * (contiguous / paged, 16-bit / FP8 E4M3), with grouped K/V heads.  A prompt's
+ * life, append -> prefill -> (append -> decode)*, runs over one cache with the
+ * same kv_lens, block table and scales.
+ *   q, o   [batch][heads_q][seqlen_q][head_dim]  16-bit, seqlen_q >= 1 (no
+ *          upper bound but the 32-bit ranges below), head_dim 128 or 64
+ *   k, v   the cache of fa_decode_* / fa_decode_kv8_*; k_pages, v_pages,
+ *          block_table, num_pages, page_size, max_pages_per_seq: the pool of
+ *          fa_decode_paged_* / fa_decode_paged_kv8_* (kv_capacity :=
+ *          max_pages_per_seq * page_size)
+ *   n_b   = q_lens ? clamp(q_lens[b], 0, seqlen_q) : seqlen_q
+ *          the valid LEADING query tokens of element b: q_lens is the tensor
+ *          fa_cache_append_* took as new_lens, with k_new's convention
+ *   len_b = kv_lens ? clamp(kv_lens[b], 0, kv_capacity) : kv_capacity
+ *          the keys of element b, the chunk's own included (the lengths AFTER
+ *          the append)
+ *   off_b = len_b - n_b   the keys that precede the chunk
+ *   O[b,hq,t,:] = softmax(Q[b,hq,t,:] . K[b,hkv,0:vis,:]^T / sqrt(D))
+ *                 . V[b,hkv,0:vis,:]                       for t < n_b
+ *   hkv = hq / (heads_q / heads_kv)
+ *   vis = causal ? clamp(off_b + t + 1, 0, len_b) : len_b
+ * causal is bottom-right aligned, as for decode: with q_lens == NULL and
+ * seqlen_q <= 16 the contract is fa_decode_*'s own.  A row that sees no key
+ * (vis == 0, e.g. kv_lens[b] < n_b) gives O = 0 exactly and LSE = -inf.
+ * Rows t >= n_b of o and lse are NOT WRITTEN (the read-side twin of append's
+ * "nothing else is touched").  Cache rows at or past len_b, unmapped table
+ * entries and pages past the length are never read (they may hold NaN); a
+ * page id outside [0, num_pages) in an entry that is read reads as zero rows,
+ * as for fa_decode_paged_*.
+ *   lse    optional fp32 [batch][heads_q][seqlen_q], natural log; may be NULL.
+ *   kv_lens, q_lens, block_table, k_scale, v_scale are DEVICE arrays read by
+ *          the kernel: no host sync, no workspace, graph-capturable; a captured
+ *          graph follows values rewritten between replays.  FP8: K is read as
+ *          k_scale[hkv] * K8 and V as v_scale[hkv] * V8 (NULL = 1.0), the bytes
+ *          converted exactly to the 16-bit type on their way into LDS.
+ * A workgroup is (batch element, query head, 128-row query block); a block at
+ * or past n_b returns at once.  The paged entries' O and LSE are bit-identical
+ * to the contiguous entries' on the gathered cache.
+ * Argument errors, all returned before any launch, in fa_decode_*'s order:
+ * a negative count: FA_ERR_BAD_SHAPE; head_dim other than 64 / 128:
+ * FA_ERR_UNSUPPORTED_HEAD_DIM; seqlen_q < 1, page_size not a positive multiple
+ * of 64 (or page_size * 2 * head_dim > INT_MAX), num_pages <= 0,
+ * max_pages_per_seq < 0, a logical capacity > INT_MAX - 64, heads_q %
+ * heads_kv != 0, batch * heads_q * seqlen_q > INT_MAX, seqlen_q * 2 * head_dim
+ * > INT_MAX, kv_capacity * 2 * head_dim > INT_MAX (contiguous; the FP8 entries
+ * accept the same capacities) or more workgroups than a grid takes:
+ * FA_ERR_BAD_SHAPE; q, k, v, o (or block_table) NULL with kv_capacity > 0:
+ * FA_ERR_NULL_POINTER.  batch == 0 or heads_q == 0 return FA_OK with nothing
+ * looked at (the page geometry is still checked); kv_capacity == 0 with rows
+ * present fills O with zeros and LSE with -inf for ALL rows, as decode does.
+ * fa_prefill_* are not tile configs: fa_config_info() does not list them. */
+int fa_prefill_f16(const void* q, const void* k, const void* v, void* o, float* lse,
+                   int batch, int heads_q, int heads_kv, int seqlen_q, int kv_capacity,
+                   int head_dim, const int* kv_lens, const int* q_lens, int causal,
+                   void* hip_stream);
+int fa_prefill_bf16(const void* q, const void* k, const void* v, void* o, float* lse,
+                    int batch, int heads_q, int heads_kv, int seqlen_q, int kv_capacity,
+                    int head_dim, const int* kv_lens, const int* q_lens, int causal,
+                    void* hip_stream);
+int fa_prefill_paged_f16(const void* q, const void* k_pages, const void* v_pages, void* o, float* lse,
+                         int batch, int heads_q, int heads_kv, int seqlen_q, int head_dim,
+                         int num_pages, int page_size, const int* block_table, int max_pages_per_seq,
+                         const int* kv_lens, const int* q_lens, int causal, void* hip_stream);
+int fa_prefill_paged_bf16(const void* q, const void* k_pages, const void* v_pages, void* o, float* lse,
+                          int batch, int heads_q, int heads_kv, int seqlen_q, int head_dim,
+                          int num_pages, int page_size, const int* block_table, int max_pages_per_seq,
+                          const int* kv_lens, const int* q_lens, int causal, void* hip_stream);
+int fa_prefill_kv8_f16(const void* q, const void* k, const void* v, void* o, float* lse,
+                       int batch, int heads_q, int heads_kv, int seqlen_q, int kv_capacity,
+                       int head_dim, const int* kv_lens, const int* q_lens, int causal,
+                       void* hip_stream, const float* k_scale, const float* v_scale);
+int fa_prefill_kv8_bf16(const void* q, const void* k, const void* v, void* o, float* lse,
+                        int batch, int heads_q, int heads_kv, int seqlen_q, int kv_capacity,
+                        int head_dim, const int* kv_lens, const int* q_lens, int causal,
+                        void* hip_stream, const float* k_scale, const float* v_scale);
+int fa_prefill_paged_kv8_f16(const void* q, const void* k_pages, const void* v_pages, void* o,
+                             float* lse, int batch, int heads_q, int heads_kv, int seqlen_q,
+                             int head_dim, int num_pages, int page_size, const int* block_table,
+                             int max_pages_per_seq, const int* kv_lens, const int* q_lens, int causal,
+                             void* hip_stream, const float* k_scale, const float* v_scale);
+int fa_prefill_paged_kv8_bf16(const void* q, const void* k_pages, const void* v_pages, void* o,
+                              float* lse, int batch, int heads_q, int heads_kv, int seqlen_q,
+                              int head_dim, int num_pages, int page_size, const int* block_table,
+                              int max_pages_per_seq, const int* kv_lens, const int* q_lens, int causal,
+                              void* hip_stream, const float* k_scale, const float* v_scale);
+
 /* The dispatcher's decision (ref tier table :620-661): config id used by
  * fa_fwd_f16 for this shape.  The _ws entries may run the causal split tier
  * instead: check fa_fwd_split_pieces() first (> 0: the split tier runs with
