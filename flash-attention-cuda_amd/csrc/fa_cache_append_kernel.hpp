@@ -38,6 +38,7 @@
 #pragma once
 
 #include "fa_fwd_kernel.hpp"
+#include "fa_varlen_map.hpp"
 
 namespace fa {
 
@@ -97,8 +98,34 @@ __device__ __forceinline__ u32x2 append_cvt_fp8x8(u32x4 raw, float rcp) {
 // reads); a 16-bit cache takes a bit copy, one instantiation (T = unsigned
 // short) for both types.  Grid: x = token blocks, y over K/V heads, z over
 // the batch (both strided, so either may exceed the grid limit).
+//
+// The packed entries (fa_cache_append_varlen_*) name their source PackedSrc<T>:
+// the kernel takes VARLEN from that, so the padded entries' instantiations
+// (and their symbols) are what they were.  k_new / v_new are then token-major
+// [T][Hkv][D] and the fields of p are read as
+//   new_lens = cu_seqlens (int32[B + 1], required), sn = T, batch = B
+// Grid: x = virtual block ids (fa_varlen_map.hpp at append_block_tokens()
+// granularity: a workgroup's tokens, so every wave's, belong to ONE sequence
+// and len, n, the page pair and the scales stay wave-uniform), y over K/V
+// heads, no z.  Token t of sequence b is packed row s_b + t; source rows are
+// Hkv * SROW bytes apart.
+template <class T>
+struct PackedSrc {};
+template <class T>
+struct AppendSrc {
+  typedef T elem;
+  static constexpr bool packed = false;
+};
+template <class T>
+struct AppendSrc<PackedSrc<T>> {
+  typedef T elem;
+  static constexpr bool packed = true;
+};
+
 template <class T, int HDIM, bool PAGED, bool KV8>
 __global__ __launch_bounds__(256) void fa_cache_append_kernel(AppendParams p) {
+  constexpr bool VARLEN = AppendSrc<T>::packed;
+  using E = typename AppendSrc<T>::elem;
   constexpr int LPR = HDIM / 8;         // lanes per row
   constexpr int RPW = 64 / LPR;         // rows per wave instruction
   constexpr int WROWS = kAppendU * RPW; // consecutive tokens of one wave (16 or 32)
@@ -110,15 +137,33 @@ __global__ __launch_bounds__(256) void fa_cache_append_kernel(AppendParams p) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lr = lane / LPR, piece = lane % LPR;
-  const long long tw = (long long)blockIdx.x * (4 * WROWS) + wave * WROWS;  // the wave's first token
+  // VARLEN: the workgroup's sequence, its first packed row, its tokens and the block within it
+  [[maybe_unused]] int vb = 0, seq0 = 0, seqn = 0, vr = 0;
+  if constexpr (VARLEN) {
+    if (!varlen_block<4 * WROWS>(p.new_lens, p.batch, p.sn, (int)blockIdx.x, vb, seq0, seqn, vr)) return;
+    vb = __builtin_amdgcn_readfirstlane(vb);
+    seq0 = __builtin_amdgcn_readfirstlane(seq0);
+    seqn = __builtin_amdgcn_readfirstlane(seqn);
+    vr = __builtin_amdgcn_readfirstlane(vr);
+  }
+  // the wave's first token
+  const long long tw = (VARLEN ? (long long)vr : (long long)blockIdx.x) * (4 * WROWS) + wave * WROWS;
+  // source: bytes between consecutive tokens
+  [[maybe_unused]] const size_t sstr = VARLEN ? (size_t)p.hkv * SROW : (size_t)SROW;
 
   for (int hk = blockIdx.y; hk < p.hkv; hk += gridDim.y) {
-    for (int b = blockIdx.z; b < p.batch; b += gridDim.z) {
+    // VARLEN: the one sequence of this workgroup
+    for (int b = VARLEN ? vb : (int)blockIdx.z; VARLEN ? b == vb : b < p.batch;
+         b += VARLEN ? 1u : gridDim.z) {
       // the wave-uniform loads first, together: one round trip before the
       // rows are known (two when paged: the table entries need the length)
       int len = p.kv_lens[b], n = p.sn;
       [[maybe_unused]] float ksc = 1.0f, vsc = 1.0f;
-      if (p.new_lens) n = p.new_lens[b];
+      if constexpr (VARLEN) {
+        n = seqn;  // already in [0, sn - seq0]
+      } else {
+        if (p.new_lens) n = p.new_lens[b];
+      }
       if constexpr (KV8) {
         if (p.k_scale) ksc = p.k_scale[hk];
         if (p.v_scale) vsc = p.v_scale[hk];
@@ -152,7 +197,8 @@ __global__ __launch_bounds__(256) void fa_cache_append_kernel(AppendParams p) {
             float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, 1.0f / vsc)));
       }
       const size_t bh = (size_t)b * p.hkv + hk;
-      const size_t soff = (bh * p.sn + t0) * SROW + piece * 16;
+      const size_t soff = VARLEN ? (((size_t)seq0 + t0) * p.hkv + hk) * SROW + piece * 16
+                                 : (bh * p.sn + t0) * SROW + piece * 16;
       const char* ks = static_cast<const char*>(p.k_new) + soff;
       const char* vs = static_cast<const char*>(p.v_new) + soff;
 
@@ -168,8 +214,8 @@ __global__ __launch_bounds__(256) void fa_cache_append_kernel(AppendParams p) {
         }
         kx[u] = vx[u] = u32x4{0, 0, 0, 0};
         if (ok[u]) {
-          kx[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(ks + (size_t)u * RPW * SROW));
-          vx[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(vs + (size_t)u * RPW * SROW));
+          kx[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(ks + (size_t)u * RPW * sstr));
+          vx[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(vs + (size_t)u * RPW * sstr));
         }
       }
 #pragma unroll
@@ -187,8 +233,8 @@ __global__ __launch_bounds__(256) void fa_cache_append_kernel(AppendParams p) {
         char* kd = static_cast<char*>(p.k_cache) + doff;
         char* vd = static_cast<char*>(p.v_cache) + doff;
         if constexpr (KV8) {
-          __builtin_nontemporal_store(append_cvt_fp8x8<T>(kx[u], krcp), reinterpret_cast<u32x2*>(kd));
-          __builtin_nontemporal_store(append_cvt_fp8x8<T>(vx[u], vrcp), reinterpret_cast<u32x2*>(vd));
+          __builtin_nontemporal_store(append_cvt_fp8x8<E>(kx[u], krcp), reinterpret_cast<u32x2*>(kd));
+          __builtin_nontemporal_store(append_cvt_fp8x8<E>(vx[u], vrcp), reinterpret_cast<u32x2*>(vd));
         } else {
           __builtin_nontemporal_store(kx[u], reinterpret_cast<u32x4*>(kd));
           __builtin_nontemporal_store(vx[u], reinterpret_cast<u32x4*>(vd));

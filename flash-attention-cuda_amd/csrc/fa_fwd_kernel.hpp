@@ -334,13 +334,15 @@ struct M16 {
     have_ref = false;
   }
   // Q: qf[b][t] = c * Q[qw + 16b + r16][32t + 8g .. +7]   (rounded to fp16)
-  __device__ __forceinline__ void issue_q(__amdgpu_buffer_rsrc_t rq, int qw) {
+  // rs: bytes between consecutive rows (token-major Q of the packed prefill
+  // entries, fa_prefill_kernel.hpp: heads_q * ROW); the default is head-major
+  __device__ __forceinline__ void issue_q(__amdgpu_buffer_rsrc_t rq, int qw, int rs = ROW) {
 #pragma unroll
     for (int b = 0; b < QB; ++b)
 #pragma unroll
       for (int t = 0; t < NTQ; ++t)
         qf[b][t] = __builtin_bit_cast(
-            tx8, buf_load16(rq, (qw + 16 * b + r16) * ROW + (4 * t + g) * 16));
+            tx8, buf_load16(rq, (qw + 16 * b + r16) * rs + (4 * t + g) * 16));
   }
   __device__ __forceinline__ void scale_q() {
     if constexpr (kScaleS) {
@@ -591,13 +593,15 @@ struct M16 {
   // issue-bound (guide T21).
   // row blocks [B0, B1), d-block pairs [EP0, EP1) (symmetric merges store a part each)
   // osc: a factor on the normalisation (the FP8 cache's V scale, fa_prefill_kernel.hpp)
+  // rs: bytes between consecutive rows, as for issue_q
   template <int B0 = 0, int B1 = QB, int EP0 = 0, int EP1 = NE / 2>
-  __device__ __forceinline__ void store_o(__amdgpu_buffer_rsrc_t ro, int qw, float osc = 1.0f) {
+  __device__ __forceinline__ void store_o(__amdgpu_buffer_rsrc_t ro, int qw, float osc = 1.0f,
+                                          int rs = ROW) {
 #pragma unroll
     for (int b = B0; b < B1; ++b) {
       const float lt = row_sum(b);  // already the full row sum (MFMA over all keys)
       const float inv = (lt > 0.f ? 1.0f / lt : 0.f) * osc;
-      const int rowb = (qw + 16 * b + r16) * ROW;
+      const int rowb = (qw + 16 * b + r16) * rs;
       const int dlane = 16 * (g & 1) + 8 * (g >> 1);
 #pragma unroll
       for (int ep = EP0; ep < EP1; ++ep) {

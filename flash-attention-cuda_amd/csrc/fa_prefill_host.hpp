@@ -11,10 +11,17 @@
 
 namespace fa {
 
-template <class T, int HDIM, bool PAGED, bool KV8, class P>
+template <class T, int HDIM, bool PAGED, bool KV8, bool VARLEN, class P>
 static int prefill_launch_inst(const P& p, unsigned grid, hipStream_t stream) {
   using KV = std::conditional_t<KV8, unsigned char, T>;
-  hipLaunchKernelGGL((fa_prefill_kernel<T, HDIM, PAGED, P, KV>), dim3(grid), dim3(256), 0, stream, p);
+  if constexpr (VARLEN) {
+    PrefillPacked<P> pp;
+    static_cast<P&>(pp) = p;
+    hipLaunchKernelGGL((fa_prefill_kernel<T, HDIM, PAGED, PrefillPacked<P>, KV>), dim3(grid), dim3(256), 0,
+                       stream, pp);
+  } else {
+    hipLaunchKernelGGL((fa_prefill_kernel<T, HDIM, PAGED, P, KV>), dim3(grid), dim3(256), 0, stream, p);
+  }
   return hipGetLastError() == hipSuccess ? FA_OK : FA_ERR_LAUNCH;
 }
 
@@ -23,7 +30,12 @@ static int prefill_launch_inst(const P& p, unsigned grid, hipStream_t stream) {
 // page_size; otherwise `pg` is unused.  KV8: the cache holds E4M3 bytes and
 // k_scale / v_scale go to the kernel; otherwise they are unused.  The checks
 // come in decode_entry's order; everything is returned before any launch.
-template <bool PAGED, bool KV8>
+// VARLEN (the fa_prefill_varlen_* entries, fa_prefill_varlen*.hip): q and o are
+// packed token-major [total_q][heads_q][head_dim], lse [heads_q][total_q];
+// `seqlen_q` is total_q, `q_lens` is cu_seqlens (int32[batch + 1], required)
+// and `batch` the number of sequences.  The grid is sized from shapes alone:
+// heads_q * (total_q / 128 + batch) workgroups (fa_varlen_map.hpp).
+template <bool PAGED, bool KV8, bool VARLEN = false>
 static int prefill_entry(int dtype, const void* q, const void* k, const void* v, void* o, float* lse,
                          int batch, int heads_q, int heads_kv, int seqlen_q, int kv_capacity,
                          int head_dim, const DecodePages& pg, const int* kv_lens, const int* q_lens,
@@ -33,7 +45,7 @@ static int prefill_entry(int dtype, const void* q, const void* k, const void* v,
   if (batch < 0 || heads_q < 0 || heads_kv < 0 || kv_capacity < 0 || head_dim < 0)
     return FA_ERR_BAD_SHAPE;
   if (head_dim != 128 && head_dim != 64) return FA_ERR_UNSUPPORTED_HEAD_DIM;
-  if (seqlen_q < 1) return FA_ERR_BAD_SHAPE;
+  if (VARLEN ? seqlen_q < 0 : seqlen_q < 1) return FA_ERR_BAD_SHAPE;
   if constexpr (PAGED) {
     // a 64-key tile must not straddle two pages
     if (pg.page_size <= 0 || pg.page_size % 64 != 0) return FA_ERR_BAD_SHAPE;
@@ -45,26 +57,36 @@ static int prefill_entry(int dtype, const void* q, const void* k, const void* v,
     if ((long long)pg.max_pages_per_seq * pg.page_size > 0x7fffffffLL - 64) return FA_ERR_BAD_SHAPE;
     kv_capacity = pg.max_pages_per_seq * pg.page_size;
   }
-  if (batch == 0 || heads_q == 0) return FA_OK;
+  if (batch == 0 || heads_q == 0 || (VARLEN && seqlen_q == 0)) return FA_OK;
   if (heads_kv == 0 || heads_q % heads_kv != 0) return FA_ERR_BAD_SHAPE;
   // LSE rows and the rows of one head's Q / O (one buffer resource) are 32-bit
-  if ((long long)batch * heads_q * seqlen_q > 0x7fffffffLL) return FA_ERR_BAD_SHAPE;
-  if ((long long)seqlen_q * 2 * head_dim > 0x7fffffffLL) return FA_ERR_BAD_SHAPE;
+  if constexpr (VARLEN) {
+    // LSE rows, and the byte range of one block's token-major Q / O rows
+    if ((long long)heads_q * seqlen_q > 0x7fffffffLL) return FA_ERR_BAD_SHAPE;
+    if ((long long)kPrefillBM * heads_q * 2 * head_dim > 0x7fffffffLL) return FA_ERR_BAD_SHAPE;
+  } else {
+    if ((long long)batch * heads_q * seqlen_q > 0x7fffffffLL) return FA_ERR_BAD_SHAPE;
+    if ((long long)seqlen_q * 2 * head_dim > 0x7fffffffLL) return FA_ERR_BAD_SHAPE;
+  }
   if constexpr (!PAGED) {
     // a head's cache rows are addressed through one buffer resource whose byte
     // range (cap * 2 * head_dim) is a 32-bit int (FP8: the same capacities)
     if ((long long)kv_capacity * 2 * head_dim > 0x7fffffffLL) return FA_ERR_BAD_SHAPE;
   }
-  const int nqb = (seqlen_q + kPrefillBM - 1) / kPrefillBM;
-  if ((long long)batch * heads_q * nqb > 0x7fffffffLL) return FA_ERR_BAD_SHAPE;
+  // VARLEN: virtual block ids per head; the padded entries: query blocks per head and element
+  const long long nqb = VARLEN ? (long long)seqlen_q / kPrefillBM + batch
+                               : (seqlen_q + kPrefillBM - 1) / kPrefillBM;
+  const long long nwg = (VARLEN ? 1LL : (long long)batch) * heads_q * nqb;
+  if (nqb > 0x7fffffffLL || nwg > 0x7fffffffLL) return FA_ERR_BAD_SHAPE;
   hipStream_t stream = (hipStream_t)hip_stream;
   if (kv_capacity == 0) {
     // rows but no keys: O = 0, LSE = -inf for every row; nothing else runs
     if (!o) return FA_ERR_NULL_POINTER;
-    return decode_fill_empty(o, lse, (size_t)batch * heads_q * seqlen_q, head_dim, stream) ? FA_OK
-                                                                                            : FA_ERR_HIP;
+    const size_t nrow = (VARLEN ? (size_t)1 : (size_t)batch) * heads_q * seqlen_q;
+    return decode_fill_empty(o, lse, nrow, head_dim, stream) ? FA_OK : FA_ERR_HIP;
   }
-  if (!q || !k || !v || !o || (PAGED && !pg.block_table)) return FA_ERR_NULL_POINTER;
+  if (!q || !k || !v || !o || (PAGED && !pg.block_table) || (VARLEN && !q_lens))
+    return FA_ERR_NULL_POINTER;
   P p = {};
   p.q = q;
   p.k = k;
@@ -78,7 +100,7 @@ static int prefill_entry(int dtype, const void* q, const void* k, const void* v,
   p.sq = seqlen_q;
   p.cap = kv_capacity;
   p.group = heads_q / heads_kv;
-  p.nqb = nqb;
+  p.nqb = VARLEN ? batch : (int)nqb;  // VARLEN: the kernel takes the sequence count here
   p.bhk = (unsigned)batch * (unsigned)heads_kv;
   p.causal = causal ? 1 : 0;
   p.c = 1.4426950408889634f / sqrtf((float)head_dim);
@@ -95,12 +117,12 @@ static int prefill_entry(int dtype, const void* q, const void* k, const void* v,
     p.k_scale = k_scale;
     p.v_scale = v_scale;
   }
-  const unsigned grid = (unsigned)((long long)batch * heads_q * nqb);
+  const unsigned grid = (unsigned)nwg;
   if (dtype == FA_DTYPE_BF16)
-    return head_dim == 128 ? prefill_launch_inst<__bf16, 128, PAGED, KV8>(p, grid, stream)
-                           : prefill_launch_inst<__bf16, 64, PAGED, KV8>(p, grid, stream);
-  return head_dim == 128 ? prefill_launch_inst<f16, 128, PAGED, KV8>(p, grid, stream)
-                         : prefill_launch_inst<f16, 64, PAGED, KV8>(p, grid, stream);
+    return head_dim == 128 ? prefill_launch_inst<__bf16, 128, PAGED, KV8, VARLEN>(p, grid, stream)
+                           : prefill_launch_inst<__bf16, 64, PAGED, KV8, VARLEN>(p, grid, stream);
+  return head_dim == 128 ? prefill_launch_inst<f16, 128, PAGED, KV8, VARLEN>(p, grid, stream)
+                         : prefill_launch_inst<f16, 64, PAGED, KV8, VARLEN>(p, grid, stream);
 }
 
 }  // namespace fa

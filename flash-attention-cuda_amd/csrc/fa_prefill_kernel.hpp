@@ -47,6 +47,7 @@
 #pragma once
 
 #include "fa_decode_kernel.hpp"
+#include "fa_varlen_map.hpp"
 
 namespace fa {
 
@@ -88,8 +89,32 @@ struct PrefillPagedKv8Params : PrefillPagedParams {
   const float* v_scale;
 };
 
+// The packed entries (fa_prefill_varlen_*) pass their parameters as
+// PrefillPacked<one of the four above>: the kernel below takes VARLEN from the
+// type, so the padded entries' instantiations (and their symbols) are what
+// they were.  q and o are then token-major [T][Hq][D], lse [Hq][T], and the
+// fields are read as
+//   q_lens = cu_seqlens (int32[B + 1], required), sq = T, nqb = B;  bhk unused
+// A workgroup is (virtual block id, query head): fa_varlen_map.hpp gives it
+// sequence b, its first packed row s_b and its n_b rows, and block r of b is
+// query block qb = r of the padded kernel's element b -- the same tile
+// sequence, so the same bits.  Q / O rows are Hq * ROW bytes apart: the
+// block's descriptor starts at row s_b + q0 of head hq and ends with the last
+// valid row's own ROW bytes, so the range check still zero-fills and drops
+// the rows past n_b.  A global heaviest-first order of causal blocks needs the
+// lengths before the launch and is not done; causal launches take the ids
+// from the top instead, which starts every sequence's blocks last (most keys)
+// to first at no cost.
+template <class Base>
+struct PrefillPacked : Base {};
+template <class P>
+struct PrefillIsPacked : std::false_type {};
+template <class Base>
+struct PrefillIsPacked<PrefillPacked<Base>> : std::true_type {};
+
 template <class T, int HDIM, bool PAGED = false, class P = PrefillParams, class KV = T>
 __global__ __launch_bounds__(256, 2) void fa_prefill_kernel(P p) {
+  constexpr bool VARLEN = PrefillIsPacked<P>::value;
   __shared__ __attribute__((aligned(16))) char smem[kPrefillLdsBytes];
   constexpr bool KV8 = !std::is_same<KV, T>::value;
   static_assert(!KV8 || std::is_same<KV, unsigned char>::value, "the cache holds T or E4M3 bytes");
@@ -115,14 +140,34 @@ __global__ __launch_bounds__(256, 2) void fa_prefill_kernel(P p) {
   // causal blocks heaviest first
   const unsigned gi = blockIdx.x % (unsigned)p.group;
   const unsigned rest = blockIdx.x / (unsigned)p.group;
-  const unsigned bhk = rest % p.bhk;
-  const int qbr = (int)(rest / p.bhk);
-  const int qb = p.causal ? p.nqb - 1 - qbr : qbr;
-  const int b = (int)(bhk / (unsigned)p.hkv), hk = (int)(bhk - (unsigned)b * p.hkv);
-  const int hq = hk * p.group + (int)gi;
-
-  int nq = p.q_lens ? p.q_lens[b] : p.sq;
-  nq = __builtin_amdgcn_readfirstlane(min(max(nq, 0), p.sq));
+  unsigned bhk;
+  int qb, b, hk, hq, nq;
+  [[maybe_unused]] int s0 = 0;  // VARLEN: the sequence's first packed row
+  if constexpr (VARLEN) {
+    // (virtual block id, kv head, head of the group): the id's sequence and
+    // block by bisection on cu (wave-uniform scalar loads)
+    hk = (int)(rest % (unsigned)p.hkv);
+    // causal: the ids are taken from the top, so each sequence's blocks start
+    // in the order last (most keys) to first and the launch ends on light
+    // blocks; the order BETWEEN sequences stays the packing order
+    int id = (int)(rest / (unsigned)p.hkv);
+    if (p.causal) id = p.sq / BM + p.nqb - 1 - id;
+    if (!varlen_block<BM>(p.q_lens, p.nqb, p.sq, id, b, s0, nq, qb)) return;
+    b = __builtin_amdgcn_readfirstlane(b);
+    s0 = __builtin_amdgcn_readfirstlane(s0);
+    nq = __builtin_amdgcn_readfirstlane(nq);
+    qb = __builtin_amdgcn_readfirstlane(qb);
+    bhk = (unsigned)b * (unsigned)p.hkv + (unsigned)hk;
+    hq = hk * p.group + (int)gi;
+  } else {
+    bhk = rest % p.bhk;
+    const int qbr = (int)(rest / p.bhk);
+    qb = p.causal ? p.nqb - 1 - qbr : qbr;
+    b = (int)(bhk / (unsigned)p.hkv), hk = (int)(bhk - (unsigned)b * p.hkv);
+    hq = hk * p.group + (int)gi;
+    nq = p.q_lens ? p.q_lens[b] : p.sq;
+    nq = __builtin_amdgcn_readfirstlane(min(max(nq, 0), p.sq));
+  }
   const int q0 = qb * BM;
   if (q0 >= nq) return;  // nothing of this block is valid: nothing is written
   int len = p.kv_lens ? p.kv_lens[b] : p.cap;
@@ -134,10 +179,26 @@ __global__ __launch_bounds__(256, 2) void fa_prefill_kernel(P p) {
   const int qwm = p.causal ? off + q0 + wave * RW : 0x3fffffff;
   const int qwl = wave * RW;  // this wave's first row within the block's descriptors
 
-  const size_t qrow0 = ((size_t)b * p.hq + hq) * (size_t)p.sq + q0;
-  const int qrows = nq - q0;  // valid rows from the block's first on (may exceed 128)
-  const __amdgpu_buffer_rsrc_t rq = make_rsrc(static_cast<const char*>(p.q) + qrow0 * ROW, qrows * ROW);
-  const __amdgpu_buffer_rsrc_t ro = make_rsrc(static_cast<char*>(p.o) + qrow0 * ROW, qrows * ROW);
+  // qrow0: the block's first row in units of ROW bytes (Q, O) and, as lrow0,
+  // of LSE floats; qs: bytes between its consecutive rows
+  size_t qrow0, lrow0;
+  int qrows, qs;
+  if constexpr (VARLEN) {
+    qrow0 = ((size_t)s0 + q0) * (size_t)p.hq + hq;
+    lrow0 = (size_t)hq * (size_t)p.sq + s0 + q0;
+    qrows = min(nq - q0, BM);
+    qs = p.hq * ROW;
+  } else {
+    qrow0 = lrow0 = ((size_t)b * p.hq + hq) * (size_t)p.sq + q0;
+    qrows = nq - q0;  // valid rows from the block's first on (may exceed 128)
+    qs = ROW;
+  }
+  // the range ends with the last valid row's own bytes (VARLEN: <= 127 * Hq *
+  // ROW + ROW, which the host checks fits)
+  const __amdgpu_buffer_rsrc_t rq = make_rsrc(static_cast<const char*>(p.q) + qrow0 * ROW,
+                                              VARLEN ? (qrows - 1) * qs + ROW : qrows * ROW);
+  const __amdgpu_buffer_rsrc_t ro = make_rsrc(static_cast<char*>(p.o) + qrow0 * ROW,
+                                              VARLEN ? (qrows - 1) * qs + ROW : qrows * ROW);
 
   // score scale: the cache's K scale rides on it (a wave-uniform load)
   float csc = p.c;
@@ -149,7 +210,7 @@ __global__ __launch_bounds__(256, 2) void fa_prefill_kernel(P p) {
 
   Pol pol;
   pol.init(lane, csc);
-  pol.issue_q(rq, qwl);  // scaled once tile 0's loads are in flight
+  pol.issue_q(rq, qwl, qs);  // scaled once tile 0's loads are in flight
 
   // Staging.  16-bit: the policy's lanes (K natural row-major, V two rows of
   // opposite parity x 4 chunks per 8 lanes).  FP8: a lane holds a 16-byte
@@ -288,9 +349,9 @@ __global__ __launch_bounds__(256, 2) void fa_prefill_kernel(P p) {
   }
   if (j < ntiles) step(j, std::integral_constant<int, 0>{});
 
-  pol.store_o(ro, qwl, vsc);
+  pol.store_o(ro, qwl, vsc, qs);
   if (p.lse) {
-    const __amdgpu_buffer_rsrc_t rl = make_rsrc(p.lse + qrow0, qrows * 4);
+    const __amdgpu_buffer_rsrc_t rl = make_rsrc(p.lse + lrow0, qrows * 4);
 #pragma unroll
     for (int bb = 0; bb < Pol::QB; ++bb) {
       const float l = pol.row_sum(bb);

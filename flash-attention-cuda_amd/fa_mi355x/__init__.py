@@ -72,6 +72,20 @@ EXPORTED_SYMBOLS = (
     "fa_prefill_kv8_bf16",
     "fa_prefill_paged_kv8_f16",
     "fa_prefill_paged_kv8_bf16",
+    "fa_prefill_varlen_f16",
+    "fa_prefill_varlen_bf16",
+    "fa_prefill_varlen_paged_f16",
+    "fa_prefill_varlen_paged_bf16",
+    "fa_prefill_varlen_kv8_f16",
+    "fa_prefill_varlen_kv8_bf16",
+    "fa_prefill_varlen_paged_kv8_f16",
+    "fa_prefill_varlen_paged_kv8_bf16",
+    "fa_cache_append_varlen_16",
+    "fa_cache_append_varlen_paged_16",
+    "fa_cache_append_varlen_kv8_f16",
+    "fa_cache_append_varlen_kv8_bf16",
+    "fa_cache_append_varlen_paged_kv8_f16",
+    "fa_cache_append_varlen_paged_kv8_bf16",
     "fa_select_config",
     "fa_num_configs",
     "fa_config_info",
@@ -191,6 +205,13 @@ def load_library() -> ctypes.CDLL:
         fn.argtypes = lib.fa_cache_append_16.argtypes + [vp, vp]
     for fn in (lib.fa_cache_append_paged_kv8_f16, lib.fa_cache_append_paged_kv8_bf16):
         fn.argtypes = lib.fa_cache_append_paged_16.argtypes + [vp, vp]
+    # the packed (cu_seqlens) twins take the same argument lists
+    lib.fa_cache_append_varlen_16.argtypes = lib.fa_cache_append_16.argtypes
+    lib.fa_cache_append_varlen_paged_16.argtypes = lib.fa_cache_append_paged_16.argtypes
+    for fn in (lib.fa_cache_append_varlen_kv8_f16, lib.fa_cache_append_varlen_kv8_bf16):
+        fn.argtypes = lib.fa_cache_append_kv8_f16.argtypes
+    for fn in (lib.fa_cache_append_varlen_paged_kv8_f16, lib.fa_cache_append_varlen_paged_kv8_bf16):
+        fn.argtypes = lib.fa_cache_append_paged_kv8_f16.argtypes
     for name in EXPORTED_SYMBOLS:
         if name.startswith("fa_cache_append"):
             getattr(lib, name).restype = i
@@ -202,6 +223,10 @@ def load_library() -> ctypes.CDLL:
         fn.argtypes = lib.fa_prefill_f16.argtypes + [vp, vp]
     for fn in (lib.fa_prefill_paged_kv8_f16, lib.fa_prefill_paged_kv8_bf16):
         fn.argtypes = lib.fa_prefill_paged_f16.argtypes + [vp, vp]
+    for form in ("", "_paged", "_kv8", "_paged_kv8"):
+        for ty in ("_f16", "_bf16"):
+            getattr(lib, "fa_prefill_varlen" + form + ty).argtypes = \
+                getattr(lib, "fa_prefill" + form + ty).argtypes
     for name in EXPORTED_SYMBOLS:
         if name.startswith("fa_prefill"):
             getattr(lib, name).restype = i
@@ -474,15 +499,29 @@ def _check_decode_head(q, kname, k, vname, v, out, k_scale, v_scale, layout):
     return kv8
 
 
+def _check_table_type(block_table):
+    import torch
+
+    if block_table.dtype != torch.int32:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE,
+                                  f"block_table must be int32, got {block_table.dtype}")
+    if block_table.dim() != 2:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, "block_table must be 2-D [B, max_pages_per_seq]")
+
+
 def _check_decode_tail(q, kname, k, vname, v, out, k_scale, v_scale, block_table, kv_lens,
-                       qname="q", oname="out"):
+                       qname="q", oname="out", batch=None):
     """What both decode checks end with, after the family's own shape checks:
     Hq % Hkv, each scale (if given) a contiguous float32 [Hkv] tensor, the
     block table (paged only: None otherwise), kv_lens, and then where all of
     them live.  The append checks end with it too, with k_new and v_new
-    (`qname`, `oname`) in the places of q and out."""
+    (`qname`, `oname`) in the places of q and out.  `batch`: the number of
+    sequences where q's first extent is not it (the packed wrappers, whose q is
+    [T,Hq,D]: heads are extent 1 there too)."""
     import torch
 
+    if batch is None:
+        batch = q.shape[0]
     heads_kv = k.shape[1]
     if heads_kv == 0 or q.shape[1] % heads_kv != 0:
         raise FlashAttentionError(FA_ERR_BAD_SHAPE,
@@ -497,21 +536,17 @@ def _check_decode_tail(q, kname, k, vname, v, out, k_scale, v_scale, block_table
                 FA_ERR_BAD_SHAPE,
                 f"{name} must be a contiguous float32 [Hkv = {heads_kv}] tensor, got {got}")
     if block_table is not None:
-        if block_table.dtype != torch.int32:
-            raise FlashAttentionError(FA_ERR_BAD_SHAPE,
-                                      f"block_table must be int32, got {block_table.dtype}")
-        if block_table.dim() != 2:
-            raise FlashAttentionError(FA_ERR_BAD_SHAPE, "block_table must be 2-D [B, max_pages_per_seq]")
-        if block_table.shape[0] != q.shape[0]:
+        _check_table_type(block_table)
+        if block_table.shape[0] != batch:
             raise FlashAttentionError(
                 FA_ERR_BAD_SHAPE,
-                f"block_table has {block_table.shape[0]} rows, {qname} a batch of {q.shape[0]}")
+                f"block_table has {block_table.shape[0]} rows, {qname} a batch of {batch}")
         if not block_table.is_contiguous():
             raise FlashAttentionError(FA_ERR_BAD_SHAPE, "block_table must be contiguous")
     if kv_lens is not None:
         if kv_lens.dtype != torch.int32:
             raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"kv_lens must be int32, got {kv_lens.dtype}")
-        if kv_lens.dim() != 1 or kv_lens.shape[0] != q.shape[0] or not kv_lens.is_contiguous():
+        if kv_lens.dim() != 1 or kv_lens.shape[0] != batch or not kv_lens.is_contiguous():
             raise FlashAttentionError(FA_ERR_BAD_SHAPE, "kv_lens must be a contiguous [B] tensor")
     for name, t in ((qname, q), (kname, k), (vname, v), (oname, out)):
         if not t.is_cuda:
@@ -944,6 +979,218 @@ def flash_attention_cache_append_paged(k_new, v_new, k_pages, v_pages, block_tab
                         new_lens, k_scale, v_scale)
     _append_call(kv8, k_new, v_new, k_pages, v_pages, block_table, kv_lens, new_lens, stream, k_scale,
                  v_scale)
+
+
+def _check_cu_seqlens(cu, name, nseq, ref, where):
+    """The packed wrappers' cu_seqlens, worded like q_lens / new_lens: presence,
+    dtype and shape (`where` false, before the tensors' devices are looked at),
+    then its device (`where` true).  Its VALUES are not looked at (no sync)."""
+    if where:
+        if not cu.is_cuda or cu.device != ref.device:
+            raise FlashAttentionError(FA_ERR_NULL_POINTER, f"{name} must be a tensor on {ref.device}")
+        return
+    import torch
+
+    if cu is None:
+        raise FlashAttentionError(
+            FA_ERR_NULL_POINTER,
+            f"{name} is required: the int32 [B + 1] prefix sum of the sequences' token counts")
+    if cu.dtype != torch.int32:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be int32, got {cu.dtype}")
+    if cu.dim() != 1 or cu.shape[0] != nseq + 1 or not cu.is_contiguous():
+        raise FlashAttentionError(
+            FA_ERR_BAD_SHAPE,
+            f"{name} must be a contiguous [B + 1 = {nseq + 1}] tensor, got {list(cu.shape)}")
+
+
+def _check_packed(x, xname, y, yname, kname, k, vname, v, block_table, cu, cuname, kv_lens, k_scale,
+                  v_scale, need_kv_lens):
+    """What the four packed wrappers check.  x, y: q and out [T,Hq,D] (prefill)
+    or k_new and v_new [T,Hkv,D] (append), contiguous, of one 16-bit dtype and
+    shape; the caches (`kname`, `vname`: [B,Hkv,cap,D], or with a block table
+    the pools [num_pages,Hkv,page_size,D]) of that dtype or both
+    torch.float8_e4m3fn (returns True then); B is the caches' batch, or the
+    table's rows; cu int32 [B + 1]; the rest as :func:`_check_decode_tail`
+    takes it.  Dtypes, ranks and shapes come before where the tensors live."""
+    import torch
+
+    paged = block_table is not None
+    if x.dtype not in (torch.float16, torch.bfloat16):
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE,
+                                  f"{xname} must be float16 or bfloat16, got {x.dtype}")
+    kv8 = _kv8_caches(x, kname, k, vname, v, k_scale, v_scale)
+    for name, t, rank, layout in ((xname, x, 3, " [T,H,D]"), (yname, y, 3, " [T,H,D]"),
+                                  (kname, k, 4, "" if paged else " (BHSD)"),
+                                  (vname, v, 4, "" if paged else " (BHSD)")):
+        if t.dtype != x.dtype and not (kv8 and rank == 4):
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be {x.dtype}, got {t.dtype}")
+        if t.dim() != rank:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be {rank}-D{layout}")
+        if not t.is_contiguous():
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be contiguous{layout}")
+    if y.shape != x.shape:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{yname} must be [T,H,D] like {xname}")
+    if k.shape != v.shape:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{kname} and {vname} must have one shape")
+    if k.shape[3] != x.shape[2]:
+        raise FlashAttentionError(
+            FA_ERR_BAD_SHAPE,
+            f"{xname} and the {'page pools' if paged else 'caches'} must agree in head_dim")
+    if need_kv_lens and k.shape[1] != x.shape[1]:
+        raise FlashAttentionError(
+            FA_ERR_BAD_SHAPE,
+            f"{xname} and the {'page pools' if paged else 'caches'} must agree in heads_kv")
+    if paged:
+        if k.shape[0] == 0:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, "the page pools hold no page")
+        if k.shape[2] == 0 or k.shape[2] % 64 != 0:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE,
+                                      f"page_size {k.shape[2]} is not a positive multiple of 64")
+        _check_table_type(block_table)
+        nseq = block_table.shape[0]
+    else:
+        nseq = k.shape[0]
+    if need_kv_lens and kv_lens is None:
+        raise FlashAttentionError(
+            FA_ERR_NULL_POINTER,
+            "kv_lens is required: the int32 [B] lengths after the append (what decode takes next)")
+    _check_cu_seqlens(cu, cuname, nseq, x, False)
+    _check_decode_tail(x, kname, k, vname, v, y, k_scale, v_scale, block_table, kv_lens,
+                       qname=xname, oname=yname, batch=nseq)
+    _check_cu_seqlens(cu, cuname, nseq, x, True)
+    return kv8, nseq
+
+
+def _packed_call(name, kv8, x, y, extra, nseq, heads, k, v, block_table, kv_lens, cu, mid, stream,
+                 k_scale, v_scale):
+    """The call of the four packed functions after their checks: the stream and
+    the C entry `name`.  x: the first packed tensor (q or k_new); y: the
+    pointers between it and the caches (append: v_new); extra: those between
+    the caches and the counts (prefill: o and lse); heads: the head counts;
+    mid: what stands between cu_seqlens and the stream (prefill: causal)."""
+    import torch
+
+    total, d = x.shape[0], x.shape[2]
+    if block_table is not None:
+        cache = (d, k.shape[0], k.shape[2], block_table.data_ptr(), block_table.shape[1])
+    else:
+        cache = (k.shape[2], d)
+    tail = ()
+    if kv8:
+        tail = (k_scale.data_ptr() if k_scale is not None else None,
+                v_scale.data_ptr() if v_scale is not None else None)
+    dev = x.device.index
+    if stream is None:
+        st = torch._C._cuda_getCurrentRawStream(dev)
+    else:
+        st = stream if isinstance(stream, int) else stream.cuda_stream
+    lib = _lib or load_library()
+    with torch.cuda.device(dev):
+        rc = getattr(lib, name)(x.data_ptr(), *y, k.data_ptr(), v.data_ptr(), *extra, nseq, *heads, total,
+                                *cache, kv_lens.data_ptr() if kv_lens is not None else None,
+                                cu.data_ptr(), *mid, st, *tail)
+    _check(rc)
+
+
+def _prefill_varlen(q, k, v, block_table, names, cu_seqlens_q, kv_lens, causal, out, return_lse, stream,
+                    k_scale, v_scale):
+    import torch
+
+    if out is None:
+        out = torch.empty_like(q)
+    kv8, nseq = _check_packed(q, "q", out, "out", names[0], k, names[1], v, block_table, cu_seqlens_q,
+                              "cu_seqlens_q", kv_lens, k_scale, v_scale, False)
+    total, hq = q.shape[0], q.shape[1]
+    lse = torch.empty((hq, total), dtype=torch.float32, device=q.device) if return_lse else None
+    name = ("fa_prefill_varlen" + ("_paged" if block_table is not None else "") + ("_kv8" if kv8 else "")
+            + ("_bf16" if q.dtype is torch.bfloat16 else "_f16"))
+    _packed_call(name, kv8, q, (), (out.data_ptr(), lse.data_ptr() if return_lse else None), nseq,
+                 (hq, k.shape[1]), k, v, block_table, kv_lens, cu_seqlens_q, (int(bool(causal)),), stream,
+                 k_scale, v_scale)
+    return (out, lse) if return_lse else out
+
+
+def flash_attention_prefill_varlen(q, k_cache, v_cache, cu_seqlens_q, kv_lens=None, causal: bool = True,
+                                   out=None, return_lse: bool = False, stream=None, k_scale=None,
+                                   v_scale=None):
+    """:func:`flash_attention_prefill` for a packed ragged batch
+    (fa_prefill_varlen_f16 / _bf16, or fa_prefill_varlen_kv8_* over an FP8
+    cache): what a serving stack holds after its QKV projection, taken as it
+    is, with no padded copy.
+
+    q: [T, Hq, D], token-major, contiguous: the B sequences' query tokens one
+    after another.  cu_seqlens_q: int32 [B + 1] on q's device, REQUIRED, the
+    prefix sum of the token counts: sequence b is rows [s_b, e_b) with s_b =
+    clamp(cu[b], 0, T), e_b = clamp(cu[b + 1], s_b, T), n_b = e_b - s_b.  B is
+    the caches' batch.  k_cache, v_cache, kv_lens (the lengths AFTER the chunk
+    was appended), causal, the scales: as for :func:`flash_attention_prefill`,
+    with n_b in q_lens' place.  Row s_b + t of the result equals row t of
+    element b of that function on the padded copy BIT FOR BIT.  Rows that
+    belong to no sequence (below cu[0], at or past cu[B]) are not written:
+    unspecified with out=None.  Any contents of cu_seqlens_q are memory-safe
+    (the clamps); if they do not increase the result is unspecified.  Returns
+    out [T, Hq, D], or (out, lse) with lse fp32 [Hq, T] when return_lse.
+    Everything is read on the device: no sync, no workspace, graph-capturable.
+    """
+    return _prefill_varlen(q, k_cache, v_cache, None, ("k_cache", "v_cache"), cu_seqlens_q, kv_lens,
+                           causal, out, return_lse, stream, k_scale, v_scale)
+
+
+def flash_attention_prefill_varlen_paged(q, k_pages, v_pages, block_table, cu_seqlens_q, kv_lens=None,
+                                         causal: bool = True, out=None, return_lse: bool = False,
+                                         stream=None, k_scale=None, v_scale=None):
+    """:func:`flash_attention_prefill_varlen` over the page pools of
+    :func:`flash_attention_prefill_paged` (fa_prefill_varlen_paged_f16 / _bf16,
+    or fa_prefill_varlen_paged_kv8_*).  B is the block table's row count; the
+    result equals the contiguous function's on the gathered cache bit for bit.
+    """
+    if block_table is None:
+        raise FlashAttentionError(FA_ERR_NULL_POINTER, "block_table is required")
+    return _prefill_varlen(q, k_pages, v_pages, block_table, ("k_pages", "v_pages"), cu_seqlens_q,
+                           kv_lens, causal, out, return_lse, stream, k_scale, v_scale)
+
+
+def _append_varlen(k_new, v_new, k, v, block_table, names, cu_seqlens, kv_lens, k_scale, v_scale, stream):
+    import torch
+
+    kv8, nseq = _check_packed(k_new, "k_new", v_new, "v_new", names[0], k, names[1], v, block_table,
+                              cu_seqlens, "cu_seqlens", kv_lens, k_scale, v_scale, True)
+    name = "fa_cache_append_varlen" + ("_paged" if block_table is not None else "")
+    if kv8:
+        name += "_kv8_bf16" if k_new.dtype is torch.bfloat16 else "_kv8_f16"
+    else:
+        name += "_16"
+    _packed_call(name, kv8, k_new, (v_new.data_ptr(),), (), nseq, (k_new.shape[1],), k, v, block_table,
+                 kv_lens, cu_seqlens, (), stream, k_scale, v_scale)
+
+
+def flash_attention_cache_append_varlen(k_new, v_new, k_cache, v_cache, cu_seqlens, kv_lens,
+                                        k_scale=None, v_scale=None, stream=None) -> None:
+    """:func:`flash_attention_cache_append` for a packed ragged batch
+    (fa_cache_append_varlen_16, or fa_cache_append_varlen_kv8_* into an FP8
+    cache).
+
+    k_new, v_new: [T, Hkv, D], token-major, contiguous.  cu_seqlens: int32
+    [B + 1], REQUIRED, read as :func:`flash_attention_prefill_varlen` reads
+    cu_seqlens_q; B is the caches' batch.  kv_lens: int32 [B], REQUIRED, the
+    lengths AFTER the append.  Token t of sequence b goes to cache row
+    kv_lens[b] - n_b + t, written iff that row exists; the bytes, the FP8
+    contract and "nothing else is touched" are the padded function's.  Read on
+    the device: no sync, no workspace, graph-capturable.  Returns None.
+    """
+    _append_varlen(k_new, v_new, k_cache, v_cache, None, ("k_cache", "v_cache"), cu_seqlens, kv_lens,
+                   k_scale, v_scale, stream)
+
+
+def flash_attention_cache_append_varlen_paged(k_new, v_new, k_pages, v_pages, block_table, cu_seqlens,
+                                              kv_lens, k_scale=None, v_scale=None, stream=None) -> None:
+    """:func:`flash_attention_cache_append_varlen` into the page pools of
+    :func:`flash_attention_cache_append_paged` (fa_cache_append_varlen_paged_16
+    / _paged_kv8_*); B is the block table's row count.  Returns None."""
+    if block_table is None:
+        raise FlashAttentionError(FA_ERR_NULL_POINTER, "block_table is required")
+    _append_varlen(k_new, v_new, k_pages, v_pages, block_table, ("k_pages", "v_pages"), cu_seqlens,
+                   kv_lens, k_scale, v_scale, stream)
 
 
 def splitkv_buffers(batch: int, heads: int, seq_len: int, num_splits: int, device="cuda"):

@@ -10,6 +10,10 @@ rank 3: the wrapper that puts the kernel beside PyTorch SDPA on one box).
     torch.ops.fa_mi355x.cache_append_paged(k_new, v_new, k_pages, v_pages, block_table, kv_lens)
     o = torch.ops.fa_mi355x.prefill(q, k_cache, v_cache, kv_lens, q_lens, causal=True)  # any Sq
     o = torch.ops.fa_mi355x.prefill_paged(q, k_pages, v_pages, block_table, kv_lens, q_lens)
+    o = torch.ops.fa_mi355x.prefill_varlen(q_packed, k_cache, v_cache, cu_seqlens_q, kv_lens)  # [T,Hq,D]
+    o = torch.ops.fa_mi355x.prefill_varlen_paged(q_packed, k_pages, v_pages, block_table, cu_seqlens_q, kv_lens)
+    torch.ops.fa_mi355x.cache_append_varlen(k_packed, v_packed, k_cache, v_cache, cu_seqlens, kv_lens)
+    torch.ops.fa_mi355x.cache_append_varlen_paged(k_packed, v_packed, k_pages, v_pages, block_table, cu_seqlens, kv_lens)
 
 ``q, k, v``: fp16 or bf16 ``[B, H, S, D]`` (D = 128 or 64) tensors on the GPU (BHSD, the
 reference layout, flash_attention.cu:119-122); returns a new tensor of the same shape and dtype.
@@ -30,8 +34,10 @@ from __future__ import annotations
 import torch
 
 from . import (flash_attention_cache_append, flash_attention_cache_append_paged,
+               flash_attention_cache_append_varlen, flash_attention_cache_append_varlen_paged,
                flash_attention_decode, flash_attention_decode_paged, flash_attention_fwd,
-               flash_attention_prefill, flash_attention_prefill_paged)
+               flash_attention_prefill, flash_attention_prefill_paged,
+               flash_attention_prefill_varlen, flash_attention_prefill_varlen_paged)
 
 OP_NAME = "fa_mi355x::fwd"
 
@@ -305,3 +311,138 @@ _LIB.impl("prefill_paged", _prefill_paged_cpu, "CPU")
 torch.library.register_fake(PREFILL_PAGED_OP_NAME, _prefill_paged_fake, lib=_LIB)
 
 prefill_paged = torch.ops.fa_mi355x.prefill_paged
+
+# The packed (cu_seqlens) twins: q / k_new / v_new token-major [T,H,D], cu_seqlens
+# int32 [B + 1] (required), B the caches' batch or the block table's rows:
+# fa_mi355x.flash_attention_prefill_varlen[_paged] and
+# flash_attention_cache_append_varlen[_paged] behind the same registrations as
+# their padded twins.  Rows of the returned tensor that belong to no sequence
+# are unspecified.
+PREFILL_VARLEN_OP_NAME = "fa_mi355x::prefill_varlen"
+_LIB.define("prefill_varlen(Tensor q, Tensor k_cache, Tensor v_cache, Tensor cu_seqlens_q, "
+            "Tensor? kv_lens=None, bool causal=True, Tensor? k_scale=None, "
+            "Tensor? v_scale=None) -> Tensor")
+
+
+def _prefill_varlen_gpu(q, k_cache, v_cache, cu_seqlens_q, kv_lens=None, causal: bool = True,
+                        k_scale=None, v_scale=None) -> torch.Tensor:
+    _no_grad_needed(q, k_cache, v_cache)
+    return flash_attention_prefill_varlen(q.contiguous(), k_cache, v_cache, cu_seqlens_q.contiguous(),
+                                          None if kv_lens is None else kv_lens.contiguous(),
+                                          causal=causal, k_scale=k_scale, v_scale=v_scale)
+
+
+def _prefill_varlen_cpu(q, k_cache, v_cache, cu_seqlens_q, kv_lens=None, causal: bool = True,
+                        k_scale=None, v_scale=None) -> torch.Tensor:
+    raise ValueError("fa_mi355x::prefill_varlen needs GPU tensors (no CPU path)")
+
+
+def _prefill_varlen_fake(q, k_cache, v_cache, cu_seqlens_q, kv_lens=None, causal: bool = True,
+                         k_scale=None, v_scale=None) -> torch.Tensor:
+    _no_grad_needed(q, k_cache, v_cache)
+    torch._check(q.dim() == 3 and q.shape[-1] in (64, 128), lambda: "expected [T, Hq, 64|128]")
+    torch._check(q.dtype in (torch.float16, torch.bfloat16), lambda: "expected fp16 or bf16")
+    torch._check(cu_seqlens_q.dim() == 1, lambda: "expected a [B + 1] cu_seqlens_q")
+    return torch.empty_like(q, memory_format=torch.contiguous_format)
+
+
+_LIB.impl("prefill_varlen", _prefill_varlen_gpu, "CUDA")
+_LIB.impl("prefill_varlen", torch.library.fallthrough_kernel, "Autograd")
+_LIB.impl("prefill_varlen", _prefill_varlen_cpu, "CPU")
+torch.library.register_fake(PREFILL_VARLEN_OP_NAME, _prefill_varlen_fake, lib=_LIB)
+
+prefill_varlen = torch.ops.fa_mi355x.prefill_varlen
+
+PREFILL_VARLEN_PAGED_OP_NAME = "fa_mi355x::prefill_varlen_paged"
+_LIB.define("prefill_varlen_paged(Tensor q, Tensor k_pages, Tensor v_pages, Tensor block_table, "
+            "Tensor cu_seqlens_q, Tensor? kv_lens=None, bool causal=True, Tensor? k_scale=None, "
+            "Tensor? v_scale=None) -> Tensor")
+
+
+def _prefill_varlen_paged_gpu(q, k_pages, v_pages, block_table, cu_seqlens_q, kv_lens=None,
+                              causal: bool = True, k_scale=None, v_scale=None) -> torch.Tensor:
+    _no_grad_needed(q, k_pages, v_pages)
+    return flash_attention_prefill_varlen_paged(q.contiguous(), k_pages, v_pages,
+                                                block_table.contiguous(), cu_seqlens_q.contiguous(),
+                                                None if kv_lens is None else kv_lens.contiguous(),
+                                                causal=causal, k_scale=k_scale, v_scale=v_scale)
+
+
+def _prefill_varlen_paged_cpu(q, k_pages, v_pages, block_table, cu_seqlens_q, kv_lens=None,
+                              causal: bool = True, k_scale=None, v_scale=None) -> torch.Tensor:
+    raise ValueError("fa_mi355x::prefill_varlen_paged needs GPU tensors (no CPU path)")
+
+
+def _prefill_varlen_paged_fake(q, k_pages, v_pages, block_table, cu_seqlens_q, kv_lens=None,
+                               causal: bool = True, k_scale=None, v_scale=None) -> torch.Tensor:
+    torch._check(block_table.dim() == 2, lambda: "expected a [B, max_pages_per_seq] block table")
+    return _prefill_varlen_fake(q, k_pages, v_pages, cu_seqlens_q, kv_lens, causal, k_scale, v_scale)
+
+
+_LIB.impl("prefill_varlen_paged", _prefill_varlen_paged_gpu, "CUDA")
+_LIB.impl("prefill_varlen_paged", torch.library.fallthrough_kernel, "Autograd")
+_LIB.impl("prefill_varlen_paged", _prefill_varlen_paged_cpu, "CPU")
+torch.library.register_fake(PREFILL_VARLEN_PAGED_OP_NAME, _prefill_varlen_paged_fake, lib=_LIB)
+
+prefill_varlen_paged = torch.ops.fa_mi355x.prefill_varlen_paged
+
+CACHE_APPEND_VARLEN_OP_NAME = "fa_mi355x::cache_append_varlen"
+_LIB.define("cache_append_varlen(Tensor k_new, Tensor v_new, Tensor(a!) k_cache, Tensor(b!) v_cache, "
+            "Tensor cu_seqlens, Tensor kv_lens, Tensor? k_scale=None, Tensor? v_scale=None) -> ()")
+
+
+def _cache_append_varlen_gpu(k_new, v_new, k_cache, v_cache, cu_seqlens, kv_lens, k_scale=None,
+                             v_scale=None) -> None:
+    flash_attention_cache_append_varlen(k_new.contiguous(), v_new.contiguous(), k_cache, v_cache,
+                                        cu_seqlens.contiguous(), kv_lens.contiguous(),
+                                        k_scale=k_scale, v_scale=v_scale)
+
+
+def _cache_append_varlen_cpu(k_new, v_new, k_cache, v_cache, cu_seqlens, kv_lens, k_scale=None,
+                             v_scale=None) -> None:
+    raise ValueError("fa_mi355x::cache_append_varlen needs GPU tensors (no CPU path)")
+
+
+def _cache_append_varlen_fake(k_new, v_new, k_cache, v_cache, cu_seqlens, kv_lens, k_scale=None,
+                              v_scale=None) -> None:
+    torch._check(k_new.dim() == 3 and k_new.shape[-1] in (64, 128), lambda: "expected [T, Hkv, 64|128]")
+    torch._check(k_new.dtype in (torch.float16, torch.bfloat16), lambda: "expected fp16 or bf16")
+    torch._check(k_cache.dim() == 4 and v_cache.dim() == 4, lambda: "expected 4-D caches")
+    torch._check(cu_seqlens.dim() == 1, lambda: "expected a [B + 1] cu_seqlens")
+
+
+_LIB.impl("cache_append_varlen", _cache_append_varlen_gpu, "CUDA")
+_LIB.impl("cache_append_varlen", _cache_append_varlen_cpu, "CPU")
+torch.library.register_fake(CACHE_APPEND_VARLEN_OP_NAME, _cache_append_varlen_fake, lib=_LIB)
+
+cache_append_varlen = torch.ops.fa_mi355x.cache_append_varlen
+
+CACHE_APPEND_VARLEN_PAGED_OP_NAME = "fa_mi355x::cache_append_varlen_paged"
+_LIB.define("cache_append_varlen_paged(Tensor k_new, Tensor v_new, Tensor(a!) k_pages, "
+            "Tensor(b!) v_pages, Tensor block_table, Tensor cu_seqlens, Tensor kv_lens, "
+            "Tensor? k_scale=None, Tensor? v_scale=None) -> ()")
+
+
+def _cache_append_varlen_paged_gpu(k_new, v_new, k_pages, v_pages, block_table, cu_seqlens, kv_lens,
+                                   k_scale=None, v_scale=None) -> None:
+    flash_attention_cache_append_varlen_paged(k_new.contiguous(), v_new.contiguous(), k_pages, v_pages,
+                                              block_table.contiguous(), cu_seqlens.contiguous(),
+                                              kv_lens.contiguous(), k_scale=k_scale, v_scale=v_scale)
+
+
+def _cache_append_varlen_paged_cpu(k_new, v_new, k_pages, v_pages, block_table, cu_seqlens, kv_lens,
+                                   k_scale=None, v_scale=None) -> None:
+    raise ValueError("fa_mi355x::cache_append_varlen_paged needs GPU tensors (no CPU path)")
+
+
+def _cache_append_varlen_paged_fake(k_new, v_new, k_pages, v_pages, block_table, cu_seqlens, kv_lens,
+                                    k_scale=None, v_scale=None) -> None:
+    _cache_append_varlen_fake(k_new, v_new, k_pages, v_pages, cu_seqlens, kv_lens, k_scale, v_scale)
+    torch._check(block_table.dim() == 2, lambda: "expected a [B, max_pages_per_seq] block table")
+
+
+_LIB.impl("cache_append_varlen_paged", _cache_append_varlen_paged_gpu, "CUDA")
+_LIB.impl("cache_append_varlen_paged", _cache_append_varlen_paged_cpu, "CPU")
+torch.library.register_fake(CACHE_APPEND_VARLEN_PAGED_OP_NAME, _cache_append_varlen_paged_fake, lib=_LIB)
+
+cache_append_varlen_paged = torch.ops.fa_mi355x.cache_append_varlen_paged

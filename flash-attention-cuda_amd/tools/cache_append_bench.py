@@ -24,6 +24,14 @@ append's exceeds the A/A difference.
 Shapes: a bandwidth-bound prefill append (B=16, Hkv=8, Sn=4096, D=128) and the
 decode step (B=64, Hkv=8, Sn=1), each into a contiguous cache and into pools of
 page size 64 and 256, 16-bit and kv8.
+
+--varlen: the packed entry flash_attention_cache_append_varlen[_paged] on
+token-major [T, Hkv, D] sources with cu_seqlens against what a packed caller
+does today -- scatter K and V into padded [B, Hkv, max n_b, D] copies, then the
+padded append with new_lens -- by the same protocol, on the three ragged
+batches of tools/prefill_bench.py --varlen (Hkv = 8, D = 128), into a
+contiguous cache and a pool of page size 256, 16-bit and kv8; written to
+profiles/cache_append_varlen_bench.jsonl.
 """
 import argparse
 import json
@@ -155,15 +163,142 @@ def run(row, page_size, kv8, rounds=9):
                 gate_faster_beyond_aa=bool(med[1] - med[0] > abs(med[2] - med[0])))
 
 
+def varlen_lengths(name):
+    """(n_b, prefix_b): the batches of tools/prefill_bench.py --varlen."""
+    if name == "uniform":
+        return [4096] * 8, [0] * 8
+    if name == "ragged":
+        return [512 * (i + 1) for i in range(8)], [0] * 8
+    return [4096] + [1 + (5 * i) % 16 for i in range(63)], [0] + [2048] * 63
+
+
+def run_varlen(name, page_size, kv8, rounds=9, copies=2, iters=4):
+    dt = torch.float16
+    n, prefix = varlen_lengths(name)
+    b, hkv, d = len(n), 8, 128
+    total, smax = sum(n), max(n)
+    kvl = [p + x for p, x in zip(prefix, n)]
+    cap = -(-max(kvl) // 256) * 256
+    paged = page_size > 0
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    cdt = torch.uint8 if kv8 else dt
+    cu = torch.tensor([0] + [sum(n[:i + 1]) for i in range(b)], dtype=torch.int32, device="cuda")
+    lens = torch.tensor(kvl, dtype=torch.int32, device="cuda")
+    new_lens = torch.tensor(n, dtype=torch.int32, device="cuda")
+    idx_b = torch.repeat_interleave(torch.arange(b, device="cuda"), new_lens.long())
+    idx_t = torch.arange(total, device="cuda") - cu[:-1].long()[idx_b]
+    if paged:
+        mpp = cap // page_size
+        npages = b * mpp
+        shape = (npages, hkv, page_size, d)
+    else:
+        shape = (b, hkv, cap, d)
+    k_scale = torch.tensor([2.0 ** -(3 - (h & 1)) * 1.3 for h in range(hkv)], dtype=torch.float32, device="cuda")
+    v_scale = torch.tensor([2.0 ** -(2 + (h & 1)) * 0.7 for h in range(hkv)], dtype=torch.float32, device="cuda")
+    scales = dict(k_scale=k_scale, v_scale=v_scale) if kv8 else {}
+
+    def rnd(*s):
+        return (torch.rand(s, generator=gen, device="cuda", dtype=torch.float32) * 2 - 1).to(dt)
+
+    srcs = [(rnd(total, hkv, d), rnd(total, hkv, d)) for _ in range(copies)]
+    caches = [[(torch.zeros(shape, dtype=cdt, device="cuda"), torch.zeros(shape, dtype=cdt, device="cuda"))
+               for _ in range(copies)] for _ in range(2)]
+    tabs = [torch.randperm(npages, generator=gen, device="cuda").view(b, mpp).to(torch.int32).contiguous()
+            if paged else None for _ in range(copies)]
+
+    def typed(c):
+        return c.view(FP8) if kv8 else c
+
+    def ours(i):
+        c = i % copies
+        (kn, vn), (kc, vc) = srcs[c], caches[0][c]
+        if paged:
+            fa_mi355x.flash_attention_cache_append_varlen_paged(kn, vn, typed(kc), typed(vc), tabs[c], cu, lens,
+                                                                **scales)
+        else:
+            fa_mi355x.flash_attention_cache_append_varlen(kn, vn, typed(kc), typed(vc), cu, lens, **scales)
+
+    def scatter_padded(i):
+        c = i % copies
+        (kn, vn), (kc, vc) = srcs[c], caches[1][c]
+        kpad = torch.empty((b, hkv, smax, d), dtype=dt, device="cuda")
+        vpad = torch.empty((b, hkv, smax, d), dtype=dt, device="cuda")
+        kpad[idx_b, :, idx_t] = kn
+        vpad[idx_b, :, idx_t] = vn
+        if paged:
+            fa_mi355x.flash_attention_cache_append_paged(kpad, vpad, typed(kc), typed(vc), tabs[c], lens, new_lens,
+                                                         **scales)
+        else:
+            fa_mi355x.flash_attention_cache_append(kpad, vpad, typed(kc), typed(vc), lens, new_lens, **scales)
+
+    legs_fn = (ours, scatter_padded)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):  # first-launch set-up outside the captures
+        for fn in legs_fn:
+            for i in range(copies):
+                fn(i)
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    same = all(torch.equal(a[0], c[0]) and torch.equal(a[1], c[1]) for a, c in zip(*caches))
+    graphs = []
+    for fn in legs_fn:
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            for i in range(iters):
+                fn(i)
+        g.replay()
+        graphs.append(g)
+    torch.cuda.synchronize()
+    legs = (0, 1, 0)  # packed, scatter + padded, packed again (the A/A leg)
+    ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+           for _ in range(rounds)] for _ in legs]
+    for r in range(rounds):
+        for j, gi in enumerate(legs):
+            ev[j][r][0].record()
+            graphs[gi].replay()
+            ev[j][r][1].record()
+    torch.cuda.synchronize()
+    ts = [sorted(a.elapsed_time(c) * 1e3 / iters for a, c in e) for e in ev]
+    med = [t[len(t) // 2] for t in ts]
+    elems = 2 * total * hkv * d  # K and V
+    nbytes = elems * 2 + elems * (1 if kv8 else 2)
+    return dict(varlen=name, cache="kv8" if kv8 else "16-bit", page_size=page_size, batch=b, heads_kv=hkv,
+                total_new=total, max_n=smax, padded_rows=b * smax, head_dim=d, kv_capacity=cap, copies=copies,
+                iters=iters, rounds=rounds, bytes_moved=nbytes, bit_identical_to_scatter_padded=same,
+                packed_us=round(med[0], 2), scatter_padded_us=round(med[1], 2), packed2_us=round(med[2], 2),
+                packed_min_us=round(min(ts[0][0], ts[2][0]), 2), packed_max_us=round(max(ts[0][-1], ts[2][-1]), 2),
+                scatter_padded_min_us=round(ts[1][0], 2), scatter_padded_max_us=round(ts[1][-1], 2),
+                packed_aa=round(med[2] / med[0], 4), scatter_padded_over_packed=round(med[1] / med[0], 3),
+                packed_gb_per_s=round(nbytes / med[0] / 1e3, 1),
+                packed_share_of_copy_rate=round(nbytes / (med[0] * 1e-6) / COPY_RATE, 4))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..",
                                                   "profiles", "cache_append_bench.jsonl"))
     ap.add_argument("--quick", action="store_true", help="one small shape (a rehearsal, not a measurement)")
+    ap.add_argument("--varlen", action="store_true",
+                    help="the packed entry against scatter + padded append (default --out: "
+                         "profiles/cache_append_varlen_bench.jsonl)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("cache_append_bench.py needs a GPU")
+    if args.varlen and args.out == ap.get_default("out"):
+        args.out = os.path.join(os.path.dirname(args.out), "cache_append_varlen_bench.jsonl")
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    if args.varlen:
+        with open(args.out, "w") as f:
+            for name in ("uniform", "ragged", "skewed"):
+                for page_size in (0, 256):
+                    for kv8 in (False, True):
+                        rec = run_varlen(name, page_size, kv8)
+                        f.write(json.dumps(rec) + "\n")
+                        f.flush()
+                        print(json.dumps(rec), flush=True)
+                        torch.cuda.empty_cache()
+        return
     with open(args.out, "w") as f:
         for row in shapes(args.quick):
             for page_size in (0, 64, 256):

@@ -23,6 +23,19 @@ TFLOP/s uses the reference's convention extended to the contract:
 
     timeout 300 python3 tools/prefill_bench.py --shape headline --dtype fp16 \\
         [--forms contig,paged,contig_kv8,paged_kv8] [--out profiles/prefill_bench.jsonl]
+
+--varlen NAME (instead of --shape): the packed (cu_seqlens, token-major Q) entry
+flash_attention_prefill_varlen[_paged] on a ragged batch at D = 128, Hq = 32,
+Hkv = 8, three arms on the same lengths and cache, alternated the same way:
+
+  packed    the packed entry on Q [T, Hq, D] and cu_seqlens;
+  padded    the padded entry alone on inputs already in ITS layout (Q
+            [B, Hq, max n_b, D] with q_lens = n, the rest padding): the yardstick;
+  whole     what a packed caller pays today: scatter Q into the padded layout,
+            the padded entry, gather O back (the padded buffers come from
+            torch's caching allocator inside the arm).
+
+    timeout 300 python3 tools/prefill_bench.py --varlen skewed [--out profiles/prefill_varlen_bench.jsonl]
 """
 import argparse
 import json
@@ -45,6 +58,19 @@ SHAPES = {
     "short_chunk": (16, 32, 8, 512, 8192),
 }
 FORMS = ("contig", "paged", "contig_kv8", "paged_kv8")
+
+
+def varlen_lengths(name):
+    """(n_b, prefix_b) of the --varlen batches."""
+    if name == "uniform":
+        return [4096] * 8, [0] * 8
+    if name == "ragged":
+        return [512 * (i + 1) for i in range(8)], [0] * 8
+    # one 4096-token prompt and 63 chunks of 1..16 tokens behind 2048-key prefixes
+    return [4096] + [1 + (5 * i) % 16 for i in range(63)], [0] + [2048] * 63
+
+
+VARLEN = ("uniform", "ragged", "skewed")
 
 
 def flops(b, hq, d, sq, prefix):
@@ -177,9 +203,91 @@ def run(shape, dt, form, rounds, iters):
     return rec
 
 
+def run_varlen(name, dt, form, rounds, iters):
+    n, prefix = varlen_lengths(name)
+    b, hq, hkv, d = len(n), 32, 8, 128
+    total, smax = sum(n), max(n)
+    kvl = [p + x for p, x in zip(prefix, n)]
+    cap = -(-max(kvl) // PAGE) * PAGE
+    gen = torch.Generator(device="cuda").manual_seed(1)
+
+    def rnd(*s):
+        return (torch.rand(s, generator=gen, device="cuda", dtype=torch.float32) * 2 - 1).to(dt)
+
+    qp = rnd(total, hq, d)
+    k, v = rnd(b, hkv, cap, d), rnd(b, hkv, cap, d)
+    cu = torch.tensor([0] + [sum(n[:i + 1]) for i in range(b)], dtype=torch.int32, device="cuda")
+    kv_lens = torch.tensor(kvl, dtype=torch.int32, device="cuda")
+    q_lens = torch.tensor(n, dtype=torch.int32, device="cuda")
+    # packed row -> (sequence, token)
+    idx_b = torch.repeat_interleave(torch.arange(b, device="cuda"), q_lens.long())
+    idx_t = torch.arange(total, device="cuda") - cu[:-1].long()[idx_b]
+    kv8, paged = form.endswith("kv8"), form.startswith("paged")
+    scales = {}
+    if kv8:
+        ks = torch.tensor([2.0 ** -(3 - (h & 1)) for h in range(hkv)], dtype=torch.float32, device="cuda")
+        vs = torch.tensor([2.0 ** -(2 + (h & 1)) for h in range(hkv)], dtype=torch.float32, device="cuda")
+        k = (k.float() / ks[None, :, None, None]).to(FP8)
+        v = (v.float() / vs[None, :, None, None]).to(FP8)
+        scales = dict(k_scale=ks, v_scale=vs)
+    table = None
+    if paged:
+        mpp = cap // PAGE
+        perm = torch.randperm(b * mpp, generator=gen, device="cuda")
+
+        def pool(x):
+            out = torch.empty((b * mpp, hkv, PAGE, d), dtype=x.dtype, device="cuda")
+            src = x.view(b, hkv, mpp, PAGE, d).permute(0, 2, 1, 3, 4).reshape(b * mpp, hkv, PAGE, d)
+            out.view(torch.uint8)[perm] = src.contiguous().view(torch.uint8)
+            return out
+
+        k, v = pool(k), pool(v)
+        table = perm.view(b, mpp).to(torch.int32).contiguous()
+    qpad = torch.zeros((b, hq, smax, d), dtype=dt, device="cuda")
+    qpad[idx_b, :, idx_t] = qp
+    op, opad = torch.empty_like(qp), torch.empty_like(qpad)
+
+    def padded_entry(q, out):
+        if paged:
+            return fa_mi355x.flash_attention_prefill_paged(q, k, v, table, kv_lens, q_lens, out=out, **scales)
+        return fa_mi355x.flash_attention_prefill(q, k, v, kv_lens, q_lens, out=out, **scales)
+
+    def packed():
+        if paged:
+            return fa_mi355x.flash_attention_prefill_varlen_paged(qp, k, v, table, cu, kv_lens, out=op, **scales)
+        return fa_mi355x.flash_attention_prefill_varlen(qp, k, v, cu, kv_lens, out=op, **scales)
+
+    def padded():
+        return padded_entry(qpad, opad)
+
+    def whole():
+        q = torch.empty((b, hq, smax, d), dtype=dt, device="cuda")
+        q[idx_b, :, idx_t] = qp
+        return padded_entry(q, torch.empty_like(q))[idx_b, :, idx_t]
+
+    same = bool(torch.equal(packed(), whole()))
+    ts = time_arms([packed, padded, whole], iters, rounds)
+    fl = 4.0 * hq * d * sum(p * x + x * (x + 1) // 2 for p, x in zip(prefix, n))
+    rec = dict(varlen=name, form=form, dtype=str(dt).split(".")[-1], batch=b, heads_q=hq, heads_kv=hkv,
+               head_dim=d, total_q=total, max_n=smax, padded_rows=b * smax, kv_capacity=cap,
+               page_size=PAGE if paged else None, rounds=rounds, iters=iters,
+               packed_grid=hq * (total // 128 + b), padded_grid=b * hq * (-(-smax // 128)),
+               packed_equals_whole_path=same)
+    for arm, (med, lo, hi) in zip(("packed", "padded", "whole"), ts):
+        rec[arm + "_ms"] = round(med, 4)
+        rec[arm + "_min_ms"] = round(lo, 4)
+        rec[arm + "_max_ms"] = round(hi, 4)
+    rec["packed_tflops"] = round(fl / (ts[0][0] * 1e-3) / 1e12, 1)
+    rec["padded_tflops"] = round(fl / (ts[1][0] * 1e-3) / 1e12, 1)
+    rec["packed_over_padded"] = round(ts[0][0] / ts[1][0], 4)
+    rec["whole_over_packed"] = round(ts[2][0] / ts[0][0], 4)
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--shape", choices=sorted(SHAPES), required=True)
+    ap.add_argument("--shape", choices=sorted(SHAPES))
+    ap.add_argument("--varlen", choices=VARLEN, help="a packed ragged batch instead of --shape")
     ap.add_argument("--dtype", choices=("fp16", "bf16"), default="fp16")
     ap.add_argument("--forms", default=",".join(FORMS))
     ap.add_argument("--rounds", type=int, default=7)
@@ -188,16 +296,21 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("prefill_bench.py needs a GPU")
+    if (args.shape is None) == (args.varlen is None):
+        ap.error("one of --shape and --varlen is required")
     if args.out is None:
         args.out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "profiles",
-                                "prefill_bench.jsonl")
+                                "prefill_varlen_bench.jsonl" if args.varlen else "prefill_bench.jsonl")
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     dt = torch.bfloat16 if args.dtype == "bf16" else torch.float16
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     with open(args.out, "a") as f:
         for form in args.forms.split(","):
             assert form in FORMS, form
-            rec = run(args.shape, dt, form, args.rounds, args.iters)
+            if args.varlen:
+                rec = run_varlen(args.varlen, dt, form, args.rounds, args.iters)
+            else:
+                rec = run(args.shape, dt, form, args.rounds, args.iters)
             rec["cus"] = cus
             f.write(json.dumps(rec) + "\n")
             f.flush()

@@ -472,6 +472,130 @@ int fa_prefill_paged_kv8_bf16(const void* q, const void* k_pages, const void* v_
                               int max_pages_per_seq, const int* kv_lens, const int* q_lens, int causal,
                               void* hip_stream, const float* k_scale, const float* v_scale);
 
+/* Packed variable-length (cu_seqlens) forms of the two entries that consume
+ * new tokens, prefill and cache append, over the same four cache forms: what a
+ * serving stack holds after its QKV projection, one token-major tensor for the
+ * whole ragged batch and an int32 prefix sum, taken as it is (no padded copy).
+ *   T      total_q / total_new: rows of the packed tensors
+ *   batch  the number of sequences B
+ *   cu     cu_seqlens_q / cu_seqlens: DEVICE int32[batch + 1], REQUIRED
+ *     s_b = clamp(cu[b], 0, T)
+ *     e_b = clamp(cu[b + 1], s_b, T)
+ *     n_b = e_b - s_b            token t of sequence b is packed row s_b + t
+ * The clamps make every cu memory-safe: whatever it holds (garbage, values
+ * that decrease), nothing outside the T rows is addressed; for a cu that is
+ * not monotone the result is unspecified.  kv_lens (the lengths AFTER the
+ * append), len_b, off_b = len_b - n_b, vis, GQA, the bottom-right causal rule,
+ * the cache forms, "rows past len_b are never read", "an out-of-pool page id
+ * reads as zero rows / drops the row" and the FP8 contracts are those of
+ * fa_prefill_* and fa_cache_append_* above, with n_b in q_lens' / new_lens'
+ * place.  Everything is read on the device: no host look at cu, no sync, no
+ * workspace, graph-capturable; a captured graph follows cu, kv_lens, tables
+ * and scales rewritten between replays (T is a launch parameter).
+ *
+ * fa_prefill_varlen_*:
+ *   q, o   [total_q][heads_q][head_dim]  16-bit, token-major, contiguous
+ *   lse    optional fp32 [heads_q][total_q], natural log; may be NULL
+ * Row s_b + t of o (and lse[hq][s_b + t]) is row t of element b of
+ * fa_prefill_* called on the padded copy with q_lens = n, BIT FOR BIT: query
+ * blocks are aligned to each sequence's own start, so a workgroup runs the
+ * tile sequence the padded entry runs.  Rows below s_0, at or past e_{B-1},
+ * and rows that belong to no sequence are NOT WRITTEN.  The launch is
+ * heads_q * (total_q / 128 + batch) workgroups whatever the lengths are (a
+ * workgroup finds its sequence by bisection on cu and returns if it has no
+ * rows).  Causal blocks are not ordered heaviest first across sequences (that
+ * needs the lengths on the host); within a sequence they start last to first.
+ * Argument errors, all before any launch, in fa_prefill_*'s order: a negative
+ * count (total_q included): FA_ERR_BAD_SHAPE; head_dim: as there; the page
+ * geometry: as there; batch, heads_q or total_q of 0: FA_OK, nothing enqueued;
+ * heads_q % heads_kv != 0, heads_q * total_q > INT_MAX (LSE rows), 128 *
+ * heads_q * 2 * head_dim > INT_MAX (the byte range of one block's rows),
+ * kv_capacity * 2 * head_dim > INT_MAX (contiguous), heads_q * (total_q / 128
+ * + batch) > INT_MAX (the grid): FA_ERR_BAD_SHAPE; kv_capacity == 0 fills O
+ * with zeros and LSE with -inf for ALL total_q rows; q, k, v, o, cu_seqlens_q
+ * (or block_table) NULL: FA_ERR_NULL_POINTER.
+ *
+ * fa_cache_append_varlen_*:
+ *   k_new, v_new  [total_new][heads_kv][head_dim]  16-bit, token-major
+ *   token t of sequence b -> cache row kv_lens[b] - n_b + t, written if and
+ *   only if the row exists (fa_cache_append_*'s rule; the FP8 byte is the
+ *   reciprocal contract's, byte for byte).
+ * Argument errors in fa_cache_append_*'s order, with total_new < 0 (or >
+ * INT_MAX - 64) in seqlen_new's place, total_new == 0 returning FA_OK beside
+ * batch == 0, total_new / TB + batch > INT_MAX (TB: 64 tokens at head_dim 128,
+ * 128 at 64) FA_ERR_BAD_SHAPE before the capacity-0 return, and a NULL
+ * cu_seqlens FA_ERR_NULL_POINTER with the other pointers. */
+int fa_prefill_varlen_f16(const void* q, const void* k, const void* v, void* o, float* lse,
+                          int batch, int heads_q, int heads_kv, int total_q, int kv_capacity,
+                          int head_dim, const int* kv_lens, const int* cu_seqlens_q, int causal,
+                          void* hip_stream);
+int fa_prefill_varlen_bf16(const void* q, const void* k, const void* v, void* o, float* lse,
+                           int batch, int heads_q, int heads_kv, int total_q, int kv_capacity,
+                           int head_dim, const int* kv_lens, const int* cu_seqlens_q, int causal,
+                           void* hip_stream);
+int fa_prefill_varlen_paged_f16(const void* q, const void* k_pages, const void* v_pages, void* o,
+                                float* lse, int batch, int heads_q, int heads_kv, int total_q,
+                                int head_dim, int num_pages, int page_size, const int* block_table,
+                                int max_pages_per_seq, const int* kv_lens, const int* cu_seqlens_q,
+                                int causal, void* hip_stream);
+int fa_prefill_varlen_paged_bf16(const void* q, const void* k_pages, const void* v_pages, void* o,
+                                 float* lse, int batch, int heads_q, int heads_kv, int total_q,
+                                 int head_dim, int num_pages, int page_size, const int* block_table,
+                                 int max_pages_per_seq, const int* kv_lens, const int* cu_seqlens_q,
+                                 int causal, void* hip_stream);
+int fa_prefill_varlen_kv8_f16(const void* q, const void* k, const void* v, void* o, float* lse,
+                              int batch, int heads_q, int heads_kv, int total_q, int kv_capacity,
+                              int head_dim, const int* kv_lens, const int* cu_seqlens_q, int causal,
+                              void* hip_stream, const float* k_scale, const float* v_scale);
+int fa_prefill_varlen_kv8_bf16(const void* q, const void* k, const void* v, void* o, float* lse,
+                               int batch, int heads_q, int heads_kv, int total_q, int kv_capacity,
+                               int head_dim, const int* kv_lens, const int* cu_seqlens_q, int causal,
+                               void* hip_stream, const float* k_scale, const float* v_scale);
+int fa_prefill_varlen_paged_kv8_f16(const void* q, const void* k_pages, const void* v_pages, void* o,
+                                    float* lse, int batch, int heads_q, int heads_kv, int total_q,
+                                    int head_dim, int num_pages, int page_size,
+                                    const int* block_table, int max_pages_per_seq,
+                                    const int* kv_lens, const int* cu_seqlens_q, int causal,
+                                    void* hip_stream, const float* k_scale, const float* v_scale);
+int fa_prefill_varlen_paged_kv8_bf16(const void* q, const void* k_pages, const void* v_pages, void* o,
+                                     float* lse, int batch, int heads_q, int heads_kv, int total_q,
+                                     int head_dim, int num_pages, int page_size,
+                                     const int* block_table, int max_pages_per_seq,
+                                     const int* kv_lens, const int* cu_seqlens_q, int causal,
+                                     void* hip_stream, const float* k_scale, const float* v_scale);
+int fa_cache_append_varlen_16(const void* k_new, const void* v_new, void* k_cache, void* v_cache,
+                              int batch, int heads_kv, int total_new, int kv_capacity, int head_dim,
+                              const int* kv_lens, const int* cu_seqlens, void* hip_stream);
+int fa_cache_append_varlen_paged_16(const void* k_new, const void* v_new, void* k_pages,
+                                    void* v_pages, int batch, int heads_kv, int total_new,
+                                    int head_dim, int num_pages, int page_size,
+                                    const int* block_table, int max_pages_per_seq,
+                                    const int* kv_lens, const int* cu_seqlens, void* hip_stream);
+int fa_cache_append_varlen_kv8_f16(const void* k_new, const void* v_new, void* k_cache,
+                                   void* v_cache, int batch, int heads_kv, int total_new,
+                                   int kv_capacity, int head_dim, const int* kv_lens,
+                                   const int* cu_seqlens, void* hip_stream, const float* k_scale,
+                                   const float* v_scale);
+int fa_cache_append_varlen_kv8_bf16(const void* k_new, const void* v_new, void* k_cache,
+                                    void* v_cache, int batch, int heads_kv, int total_new,
+                                    int kv_capacity, int head_dim, const int* kv_lens,
+                                    const int* cu_seqlens, void* hip_stream, const float* k_scale,
+                                    const float* v_scale);
+int fa_cache_append_varlen_paged_kv8_f16(const void* k_new, const void* v_new, void* k_pages,
+                                         void* v_pages, int batch, int heads_kv, int total_new,
+                                         int head_dim, int num_pages, int page_size,
+                                         const int* block_table, int max_pages_per_seq,
+                                         const int* kv_lens, const int* cu_seqlens,
+                                         void* hip_stream, const float* k_scale,
+                                         const float* v_scale);
+int fa_cache_append_varlen_paged_kv8_bf16(const void* k_new, const void* v_new, void* k_pages,
+                                          void* v_pages, int batch, int heads_kv, int total_new,
+                                          int head_dim, int num_pages, int page_size,
+                                          const int* block_table, int max_pages_per_seq,
+                                          const int* kv_lens, const int* cu_seqlens,
+                                          void* hip_stream, const float* k_scale,
+                                          const float* v_scale);
+
 /* The dispatcher's decision (ref tier table :620-661): config id used by
  * fa_fwd_f16 for this shape.  The _ws entries may run the causal split tier
  * instead: check fa_fwd_split_pieces() first (> 0: the split tier runs with
