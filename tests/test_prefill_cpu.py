@@ -4,9 +4,13 @@ fake pointers suffice), the Python wrappers' rejections on CPU tensors, the
 compile-time resource usage of the four prefill units, the references of
 tests/prefill_refs.py against one another in the range decode never reached
 (ragged Sq > 16), and the key-sensitivity checkers on the float64 restatement
-of the contract at the GPU test's exact shapes.
+of the contract at the GPU test's exact shapes, and the staircase inputs of
+tests/test_prefill_ranges_gpu.py: the side of the rescale threshold their steps
+lie on, exactness in every type, and the references alone against half of
+each gate.
 """
 import ctypes
+import math
 import os
 import re
 
@@ -311,3 +315,111 @@ def test_needle_checkers_accept_the_contract(kind, d):
     off_by_one = ks.check_census(o[0, :, :100].to(torch.float16).double(), vis[0, :, 1:101], counts, 0.25,
                                  "stripe", "off by one", dtype=torch.float16)
     assert not off_by_one.ok
+
+
+# ---- the staircase inputs (prefill_refs.staircase) of tests/test_prefill_ranges_gpu.py --
+
+ST_CASES = [(p, "q") for p in pr.ST_PATTERNS] + [(p, "scale") for p in ("asc4.5", "over8", "jump")]
+ST_IDS = [f"{p}-{c}" for p, c in ST_CASES]
+RESCALE_LOG2 = 8.0  # fa_fwd_kernel.hpp
+
+
+@pytest.mark.parametrize("d", [128, 64])
+@pytest.mark.parametrize("pattern,carry", [(p, c) for p in ("under8", "over8") for c in ("q", "scale")])
+def test_staircase_steps_lie_on_the_intended_side_of_the_threshold(pattern, carry, d):
+    """Clean patterns, float64: every visible row's maximum grows from one visible
+    tile to the next by a step that is at least 0.05 log2 units below (under8) or
+    above (over8) the kernel's rescale threshold, causal and not."""
+    src = open(os.path.join(cc.PKG, "csrc", "fa_fwd_kernel.hpp")).read()
+    assert re.findall(r"constexpr float RESCALE_LOG2 = ([0-9.]+)f;", src) == ["8.0"]
+    st = pr.staircase(pattern, d, carry)
+    assert not st.noisy
+    kd = st.dequant()[0]
+    g = pr.ST_HQ // pr.ST_HKV
+    log2e_over_sqrt_d = math.log2(math.e) / math.sqrt(d)
+    seen = 0
+    for causal in (True, False):
+        vis = pr.visible(pr.ST_KV_LENS, pr.ST_Q_LENS, pr.ST_B, pr.ST_SQ, pr.ST_CAP, causal)
+        for bi in range(pr.ST_B):
+            for h in range(pr.ST_HQ):
+                s = st.q[bi, h] @ kd[bi, h // g].T * log2e_over_sqrt_d          # [Sq, cap], log2 units
+                s = np.where(np.arange(pr.ST_CAP)[None, :] < vis[bi][:, None], s, -np.inf)
+                tmax = s.reshape(pr.ST_SQ, -1, pr.ST_TILE).max(-1)              # [Sq, tiles]
+                for t in range(pr.ST_Q_LENS[bi]):
+                    row = tmax[t][np.isfinite(tmax[t])]
+                    assert len(row) == -(-vis[bi, t] // pr.ST_TILE)
+                    grow = np.diff(row)
+                    seen += len(grow)
+                    if pattern == "under8":
+                        assert (grow > 4.0).all() and (grow <= RESCALE_LOG2 - 0.05).all(), (bi, h, t, grow)
+                    else:
+                        assert (grow >= RESCALE_LOG2 + 0.05).all(), (bi, h, t, grow)
+    assert seen > 1000
+
+
+@pytest.mark.parametrize("d", [128, 64])
+@pytest.mark.parametrize("pattern,carry", ST_CASES, ids=ST_IDS)
+def test_staircase_values_are_exact_in_every_type(pattern, carry, d):
+    """Q in fp16 and bf16; what the cache holds in fp16, bf16 and E4M3 (and back);
+    the scales in fp32, none of the carried ones a power of two."""
+    st = pr.staircase(pattern, d, carry)
+    for name, a, types in (("q", st.q, (torch.float16, torch.bfloat16)),
+                           ("k", st.k, (torch.float16, torch.bfloat16, FP8)),
+                           ("v", st.v, (torch.float16, torch.bfloat16, FP8))):
+        t = torch.tensor(a)
+        for ty in types:
+            assert torch.equal(t.float().to(ty).double(), t), (name, ty)
+    assert float(np.abs(st.v).max()) <= 0.5 and np.abs(st.levels).max() <= 8
+    assert np.array_equal(st.k[..., 0], np.repeat(st.levels, pr.ST_TILE, axis=1)[:, None, :].repeat(pr.ST_HKV, 1))
+    for s in (st.k_scale, st.v_scale):
+        assert np.array_equal(s.astype(np.float32).astype(np.float64), s)
+        if carry == "scale":
+            assert (np.frexp(s)[0] != 0.5).all(), s
+        else:
+            assert (s == 1.0).all()
+    if carry == "scale":
+        assert (st.q[..., 0] == 1.0).all() and np.array_equal(st.k_scale, st.delta)
+    else:
+        assert np.array_equal(st.q[0, :, 0, 0], np.repeat(st.delta, pr.ST_HQ // pr.ST_HKV))
+    if not st.noisy:
+        assert not st.q[..., 1:].any()
+
+
+@pytest.mark.parametrize("causal", [True, False], ids=["causal", "full"])
+@pytest.mark.parametrize("d", [128, 64])
+@pytest.mark.parametrize("dtype", dr.DTYPES)
+@pytest.mark.parametrize("pattern,carry", ST_CASES, ids=ST_IDS)
+def test_staircase_reference_alone_stays_inside_half_the_gates(pattern, carry, dtype, d, causal):
+    """The model of the roundings the design allows (prefill_refs.st_model)
+    against contract_f64 on the same inputs: at most HALF of each gate, for
+    every pattern, dtype, head_dim and mask the GPU tests use."""
+    st = pr.staircase(pattern, d, carry)
+    o64, lse64, smax = pr.st_contract(pattern, d, carry, causal)
+    om, lm = pr.st_model(st, dtype, pr.ST_KV_LENS, pr.ST_Q_LENS, causal)
+    gate = dr.GATE_F16 if dtype is torch.float16 else dr.GATE_BF16
+    lgate = 2.0 ** -10 * smax + 1e-5
+    for bi, n in enumerate(pr.ST_Q_LENS):
+        assert np.array_equal(np.isneginf(lm[bi, :, :n]), np.isneginf(lse64[bi, :, :n]))
+        fin = np.isfinite(lse64[bi, :, :n])
+        oerr = float(np.abs(om[bi, :, :n] - o64[bi, :, :n]).max())
+        lerr = float(np.abs(lm[bi, :, :n][fin] - lse64[bi, :, :n][fin]).max())
+        print(f"{pattern} {carry} {dr.name(dtype)} d={d} causal={causal} b={bi}: O {oerr:.3e} of {gate:.0e}, "
+              f"LSE {lerr:.3e} of {lgate:.3e}")
+        assert oerr <= gate / 2, (bi, oerr)
+        assert lerr <= lgate / 2, (bi, lerr, lgate)
+
+
+@pytest.mark.parametrize("causal", [True, False], ids=["causal", "full"])
+@pytest.mark.parametrize("d", [128, 64])
+@pytest.mark.parametrize("pattern", list(pr.ST_PATTERNS))
+def test_staircase_oracle_agrees_with_the_contract(pattern, d, causal):
+    """fp16 on a 16-bit cache is judged by the CPU oracle: on these inputs it and
+    contract_f64 agree within half the gate."""
+    st = pr.staircase(pattern, d, "q")
+    host = tuple(dr.bits(torch.tensor(a).to(torch.float16)) for a in (st.q, st.k, st.v))
+    oo = pr.oracle_rows(*host, pr.ST_KV_LENS, pr.ST_Q_LENS, causal).view(np.float16).astype(np.float64)
+    o64 = pr.st_contract(pattern, d, "q", causal)[0]
+    for bi, n in enumerate(pr.ST_Q_LENS):
+        err = float(np.abs(oo[bi, :, :n] - o64[bi, :, :n]).max())
+        print(f"{pattern} d={d} causal={causal} b={bi}: |oracle - f64| {err:.3e}")
+        assert err <= dr.GATE_F16 / 2, (bi, err)
