@@ -13,7 +13,7 @@ extern "C" int fa_decode_f16(const void* q, const void* k, const void* v, void* 
                              int head_dim, const int* kv_lens, int causal, int num_splits,
                              void* workspace, unsigned long long ws_bytes, void* hip_stream) {
   return decode_entry<false, false>(FA_DTYPE_F16, q, k, v, o, lse, batch, heads_q, heads_kv, seqlen_q,
-                                    kv_capacity, head_dim, {}, kv_lens, causal, num_splits, workspace,
+                                    kv_capacity, head_dim, {}, kv_lens, causal, 0, num_splits, workspace,
                                     ws_bytes, hip_stream, nullptr, nullptr);
 }
 
@@ -22,7 +22,7 @@ extern "C" int fa_decode_bf16(const void* q, const void* k, const void* v, void*
                               int head_dim, const int* kv_lens, int causal, int num_splits,
                               void* workspace, unsigned long long ws_bytes, void* hip_stream) {
   return decode_entry<false, false>(FA_DTYPE_BF16, q, k, v, o, lse, batch, heads_q, heads_kv, seqlen_q,
-                                    kv_capacity, head_dim, {}, kv_lens, causal, num_splits, workspace,
+                                    kv_capacity, head_dim, {}, kv_lens, causal, 0, num_splits, workspace,
                                     ws_bytes, hip_stream, nullptr, nullptr);
 }
 

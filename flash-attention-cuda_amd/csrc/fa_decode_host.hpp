@@ -132,6 +132,16 @@ static int decode_launch_nb(int nb, const P& p, unsigned grid, hipStream_t strea
   }
 }
 
+// The capacity a windowed decode plans its split from: the tiles a call can
+// touch are those holding [len - Sq + 1 - W, len), at most ceil((W + Sq - 1) /
+// 64) + 1 of them.  Callers size the workspace with fa_decode_ws_bytes at this
+// capacity (window <= 0: the capacity itself).
+inline int decode_window_capacity(int kv_capacity, int seqlen_q, int window) {
+  if (window <= 0) return kv_capacity;
+  const long long eff = 64 * (((long long)window + seqlen_q - 1 + 63) / 64) + 64;
+  return (int)std::min<long long>(kv_capacity, eff);
+}
+
 // what the paged entries take in place of kv_capacity
 struct DecodePages {
   int num_pages, page_size;
@@ -144,18 +154,27 @@ struct DecodePages {
 // page_size; otherwise `pg` is unused.  KV8: the cache holds E4M3 bytes and
 // k_scale / v_scale go to the kernel; otherwise they are unused.  The twelve
 // kernels a <PAGED, KV8> pair can launch are instantiated from here.
-template <bool PAGED, bool KV8>
+// WIN (the fa_decode_win_* entries, fa_decode_win*.hip): `window` is the
+// sliding window W and the kernels are the Windowed<> instantiations; a
+// negative W is refused with the negative shapes, W > 0 without causal right
+// after the seqlen_q check, W = 0 (no window) runs as W = capacity, which
+// masks nothing, and num_splits = 0 plans from decode_window_capacity().
+// Without WIN `window` is not looked at (the entries pass 0).
+template <bool PAGED, bool KV8, bool WIN = false>
 static int decode_entry(int dtype, const void* q, const void* k, const void* v, void* o, float* lse,
                         int batch, int heads_q, int heads_kv, int seqlen_q, int kv_capacity,
                         int head_dim, const DecodePages& pg, const int* kv_lens, int causal,
-                        int num_splits, void* ws, unsigned long long ws_bytes, void* hip_stream,
-                        const float* k_scale, const float* v_scale) {
-  using P = std::conditional_t<PAGED, std::conditional_t<KV8, DecodePagedKv8Params, DecodePagedParams>,
-                               std::conditional_t<KV8, DecodeKv8Params, DecodeParams>>;
+                        int window, int num_splits, void* ws, unsigned long long ws_bytes,
+                        void* hip_stream, const float* k_scale, const float* v_scale) {
+  using P0 = std::conditional_t<PAGED, std::conditional_t<KV8, DecodePagedKv8Params, DecodePagedParams>,
+                                std::conditional_t<KV8, DecodeKv8Params, DecodeParams>>;
+  using P = std::conditional_t<WIN, Windowed<P0>, P0>;
   if (batch < 0 || heads_q < 0 || heads_kv < 0 || kv_capacity < 0 || head_dim < 0 || num_splits < 0)
     return FA_ERR_BAD_SHAPE;
+  if (WIN && window < 0) return FA_ERR_BAD_SHAPE;
   if (head_dim != 128 && head_dim != 64) return FA_ERR_UNSUPPORTED_HEAD_DIM;
   if (seqlen_q < 1 || seqlen_q > 16) return FA_ERR_BAD_SHAPE;
+  if (WIN && window > 0 && !causal) return FA_ERR_BAD_SHAPE;
   if constexpr (PAGED) {
     // a 64-key tile must not straddle two pages
     if (pg.page_size <= 0 || pg.page_size % 64 != 0) return FA_ERR_BAD_SHAPE;
@@ -189,7 +208,10 @@ static int decode_entry(int dtype, const void* q, const void* k, const void* v, 
   if (!q || !k || !v || !o || (PAGED && !pg.block_table)) return FA_ERR_NULL_POINTER;
   const DecodeGeom ge = decode_geom(batch, heads_q, heads_kv, seqlen_q);
   if (num_splits > kDecodeMaxSplits) return FA_ERR_BAD_CONFIG;
-  const int ns = num_splits > 0 ? num_splits : decode_plan(ge, kv_capacity);
+  const int ns = num_splits > 0
+                     ? num_splits
+                     : decode_plan(ge, WIN ? decode_window_capacity(kv_capacity, seqlen_q, window)
+                                           : kv_capacity);
   if (ge.units * ns > 0x7fffffffLL) return FA_ERR_BAD_SHAPE;
   if (ns > 1) {
     // one arrival counter per unit in the 64-KB region (the plan splits only
@@ -217,6 +239,7 @@ static int decode_entry(int dtype, const void* q, const void* k, const void* v, 
   p.causal = causal ? 1 : 0;
   p.c = 1.4426950408889634f / sqrtf((float)head_dim);
   if (ns > 1) decode_set_workspace(p, ge, ns, ws);
+  if constexpr (WIN) p.window = window > 0 ? std::min(window, kv_capacity) : kv_capacity;
   if constexpr (PAGED) {
     p.table = pg.block_table;
     p.max_pages = pg.max_pages_per_seq;

@@ -98,6 +98,28 @@ struct DecodePagedKv8Params : DecodePagedParams {
   const float* v_scale;
 };
 
+// The sliding-window entries (fa_decode_win_*, fa_prefill[_varlen]_win_*) pass
+// their parameters as Windowed<one of the structs above / of
+// fa_prefill_kernel.hpp>: the kernels take WIN from the type, so the entries
+// without a window keep their instantiations and their symbols (DESIGN.md
+// §3.0m).  window = W >= 1: a row at position pos sees the keys
+//   max(0, pos - W + 1) <= j <= pos
+// (its own included: Hugging Face's sliding_window = W, flash-attn's
+// window_size = (W - 1, 0)).  The host clamps W to the capacity, past which it
+// changes nothing, so pos - W cannot overflow.
+template <class Base>
+struct Windowed : Base {
+  int window;
+};
+template <class P>
+struct ParamsWindowed : std::false_type {};
+template <class Base>
+struct ParamsWindowed<Windowed<Base>> : std::true_type {};
+// an offset no K/V descriptor's range reaches: the load returns zeros and
+// moves no memory.  The windowed kernels give it to the lanes whose row of the
+// first tile lies below the window, so those rows are not read at all.
+constexpr int kBelowWindow = 0x7ffffff0;
+
 // 8 E4M3 bytes (two words) -> 8 elements of T.  Exact: every finite E4M3 code
 // is representable in f16 and in bf16, and the scale operand is 1.0.
 template <class T>
@@ -195,6 +217,7 @@ template <class T, int HDIM, int NB, bool PAGED = false, class P = DecodeParams,
 __global__ __launch_bounds__(256, 1) void fa_decode_kernel(P p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr bool KV8 = !std::is_same<KV, T>::value;
+  constexpr bool WIN = ParamsWindowed<P>::value;
   static_assert(!KV8 || std::is_same<KV, unsigned char>::value, "the cache holds T or E4M3 bytes");
   constexpr int ROW = 2 * HDIM;      // bytes per Q/O row
   constexpr int CROW = KV8 ? HDIM : 2 * HDIM;  // bytes per K/V cache row
@@ -227,8 +250,19 @@ __global__ __launch_bounds__(256, 1) void fa_decode_kernel(P p) {
   int len = p.kv_lens ? p.kv_lens[b] : p.cap;
   len = __builtin_amdgcn_readfirstlane(min(max(len, 0), p.cap));
   const int ntiles = (len + 63) >> 6;
-  const int t0 = (int)((long long)ntiles * piece / ns);
-  const int t1 = (int)((long long)ntiles * (piece + 1) / ns);
+  // WIN: the first key any row sees is row 0's lower bound; the pieces divide
+  // the tiles from its tile on (an empty piece hands off l = 0 like one past
+  // ntiles).  lo_in: the rows of tile tlo below that key, which are not read.
+  [[maybe_unused]] int win = 0, kv_lo = 0, tlo = 0;
+  if constexpr (WIN) {
+    win = p.window;
+    kv_lo = max(0, len - p.sq + 1 - win);
+    tlo = kv_lo >> 6;
+  }
+  const int t0 = WIN ? tlo + (int)((long long)(ntiles - tlo) * piece / ns)
+                     : (int)((long long)ntiles * piece / ns);
+  const int t1 = WIN ? tlo + (int)((long long)(ntiles - tlo) * (piece + 1) / ns)
+                     : (int)((long long)ntiles * (piece + 1) / ns);
 
   const int row0 = rg * RW;  // first row of this group among the kv head's rows
   const size_t qrow = ((size_t)b * p.hq + (size_t)hk * p.group) * p.sq;  // [B*Hq*Sq] row of r = 0
@@ -289,6 +323,9 @@ __global__ __launch_bounds__(256, 1) void fa_decode_kernel(P p) {
     lim[nb] = p.causal ? len - p.sq + 1 + r % p.sq : len;
   }
   const int mask_from = p.causal ? len - p.sq + 1 : len;  // tiles ending past it need the mask
+  // WIN: row r also masks the keys below lim - win; tiles starting below the
+  // last row's bound need the mask
+  [[maybe_unused]] const int mask_below = WIN ? len - win : 0;
 
   // K: A-operand row r16 of 16-key block cb is key 16 cb + sigma(r16), so the
   // S^T accumulator of lane (g, r16) holds keys 16 cb + 4 sg + i (the order
@@ -369,6 +406,44 @@ __global__ __launch_bounds__(256, 1) void fa_decode_kernel(P p) {
       vr[ps] = __builtin_amdgcn_raw_buffer_load_b128(rv, (int)(base + ps * RPW * CROW), 0, 0);
   };
 
+  // WIN: a wave's first tile may be tile tlo, whose rows below kv_lo are
+  // addressed past the range (zeros, not read).  (Twins of load_k / load_v, not
+  // a flag on them: one generic lambda each changed the register allocation of
+  // the kernels without a window, whose device code is to stay what it was.)
+  [[maybe_unused]] auto load_k_first = [&](int tl) {
+    unsigned base;
+    if constexpr (PAGED)
+      base = tofs + kvo;
+    else
+      base = (unsigned)min(64 * tl, len) * CROW + kvo;
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb) {
+      const bool in = 64 * tl + 16 * cb + (int)krow >= kv_lo;
+      if constexpr (KV8) {
+#pragma unroll
+        for (int tt = 0; tt < NTQ / 2; ++tt)
+          kq[cb][tt] = __builtin_amdgcn_raw_buffer_load_b128(
+              rk, in ? (int)(base + 16 * cb * CROW + 64 * tt) : kBelowWindow, 0, 0);
+      } else {
+#pragma unroll
+        for (int t = 0; t < NTQ; ++t)
+          kf[cb][t] = __builtin_bit_cast(
+              tx8, buf_load16(rk, in ? (int)(base + 16 * cb * ROW + 64 * t) : kBelowWindow));
+      }
+    }
+  };
+  [[maybe_unused]] auto load_v_first = [&](int tl) {
+    unsigned base;
+    if constexpr (PAGED)
+      base = tofs + vvo;
+    else
+      base = (unsigned)min(64 * tl, len) * CROW + vvo;
+#pragma unroll
+    for (int ps = 0; ps < NPASS; ++ps)
+      vr[ps] = __builtin_amdgcn_raw_buffer_load_b128(
+          rv, 64 * tl + ps * RPW + vrl >= kv_lo ? (int)(base + ps * RPW * CROW) : kBelowWindow, 0, 0);
+  };
+
   int tile = t0 + wave;
   const int tend = tile < t1 ? t1 : tile;  // a wave with no tile loads nothing
 
@@ -412,8 +487,13 @@ __global__ __launch_bounds__(256, 1) void fa_decode_kernel(P p) {
     }
     tile_at(tile < tend, tile, pg, r);
   }
-  load_k(tile < tend ? tile : ntiles);
-  load_v(tile < tend ? tile : ntiles);
+  if constexpr (WIN) {
+    load_k_first(tile < tend ? tile : ntiles);
+    load_v_first(tile < tend ? tile : ntiles);
+  } else {
+    load_k(tile < tend ? tile : ntiles);
+    load_v(tile < tend ? tile : ntiles);
+  }
   for (; tile < tend; tile += 4) {
     const int nxt = tile + 4 < tend ? tile + 4 : ntiles;
     if constexpr (PAGED) {
@@ -431,7 +511,7 @@ __global__ __launch_bounds__(256, 1) void fa_decode_kernel(P p) {
     // next K can be issued before the softmax; else block by block (16 score
     // registers live at a time)
     const int kv0 = 64 * tile;
-    const bool need_mask = kv0 + 64 > mask_from;
+    const bool need_mask = WIN ? kv0 + 64 > mask_from || kv0 < mask_below : kv0 + 64 > mask_from;
     f32x4 s[NB][4];
     tx8 pf[NB][2];
     auto qk = [&](int nb) {
@@ -459,7 +539,12 @@ __global__ __launch_bounds__(256, 1) void fa_decode_kernel(P p) {
         for (int cb = 0; cb < 4; ++cb)
 #pragma unroll
           for (int i = 0; i < 4; ++i)
-            s[nb][cb][i] = kv0 + 16 * cb + 4 * sg + i < lim[nb] ? s[nb][cb][i] : ninf();
+            if constexpr (WIN)  // lim - win <= key < lim, as one unsigned compare
+              s[nb][cb][i] = (unsigned)(lim[nb] - 1 - (kv0 + 16 * cb + 4 * sg + i)) < (unsigned)win
+                                 ? s[nb][cb][i]
+                                 : ninf();
+            else
+              s[nb][cb][i] = kv0 + 16 * cb + 4 * sg + i < lim[nb] ? s[nb][cb][i] : ninf();
       }
       float mx = s[nb][0][0];
 #pragma unroll

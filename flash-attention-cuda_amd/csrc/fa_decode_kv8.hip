@@ -14,7 +14,7 @@ extern "C" int fa_decode_kv8_f16(const void* q, const void* k, const void* v, vo
                                  void* workspace, unsigned long long ws_bytes, void* hip_stream,
                                  const float* k_scale, const float* v_scale) {
   return decode_entry<false, true>(FA_DTYPE_F16, q, k, v, o, lse, batch, heads_q, heads_kv, seqlen_q,
-                                   kv_capacity, head_dim, {}, kv_lens, causal, num_splits, workspace,
+                                   kv_capacity, head_dim, {}, kv_lens, causal, 0, num_splits, workspace,
                                    ws_bytes, hip_stream, k_scale, v_scale);
 }
 
@@ -24,6 +24,6 @@ extern "C" int fa_decode_kv8_bf16(const void* q, const void* k, const void* v, v
                                   void* workspace, unsigned long long ws_bytes, void* hip_stream,
                                   const float* k_scale, const float* v_scale) {
   return decode_entry<false, true>(FA_DTYPE_BF16, q, k, v, o, lse, batch, heads_q, heads_kv, seqlen_q,
-                                   kv_capacity, head_dim, {}, kv_lens, causal, num_splits, workspace,
+                                   kv_capacity, head_dim, {}, kv_lens, causal, 0, num_splits, workspace,
                                    ws_bytes, hip_stream, k_scale, v_scale);
 }

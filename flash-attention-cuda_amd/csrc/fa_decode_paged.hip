@@ -16,7 +16,7 @@ extern "C" int fa_decode_paged_f16(const void* q, const void* k_pages, const voi
   return decode_entry<true, false>(FA_DTYPE_F16, q, k_pages, v_pages, o, lse, batch, heads_q, heads_kv,
                                    seqlen_q, 0, head_dim,
                                    {num_pages, page_size, block_table, max_pages_per_seq}, kv_lens,
-                                   causal, num_splits, workspace, ws_bytes, hip_stream, nullptr, nullptr);
+                                   causal, 0, num_splits, workspace, ws_bytes, hip_stream, nullptr, nullptr);
 }
 
 extern "C" int fa_decode_paged_bf16(const void* q, const void* k_pages, const void* v_pages, void* o,
@@ -28,5 +28,5 @@ extern "C" int fa_decode_paged_bf16(const void* q, const void* k_pages, const vo
   return decode_entry<true, false>(FA_DTYPE_BF16, q, k_pages, v_pages, o, lse, batch, heads_q, heads_kv,
                                    seqlen_q, 0, head_dim,
                                    {num_pages, page_size, block_table, max_pages_per_seq}, kv_lens,
-                                   causal, num_splits, workspace, ws_bytes, hip_stream, nullptr, nullptr);
+                                   causal, 0, num_splits, workspace, ws_bytes, hip_stream, nullptr, nullptr);
 }

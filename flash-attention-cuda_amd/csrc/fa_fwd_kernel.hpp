@@ -306,6 +306,7 @@ struct M16 {
   f32x4 lacc[QB];     // running row sums l (ones . P on the matrix pipe, in the PV chain)
   float l32[QB];      // L32_: this lane's share of l (fp32 exponentials)
   bool have_ref;     // wave-uniform: a tile has set m_ref
+  bool seen[QB];     // softmax<.., WIN>: per row, a tile has set m_ref
   float c;
 
   __device__ __forceinline__ void init(int lane_, float c_) {
@@ -330,6 +331,7 @@ struct M16 {
       m_ref[b] = 0.f;
       lacc[b] = f32x4{};
       l32[b] = 0.f;
+      seen[b] = false;
     }
     have_ref = false;
   }
@@ -454,8 +456,15 @@ struct M16 {
         if constexpr (L32_) asm volatile("" : "+v"(l32[b]));
       }
   }
-  template <bool CAUSAL>
-  __device__ __forceinline__ void softmax(int kv0, int kv_hi, int qw, float /*c*/, bool need_mask) {
+  // WIN (the windowed prefill kernels, fa_prefill_kernel.hpp): row q also
+  // masks the keys below q - win + 1, and the reference is established per
+  // row, at the first tile in which the row sees a key (seen[]): with a lower
+  // bound a wave's first tile no longer holds a key of every row, and a row
+  // left at m_ref = 0 whose real scores all lie far below zero would lose
+  // every P to underflow.  The default is the code without a window.
+  template <bool CAUSAL, bool WIN = false>
+  __device__ __forceinline__ void softmax(int kv0, int kv_hi, int qw, float /*c*/, bool need_mask,
+                                          [[maybe_unused]] int win = 0) {
     if constexpr (kScaleS) {
 #pragma unroll
       for (int b = 0; b < QB; ++b)
@@ -471,7 +480,8 @@ struct M16 {
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
             const int kv = kv0 + 16 * cb + 4 * sg + i;
-            const bool ok = kv < kv_hi && (!CAUSAL || kv <= qrow);
+            bool ok = kv < kv_hi && (!CAUSAL || kv <= qrow);
+            if constexpr (WIN) ok = ok && kv > qrow - win;
             s[b][cb][i] = ok ? s[b][cb][i] : ninf();
           }
       }
@@ -479,7 +489,7 @@ struct M16 {
     // row max relative to m_ref; shift m_ref (and rescale O, l) only when it
     // grew by more than RESCALE_LOG2 -- P then stays <= 2^RESCALE_LOG2
     float mx[QB];
-    bool grow = !have_ref;
+    bool grow = WIN ? false : !have_ref;
 #pragma unroll
     for (int b = 0; b < QB; ++b) {
       float m = s[b][0][0];
@@ -492,6 +502,8 @@ struct M16 {
       // (wave-uniform) rescale path
       mx[b] = m;
       grow |= mx[b] > RESCALE_LOG2;
+      // WIN: some lane of a row without a reference sees a key
+      if constexpr (WIN) grow |= !seen[b] && mx[b] != ninf();
     }
     if (__any(grow)) {
 #pragma unroll
@@ -500,9 +512,20 @@ struct M16 {
       for (int b = 0; b < QB; ++b) {
         // first tile: centre on the max; later: only ever move m_ref up.
         // A row with every key masked (mx = -inf) keeps m_ref.
-        float sh = have_ref ? fmaxf(mx[b], 0.f) : mx[b];
+        // WIN: "first tile" is per row, the first in which it sees a key
+        const bool had = WIN ? seen[b] : have_ref;
+        float sh = had ? fmaxf(mx[b], 0.f) : mx[b];
         sh = sh == ninf() ? 0.f : sh;
-        if (have_ref) {
+        if constexpr (WIN) {
+          // a row's first reference: O and l are still zero and stay so (the
+          // factor 2^-sh of a far-negative sh would be inf)
+          const float alpha = had ? __builtin_amdgcn_exp2f(-sh) : 1.0f;
+#pragma unroll
+          for (int e = 0; e < NE; ++e) acc[b][e] *= alpha;
+          lacc[b] *= alpha;
+          if constexpr (L32_) l32[b] *= alpha;
+          seen[b] = had || mx[b] != ninf();
+        } else if (have_ref) {
           const float alpha = __builtin_amdgcn_exp2f(-sh);
 #pragma unroll
           for (int e = 0; e < NE; ++e) acc[b][e] *= alpha;
@@ -572,11 +595,11 @@ struct M16 {
       __builtin_amdgcn_sched_group_barrier(0x008, 2 * kQkPipe, 0);
     }
   }
-  template <bool CAUSAL>
+  template <bool CAUSAL, bool WIN = false>
   __device__ __forceinline__ void tile(const char* kb, const char* vb, int kv0, int kv_hi, int qw,
-                                       float c_, bool need_mask) {
+                                       float c_, bool need_mask, int win = 0) {
     qk(kb);
-    softmax<CAUSAL>(kv0, kv_hi, qw, c_, need_mask);
+    softmax<CAUSAL, WIN>(kv0, kv_hi, qw, c_, need_mask, win);
     pv(vb);
   }
 

@@ -11,7 +11,7 @@ extern "C" int fa_prefill_f16(const void* q, const void* k, const void* v, void*
                               int head_dim, const int* kv_lens, const int* q_lens, int causal,
                               void* hip_stream) {
   return prefill_entry<false, false>(FA_DTYPE_F16, q, k, v, o, lse, batch, heads_q, heads_kv, seqlen_q,
-                                     kv_capacity, head_dim, {}, kv_lens, q_lens, causal, hip_stream,
+                                     kv_capacity, head_dim, {}, kv_lens, q_lens, causal, 0, hip_stream,
                                      nullptr, nullptr);
 }
 
@@ -20,6 +20,6 @@ extern "C" int fa_prefill_bf16(const void* q, const void* k, const void* v, void
                                int head_dim, const int* kv_lens, const int* q_lens, int causal,
                                void* hip_stream) {
   return prefill_entry<false, false>(FA_DTYPE_BF16, q, k, v, o, lse, batch, heads_q, heads_kv, seqlen_q,
-                                     kv_capacity, head_dim, {}, kv_lens, q_lens, causal, hip_stream,
+                                     kv_capacity, head_dim, {}, kv_lens, q_lens, causal, 0, hip_stream,
                                      nullptr, nullptr);
 }

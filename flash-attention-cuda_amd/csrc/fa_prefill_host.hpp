@@ -35,17 +35,26 @@ static int prefill_launch_inst(const P& p, unsigned grid, hipStream_t stream) {
 // `seqlen_q` is total_q, `q_lens` is cu_seqlens (int32[batch + 1], required)
 // and `batch` the number of sequences.  The grid is sized from shapes alone:
 // heads_q * (total_q / 128 + batch) workgroups (fa_varlen_map.hpp).
-template <bool PAGED, bool KV8, bool VARLEN = false>
+// WIN (the fa_prefill[_varlen]_win_* entries, fa_prefill*_win*.hip): `window`
+// is the sliding window W and the kernels are the Windowed<> instantiations,
+// with decode_entry's rules: a negative W is refused with the negative shapes,
+// W > 0 without causal right after the seqlen_q check, and W = 0 (no window)
+// runs as W = capacity.  Without WIN `window` is not looked at.
+template <bool PAGED, bool KV8, bool VARLEN = false, bool WIN = false>
 static int prefill_entry(int dtype, const void* q, const void* k, const void* v, void* o, float* lse,
                          int batch, int heads_q, int heads_kv, int seqlen_q, int kv_capacity,
                          int head_dim, const DecodePages& pg, const int* kv_lens, const int* q_lens,
-                         int causal, void* hip_stream, const float* k_scale, const float* v_scale) {
-  using P = std::conditional_t<PAGED, std::conditional_t<KV8, PrefillPagedKv8Params, PrefillPagedParams>,
-                               std::conditional_t<KV8, PrefillKv8Params, PrefillParams>>;
+                         int causal, int window, void* hip_stream, const float* k_scale,
+                         const float* v_scale) {
+  using P0 = std::conditional_t<PAGED, std::conditional_t<KV8, PrefillPagedKv8Params, PrefillPagedParams>,
+                                std::conditional_t<KV8, PrefillKv8Params, PrefillParams>>;
+  using P = std::conditional_t<WIN, Windowed<P0>, P0>;
   if (batch < 0 || heads_q < 0 || heads_kv < 0 || kv_capacity < 0 || head_dim < 0)
     return FA_ERR_BAD_SHAPE;
+  if (WIN && window < 0) return FA_ERR_BAD_SHAPE;
   if (head_dim != 128 && head_dim != 64) return FA_ERR_UNSUPPORTED_HEAD_DIM;
   if (VARLEN ? seqlen_q < 0 : seqlen_q < 1) return FA_ERR_BAD_SHAPE;
+  if (WIN && window > 0 && !causal) return FA_ERR_BAD_SHAPE;
   if constexpr (PAGED) {
     // a 64-key tile must not straddle two pages
     if (pg.page_size <= 0 || pg.page_size % 64 != 0) return FA_ERR_BAD_SHAPE;
@@ -104,6 +113,7 @@ static int prefill_entry(int dtype, const void* q, const void* k, const void* v,
   p.bhk = (unsigned)batch * (unsigned)heads_kv;
   p.causal = causal ? 1 : 0;
   p.c = 1.4426950408889634f / sqrtf((float)head_dim);
+  if constexpr (WIN) p.window = window > 0 ? std::min(window, kv_capacity) : kv_capacity;
   if constexpr (PAGED) {
     p.table = pg.block_table;
     p.max_pages = pg.max_pages_per_seq;

@@ -111,10 +111,26 @@ template <class P>
 struct PrefillIsPacked : std::false_type {};
 template <class Base>
 struct PrefillIsPacked<PrefillPacked<Base>> : std::true_type {};
+// the packed windowed entries pass PrefillPacked<Windowed<Base>>
+template <class Base>
+struct ParamsWindowed<PrefillPacked<Base>> : ParamsWindowed<Base> {};
 
+// WIN (P = [PrefillPacked<]Windowed<...>[>], the fa_prefill[_varlen]_win_*
+// entries; without causal the host admits W = 0 alone and the kernel applies
+// no lower bound): row t of the block also masks the keys below
+// off_b + t - W + 1.  The block's key range becomes [kv_lo, kv_hi) with
+// kv_lo = max(0, off_b + q0 - W + 1), its first row's lower bound: the tile
+// loop, the contiguous descriptors and the paged look-ahead start at tile
+// tlo = kv_lo / 64, the rows of tile tlo below kv_lo are not loaded, and table
+// entries of pages wholly below kv_lo are not read.  A wave skips the MFMAs of
+// the tiles wholly below its lowest row's bound as it skips those above its
+// rows (it still stages and takes the barrier), and the softmax reference is
+// set per row (M16::softmax<.., WIN>).  All of it sits under
+// `if constexpr (WIN)`: the other instantiations carry none of it.
 template <class T, int HDIM, bool PAGED = false, class P = PrefillParams, class KV = T>
 __global__ __launch_bounds__(256, 2) void fa_prefill_kernel(P p) {
   constexpr bool VARLEN = PrefillIsPacked<P>::value;
+  constexpr bool WIN = ParamsWindowed<P>::value;
   __shared__ __attribute__((aligned(16))) char smem[kPrefillLdsBytes];
   constexpr bool KV8 = !std::is_same<KV, T>::value;
   static_assert(!KV8 || std::is_same<KV, unsigned char>::value, "the cache holds T or E4M3 bytes");
@@ -175,6 +191,18 @@ __global__ __launch_bounds__(256, 2) void fa_prefill_kernel(P p) {
   const int off = len - nq;  // keys before the chunk (negative: the leading rows see nothing)
   const int kv_hi = p.causal ? max(0, min(len, off + q0 + BM)) : len;
   const int ntiles = (kv_hi + BN - 1) / BN;
+  // WIN: the first key any row of the block sees (<= kv_hi: off + q0 < len),
+  // its tile, and the rows of that tile that lie below it
+  [[maybe_unused]] int win = 0, kv_lo = 0, tlo = 0, lo_in = 0;
+  if constexpr (WIN) {
+    // not causal (the host lets only W = 0 through): no lower bound, as no
+    // upper one -- a window past every row - key difference, so the mask,
+    // need_mask and the skip below are the plain kernel's
+    win = p.causal ? p.window : 0x7fffffff;
+    kv_lo = p.causal ? max(0, off + q0 - win + 1) : 0;
+    tlo = kv_lo / BN;
+    lo_in = kv_lo - BN * tlo;
+  }
   // the row the mask compares keys with; non-causal: past every key
   const int qwm = p.causal ? off + q0 + wave * RW : 0x3fffffff;
   const int qwl = wave * RW;  // this wave's first row within the block's descriptors
@@ -272,6 +300,20 @@ __global__ __launch_bounds__(256, 2) void fa_prefill_kernel(P p) {
       vst[i] = __builtin_amdgcn_raw_buffer_load_b128(rv, vvo + RPP * i * CROW, 0, 0);
     }
   };
+  // WIN, tile tlo (the prologue's): its rows below kv_lo are addressed past
+  // the range, so they come as zeros (a masked P = 0 meets a finite V) and
+  // are not read.  (A twin of issue_loads, not a flag on it: folding the two
+  // into one generic lambda changed the register allocation of the kernels
+  // without a window, whose device code is to stay what it was.)
+  [[maybe_unused]] auto issue_loads_first = [&]() {
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+      kst[i] = __builtin_amdgcn_raw_buffer_load_b128(
+          rk, kr0 + RPP * i >= lo_in ? kvo + RPP * i * CROW : kBelowWindow, 0, 0);
+      vst[i] = __builtin_amdgcn_raw_buffer_load_b128(
+          rv, vr0 + RPP * i >= lo_in ? vvo + RPP * i * CROW : kBelowWindow, 0, 0);
+    }
+  };
   auto write_lds = [&](char* kb) {
     char* vb = kb + TILE_BYTES;
 #pragma unroll
@@ -300,18 +342,31 @@ __global__ __launch_bounds__(256, 2) void fa_prefill_kernel(P p) {
   [[maybe_unused]] tab_t tab = nullptr;
   if constexpr (PAGED) {
     tab = (tab_t)(p.table + (size_t)b * p.max_pages);
-    const int pg0 = ntiles > 0 ? tab[0] : 0;
-    tile_at(0, pg0, 0);
-    rN = p.tpp > 1 ? 1 : 0;
-    pgN = ntiles > 1 ? tab[p.tpp > 1 ? 0 : 1] : 0;
-    jF = 2 / p.tpp, rF = 2 - jF * p.tpp;
+    if constexpr (WIN) {
+      // the same state, started at tile tlo (any block of its page)
+      const int j0 = tlo / p.tpp, j1 = (tlo + 1) / p.tpp;
+      const int pg0 = ntiles > tlo ? tab[j0] : 0;
+      tile_at(tlo, pg0, tlo - j0 * p.tpp);
+      rN = tlo + 1 - j1 * p.tpp;
+      pgN = ntiles > tlo + 1 ? tab[j1] : 0;
+      jF = (tlo + 2) / p.tpp, rF = tlo + 2 - jF * p.tpp;
+    } else {
+      const int pg0 = ntiles > 0 ? tab[0] : 0;
+      tile_at(0, pg0, 0);
+      rN = p.tpp > 1 ? 1 : 0;
+      pgN = ntiles > 1 ? tab[p.tpp > 1 ? 0 : 1] : 0;
+      jF = 2 / p.tpp, rF = 2 - jF * p.tpp;
+    }
   } else {
-    tile_at(0, 0, 0);
+    tile_at(WIN ? tlo : 0, 0, 0);
   }
 
   // prologue: unconditional, so every earlier load (Q included) has retired
   // before the loop and no in-loop MFMA waits on the prefetch
-  issue_loads();
+  if constexpr (WIN)
+    issue_loads_first();
+  else
+    issue_loads();
   // every prologue load is issued before the first VALU that waits on one
   // (else the scheduler hoists Q's scaling above the K/V loads)
   __builtin_amdgcn_sched_barrier(0);
@@ -335,14 +390,22 @@ __global__ __launch_bounds__(256, 2) void fa_prefill_kernel(P p) {
       if (++rF == p.tpp) rF = 0, ++jF;
     }
     // wave-uniform: does any key of this tile lie at/below some row of this wave?
-    if (kv0 <= qwm + RW - 1) {
+    if constexpr (WIN) {
+      // ... and at/above the lower bound of some row of this wave?  The mask
+      // is also needed where a key lies below the wave's highest lower bound
+      if (kv0 <= qwm + RW - 1 && kv0 + BN - 1 > qwm - win) {
+        const bool need_mask =
+            (kv0 + BN > kv_hi) || (kv0 + BN - 1 > qwm) || (kv0 < qwm + RW - win);
+        pol.template tile<true, true>(kb, kb + TILE_BYTES, kv0, kv_hi, qwm, csc, need_mask, win);
+      }
+    } else if (kv0 <= qwm + RW - 1) {
       const bool need_mask = (kv0 + BN > kv_hi) || (kv0 + BN - 1 > qwm);
       pol.template tile<true>(kb, kb + TILE_BYTES, kv0, kv_hi, qwm, csc, need_mask);
     }
     write_lds(kb_next);
     __syncthreads();
   };
-  int j = 0;
+  int j = WIN ? tlo : 0;
   for (; j + 1 < ntiles; j += 2) {
     step(j, std::integral_constant<int, 0>{});
     step(j + 1, std::integral_constant<int, 1>{});

@@ -13,7 +13,7 @@ extern "C" int fa_prefill_kv8_f16(const void* q, const void* k, const void* v, v
                                   int head_dim, const int* kv_lens, const int* q_lens, int causal,
                                   void* hip_stream, const float* k_scale, const float* v_scale) {
   return prefill_entry<false, true>(FA_DTYPE_F16, q, k, v, o, lse, batch, heads_q, heads_kv, seqlen_q,
-                                    kv_capacity, head_dim, {}, kv_lens, q_lens, causal, hip_stream,
+                                    kv_capacity, head_dim, {}, kv_lens, q_lens, causal, 0, hip_stream,
                                     k_scale, v_scale);
 }
 
@@ -22,6 +22,6 @@ extern "C" int fa_prefill_kv8_bf16(const void* q, const void* k, const void* v, 
                                    int head_dim, const int* kv_lens, const int* q_lens, int causal,
                                    void* hip_stream, const float* k_scale, const float* v_scale) {
   return prefill_entry<false, true>(FA_DTYPE_BF16, q, k, v, o, lse, batch, heads_q, heads_kv, seqlen_q,
-                                    kv_capacity, head_dim, {}, kv_lens, q_lens, causal, hip_stream,
+                                    kv_capacity, head_dim, {}, kv_lens, q_lens, causal, 0, hip_stream,
                                     k_scale, v_scale);
 }

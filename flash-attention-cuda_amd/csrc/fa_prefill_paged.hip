@@ -14,7 +14,7 @@ extern "C" int fa_prefill_paged_f16(const void* q, const void* k_pages, const vo
   return prefill_entry<true, false>(FA_DTYPE_F16, q, k_pages, v_pages, o, lse, batch, heads_q, heads_kv,
                                     seqlen_q, 0, head_dim,
                                     {num_pages, page_size, block_table, max_pages_per_seq}, kv_lens,
-                                    q_lens, causal, hip_stream, nullptr, nullptr);
+                                    q_lens, causal, 0, hip_stream, nullptr, nullptr);
 }
 
 extern "C" int fa_prefill_paged_bf16(const void* q, const void* k_pages, const void* v_pages, void* o,
@@ -25,5 +25,5 @@ extern "C" int fa_prefill_paged_bf16(const void* q, const void* k_pages, const v
   return prefill_entry<true, false>(FA_DTYPE_BF16, q, k_pages, v_pages, o, lse, batch, heads_q, heads_kv,
                                     seqlen_q, 0, head_dim,
                                     {num_pages, page_size, block_table, max_pages_per_seq}, kv_lens,
-                                    q_lens, causal, hip_stream, nullptr, nullptr);
+                                    q_lens, causal, 0, hip_stream, nullptr, nullptr);
 }

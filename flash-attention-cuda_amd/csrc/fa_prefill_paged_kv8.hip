@@ -18,7 +18,7 @@ extern "C" int fa_prefill_paged_kv8_f16(const void* q, const void* k_pages, cons
   return prefill_entry<true, true>(FA_DTYPE_F16, q, k_pages, v_pages, o, lse, batch, heads_q, heads_kv,
                                    seqlen_q, 0, head_dim,
                                    {num_pages, page_size, block_table, max_pages_per_seq}, kv_lens,
-                                   q_lens, causal, hip_stream, k_scale, v_scale);
+                                   q_lens, causal, 0, hip_stream, k_scale, v_scale);
 }
 
 extern "C" int fa_prefill_paged_kv8_bf16(const void* q, const void* k_pages, const void* v_pages, void* o,
@@ -30,5 +30,5 @@ extern "C" int fa_prefill_paged_kv8_bf16(const void* q, const void* k_pages, con
   return prefill_entry<true, true>(FA_DTYPE_BF16, q, k_pages, v_pages, o, lse, batch, heads_q, heads_kv,
                                    seqlen_q, 0, head_dim,
                                    {num_pages, page_size, block_table, max_pages_per_seq}, kv_lens,
-                                   q_lens, causal, hip_stream, k_scale, v_scale);
+                                   q_lens, causal, 0, hip_stream, k_scale, v_scale);
 }

@@ -13,7 +13,7 @@ using namespace fa;
       int heads_q, int heads_kv, int total_q, int kv_capacity, int head_dim, const int* kv_lens,      \
       const int* cu_seqlens_q, int causal, void* hip_stream) {                                        \
     return prefill_entry<false, false, true>(DTYPE, q, k, v, o, lse, batch, heads_q, heads_kv,        \
-        total_q, kv_capacity, head_dim, {}, kv_lens, cu_seqlens_q, causal, hip_stream, nullptr,       \
+        total_q, kv_capacity, head_dim, {}, kv_lens, cu_seqlens_q, causal, 0, hip_stream, nullptr,    \
         nullptr);                                                                                     \
   }
 FA_PREFILL_VARLEN(f16, FA_DTYPE_F16)

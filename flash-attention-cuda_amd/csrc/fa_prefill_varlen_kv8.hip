@@ -14,7 +14,7 @@ using namespace fa;
       const int* cu_seqlens_q, int causal, void* hip_stream, const float* k_scale,                    \
       const float* v_scale) {                                                                         \
     return prefill_entry<false, true, true>(DTYPE, q, k, v, o, lse, batch, heads_q, heads_kv,         \
-        total_q, kv_capacity, head_dim, {}, kv_lens, cu_seqlens_q, causal, hip_stream, k_scale,       \
+        total_q, kv_capacity, head_dim, {}, kv_lens, cu_seqlens_q, causal, 0, hip_stream, k_scale,    \
         v_scale);                                                                                     \
   }
 FA_PREFILL_VARLEN(f16, FA_DTYPE_F16)

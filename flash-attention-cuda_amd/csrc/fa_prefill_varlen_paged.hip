@@ -15,7 +15,7 @@ using namespace fa;
       const int* cu_seqlens_q, int causal, void* hip_stream) {                                        \
     return prefill_entry<true, false, true>(DTYPE, q, k_pages, v_pages, o, lse, batch, heads_q,       \
         heads_kv, total_q, 0, head_dim, {num_pages, page_size, block_table, max_pages_per_seq},       \
-        kv_lens, cu_seqlens_q, causal, hip_stream, nullptr, nullptr);                                 \
+        kv_lens, cu_seqlens_q, causal, 0, hip_stream, nullptr, nullptr);                              \
   }
 FA_PREFILL_VARLEN(f16, FA_DTYPE_F16)
 FA_PREFILL_VARLEN(bf16, FA_DTYPE_BF16)

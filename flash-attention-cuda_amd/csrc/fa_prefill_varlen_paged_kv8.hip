@@ -16,7 +16,7 @@ using namespace fa;
       const float* v_scale) {                                                                         \
     return prefill_entry<true, true, true>(DTYPE, q, k_pages, v_pages, o, lse, batch, heads_q,        \
         heads_kv, total_q, 0, head_dim, {num_pages, page_size, block_table, max_pages_per_seq},       \
-        kv_lens, cu_seqlens_q, causal, hip_stream, k_scale, v_scale);                                 \
+        kv_lens, cu_seqlens_q, causal, 0, hip_stream, k_scale, v_scale);                              \
   }
 FA_PREFILL_VARLEN(f16, FA_DTYPE_F16)
 FA_PREFILL_VARLEN(bf16, FA_DTYPE_BF16)

@@ -86,6 +86,30 @@ EXPORTED_SYMBOLS = (
     "fa_cache_append_varlen_kv8_bf16",
     "fa_cache_append_varlen_paged_kv8_f16",
     "fa_cache_append_varlen_paged_kv8_bf16",
+    "fa_decode_win_f16",
+    "fa_decode_win_bf16",
+    "fa_decode_win_paged_f16",
+    "fa_decode_win_paged_bf16",
+    "fa_decode_win_kv8_f16",
+    "fa_decode_win_kv8_bf16",
+    "fa_decode_win_paged_kv8_f16",
+    "fa_decode_win_paged_kv8_bf16",
+    "fa_prefill_win_f16",
+    "fa_prefill_win_bf16",
+    "fa_prefill_win_paged_f16",
+    "fa_prefill_win_paged_bf16",
+    "fa_prefill_win_kv8_f16",
+    "fa_prefill_win_kv8_bf16",
+    "fa_prefill_win_paged_kv8_f16",
+    "fa_prefill_win_paged_kv8_bf16",
+    "fa_prefill_varlen_win_f16",
+    "fa_prefill_varlen_win_bf16",
+    "fa_prefill_varlen_win_paged_f16",
+    "fa_prefill_varlen_win_paged_bf16",
+    "fa_prefill_varlen_win_kv8_f16",
+    "fa_prefill_varlen_win_kv8_bf16",
+    "fa_prefill_varlen_win_paged_kv8_f16",
+    "fa_prefill_varlen_win_paged_kv8_bf16",
     "fa_select_config",
     "fa_num_configs",
     "fa_config_info",
@@ -230,6 +254,15 @@ def load_library() -> ctypes.CDLL:
     for name in EXPORTED_SYMBOLS:
         if name.startswith("fa_prefill"):
             getattr(lib, name).restype = i
+    # the sliding-window twins: `int window` directly after `causal`
+    for form in ("", "_paged", "_kv8", "_paged_kv8"):
+        for ty in ("_f16", "_bf16"):
+            for fam, after in (("fa_decode", 4), ("fa_prefill", 1), ("fa_prefill_varlen", 1)):
+                base = getattr(lib, fam + form + ty).argtypes
+                at = len(base) - after - (2 if "kv8" in form else 0)  # causal's successor
+                fn = getattr(lib, fam + "_win" + form + ty)
+                fn.argtypes = base[:at] + [i] + base[at:]
+                fn.restype = i
     lib.fa_decode_num_splits.argtypes = [i, i, i, i, i, i]
     lib.fa_decode_num_splits.restype = i
     lib.fa_decode_ws_bytes.argtypes = [i, i, i, i, i, i, i]
@@ -625,18 +658,45 @@ def _check_decode_paged(q, k_pages, v_pages, block_table, kv_lens, out, k_scale=
     return kv8
 
 
-_DEC_ENTRY = {}  # (paged, kv8, bf16) -> the C entry
+def _check_window(window, causal) -> int:
+    """The sliding window W of the decode / prefill functions: 0 = none, W >= 1
+    = a row sees at most W keys, its own included (causal only).  Returns the
+    value the C entry takes: a W past INT_MAX is INT_MAX (a C int; the entry
+    clamps W to the capacity anyway, past which it masks nothing)."""
+    if isinstance(window, bool) or not isinstance(window, int):
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE,
+                                  f"window must be an int, got {type(window).__name__}")
+    if window < 0:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"window must be >= 0 (0: no window), got {window}")
+    if window > 0 and not causal:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, "a window needs causal=True (no look-ahead windows)")
+    return min(window, 0x7fffffff)
+
+
+def decode_window_capacity(kv_capacity: int, seqlen_q: int, window: int) -> int:
+    """The capacity a windowed decode plans its split from and sizes its
+    workspace for (csrc/fa_decode_host.hpp): the tiles holding the last W + Sq
+    - 1 keys, min(cap, 64 * ceil((W + Sq - 1) / 64) + 64); window 0: cap."""
+    if window <= 0:
+        return kv_capacity
+    return min(kv_capacity, 64 * ((window + seqlen_q - 1 + 63) // 64) + 64)
+
+
+_DEC_ENTRY = {}  # (paged, kv8, bf16, windowed) -> the C entry
 
 
 def _decode_call(kv8, q, k, v, out, block_table, kv_lens, causal, return_lse, num_splits, stream,
-                 k_scale, v_scale):
+                 k_scale, v_scale, window=0):
     """The call of both decode functions after their checks: the stream, the
     optional LSE, the split workspace and the C entry of q's dtype.
     block_table: None when k, v are a contiguous cache (the fa_decode_*
     entries), the table when they are page pools (the fa_decode_paged_*
-    entries); kv8: the _kv8 entries, which also take the two scales."""
+    entries); kv8: the _kv8 entries, which also take the two scales; window >
+    0: the fa_decode_win_* entries, whose plan and workspace follow
+    :func:`decode_window_capacity`."""
     import torch
 
+    win = (window,) if window else ()  # checked by the public function
     b, hq, sq, d = q.shape
     hkv, cap = k.shape[1], k.shape[2]
     paged = block_table is not None
@@ -647,10 +707,11 @@ def _decode_call(kv8, q, k, v, out, block_table, kv_lens, causal, return_lse, nu
     else:
         cache = (cap, d)
     lib = _lib or load_library()
-    which = (paged, kv8, q.dtype is torch.bfloat16)
+    which = (paged, kv8, q.dtype is torch.bfloat16, bool(win))
     fn = _DEC_ENTRY.get(which)
     if fn is None:
-        fn = _DEC_ENTRY[which] = getattr(lib, "fa_decode" + ("_paged" if paged else "")
+        fn = _DEC_ENTRY[which] = getattr(lib, "fa_decode" + ("_win" if win else "")
+                                         + ("_paged" if paged else "")
                                          + ("_kv8" if kv8 else "") + ("_bf16" if which[2] else "_f16"))
     tail = ()
     if kv8:
@@ -666,15 +727,17 @@ def _decode_call(kv8, q, k, v, out, block_table, kv_lens, causal, return_lse, nu
     with torch.cuda.device(dev):
         need = 0
         if not paged or cap <= 0x7fffffff - 64:  # (past it the paged entry itself refuses the shape)
-            key = (dev, b, hq, hkv, sq, cap, d, ns)
+            # a windowed call plans (and needs a workspace) as for the window's capacity
+            pcap = decode_window_capacity(cap, sq, win[0]) if win else cap
+            key = (dev, b, hq, hkv, sq, pcap, d, ns)
             need = _DEC_NEED.get(key)
             if need is None:
-                need = lib.fa_decode_ws_bytes(b, hq, hkv, sq, cap, d, ns)
+                need = lib.fa_decode_ws_bytes(b, hq, hkv, sq, pcap, d, ns)
                 _DEC_NEED[key] = need
         ws = _workspace(need, dev, st) if need else None
         rc = fn(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
                 lse.data_ptr() if return_lse else None, b, hq, hkv, sq, *cache,
-                kv_lens.data_ptr() if kv_lens is not None else None, int(bool(causal)), ns,
+                kv_lens.data_ptr() if kv_lens is not None else None, int(bool(causal)), *win, ns,
                 ws.data_ptr() if need else None, need, st, *tail)
     _check(rc)
     return (out, lse) if return_lse else out
@@ -682,7 +745,7 @@ def _decode_call(kv8, q, k, v, out, block_table, kv_lens, causal, return_lse, nu
 
 def flash_attention_decode(q, k_cache, v_cache, kv_lens=None, causal: bool = True, out=None,
                            return_lse: bool = False, num_splits: int = 0, stream=None,
-                           k_scale=None, v_scale=None):
+                           k_scale=None, v_scale=None, window: int = 0):
     """Decode attention over a K/V cache (fa_decode_f16 / fa_decode_bf16, or
     fa_decode_kv8_* over an FP8 cache).
 
@@ -702,19 +765,30 @@ def flash_attention_decode(q, k_cache, v_cache, kv_lens=None, causal: bool = Tru
     v_scale[hkv] * v_cache; k_scale, v_scale: contiguous float32 [Hkv] tensors
     on q's device (None: 1.0).  Their values are read on the device, so a
     captured graph follows them.  Scales beside a 16-bit cache are an error.
+
+    window: 0 = none; W >= 1 = sliding-window attention (causal only): the row
+    at position pos sees the keys max(0, pos - W + 1) .. pos, at most W, its
+    own included -- Hugging Face's ``sliding_window = W``, flash-attn's
+    ``window_size = (W - 1, 0)`` (the fa_decode_win_* entries).  Cache rows below
+    the first row's lower bound are never read, and in the paged form neither
+    are the table entries of pages lying wholly below it: those pages may be
+    freed or reused.
+    With num_splits = 0 a windowed call is planned from
+    :func:`decode_window_capacity`, the keys it can touch.
     """
+    window = _check_window(window, causal)  # before the tensors: a bad window is named whatever they are
     if out is None:
         import torch
 
         out = torch.empty_like(q)
     kv8 = _check_decode(q, k_cache, v_cache, kv_lens, out, k_scale, v_scale)
     return _decode_call(kv8, q, k_cache, v_cache, out, None, kv_lens, causal, return_lse, num_splits,
-                        stream, k_scale, v_scale)
+                        stream, k_scale, v_scale, window)
 
 
 def flash_attention_decode_paged(q, k_pages, v_pages, block_table, kv_lens=None, causal: bool = True,
                                  out=None, return_lse: bool = False, num_splits: int = 0, stream=None,
-                                 k_scale=None, v_scale=None):
+                                 k_scale=None, v_scale=None, window: int = 0):
     """Decode attention over a paged K/V cache (fa_decode_paged_f16 / _bf16, or
     fa_decode_paged_kv8_* over an FP8 pool).
 
@@ -731,28 +805,33 @@ def flash_attention_decode_paged(q, k_pages, v_pages, block_table, kv_lens=None,
     the return value and the contract (no sync, graph-capturable, the
     per-(device, stream) workspace) are those of :func:`flash_attention_decode`,
     whose result on the gathered cache this one equals bit for bit.  Pools of
-    torch.float8_e4m3fn with k_scale / v_scale: as for that function.
+    torch.float8_e4m3fn with k_scale / v_scale, and window: as for that
+    function (fa_decode_win_paged_*); block-table entries of pages wholly
+    below the window are never read.
     """
+    window = _check_window(window, causal)  # before the tensors: a bad window is named whatever they are
     if out is None:
         import torch
 
         out = torch.empty_like(q)
     kv8 = _check_decode_paged(q, k_pages, v_pages, block_table, kv_lens, out, k_scale, v_scale)
     return _decode_call(kv8, q, k_pages, v_pages, out, block_table, kv_lens, causal, return_lse,
-                        num_splits, stream, k_scale, v_scale)
+                        num_splits, stream, k_scale, v_scale, window)
 
 
-_PRE_ENTRY = {}  # (paged, kv8, bf16) -> the C entry
+_PRE_ENTRY = {}  # (paged, kv8, bf16, windowed) -> the C entry
 
 
 def _prefill_call(kv8, q, k, v, out, block_table, kv_lens, q_lens, causal, return_lse, stream, k_scale,
-                  v_scale):
+                  v_scale, window=0):
     """The call of both prefill functions after their checks (the twin of
     :func:`_decode_call`, without a workspace): the stream, the optional LSE
     and the C entry of the cache form and q's dtype.  The LSE is allocated
-    with empty(): rows past q_lens are not written."""
+    with empty(): rows past q_lens are not written.  window > 0: the
+    fa_prefill_win_* entries."""
     import torch
 
+    win = (window,) if window else ()  # checked by the public function
     b, hq, sq, d = q.shape
     hkv = k.shape[1]
     paged = block_table is not None
@@ -761,10 +840,11 @@ def _prefill_call(kv8, q, k, v, out, block_table, kv_lens, q_lens, causal, retur
     else:
         cache = (k.shape[2], d)
     lib = _lib or load_library()
-    which = (paged, kv8, q.dtype is torch.bfloat16)
+    which = (paged, kv8, q.dtype is torch.bfloat16, bool(win))
     fn = _PRE_ENTRY.get(which)
     if fn is None:
-        fn = _PRE_ENTRY[which] = getattr(lib, "fa_prefill" + ("_paged" if paged else "")
+        fn = _PRE_ENTRY[which] = getattr(lib, "fa_prefill" + ("_win" if win else "")
+                                         + ("_paged" if paged else "")
                                          + ("_kv8" if kv8 else "") + ("_bf16" if which[2] else "_f16"))
     tail = ()
     if kv8:
@@ -780,14 +860,14 @@ def _prefill_call(kv8, q, k, v, out, block_table, kv_lens, q_lens, causal, retur
         rc = fn(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
                 lse.data_ptr() if return_lse else None, b, hq, hkv, sq, *cache,
                 kv_lens.data_ptr() if kv_lens is not None else None,
-                q_lens.data_ptr() if q_lens is not None else None, int(bool(causal)), st, *tail)
+                q_lens.data_ptr() if q_lens is not None else None, int(bool(causal)), *win, st, *tail)
     _check(rc)
     return (out, lse) if return_lse else out
 
 
 def flash_attention_prefill(q, k_cache, v_cache, kv_lens=None, q_lens=None, causal: bool = True,
                             out=None, return_lse: bool = False, stream=None, k_scale=None,
-                            v_scale=None):
+                            v_scale=None, window: int = 0):
     """Prefill attention over a K/V cache (fa_prefill_f16 / fa_prefill_bf16, or
     fa_prefill_kv8_* over an FP8 cache): a prompt, or a chunk of one behind a
     cached prefix, against the cache :func:`flash_attention_cache_append` wrote
@@ -807,19 +887,29 @@ def flash_attention_prefill(q, k_cache, v_cache, kv_lens=None, q_lens=None, caus
     when return_lse.  Lengths and scales are read on the device: no sync, no
     workspace, graph-capturable; enqueued on ``stream`` (default: torch's
     current stream).
+
+    window: 0 = none; W >= 1 = sliding-window attention (causal only): the row
+    at position pos sees the keys max(0, pos - W + 1) .. pos, at most W, its
+    own included -- Hugging Face's ``sliding_window = W``, flash-attn's
+    ``window_size = (W - 1, 0)`` (the fa_prefill_win_* entries).  Cache rows below
+    a 128-row query block's first lower bound are never read, and in the paged form neither
+    are the table entries of pages lying wholly below it: those pages may be
+    freed or reused.
+    pos = kv_lens[b] - n_b + t.
     """
+    window = _check_window(window, causal)  # before the tensors: a bad window is named whatever they are
     if out is None:
         import torch
 
         out = torch.empty_like(q)
     kv8 = _check_decode(q, k_cache, v_cache, kv_lens, out, k_scale, v_scale, q_lens)
     return _prefill_call(kv8, q, k_cache, v_cache, out, None, kv_lens, q_lens, causal, return_lse,
-                         stream, k_scale, v_scale)
+                         stream, k_scale, v_scale, window)
 
 
 def flash_attention_prefill_paged(q, k_pages, v_pages, block_table, kv_lens=None, q_lens=None,
                                   causal: bool = True, out=None, return_lse: bool = False, stream=None,
-                                  k_scale=None, v_scale=None):
+                                  k_scale=None, v_scale=None, window: int = 0):
     """:func:`flash_attention_prefill` over the page pools
     :func:`flash_attention_decode_paged` reads (fa_prefill_paged_f16 / _bf16, or
     fa_prefill_paged_kv8_* over an FP8 pool).
@@ -830,7 +920,10 @@ def flash_attention_prefill_paged(q, k_pages, v_pages, block_table, kv_lens=None
     page id outside the pool reads as zero rows.  The result equals
     :func:`flash_attention_prefill` on the gathered cache bit for bit.  Rows
     t >= n_b of out and lse are not written (unspecified with out=None).
+    window: as for that function (fa_prefill_win_paged_*); block-table entries
+    of pages wholly below a query block's window are never read.
     """
+    window = _check_window(window, causal)  # before the tensors: a bad window is named whatever they are
     if block_table is None:
         raise FlashAttentionError(FA_ERR_NULL_POINTER, "block_table is required")
     if out is None:
@@ -839,7 +932,7 @@ def flash_attention_prefill_paged(q, k_pages, v_pages, block_table, kv_lens=None
         out = torch.empty_like(q)
     kv8 = _check_decode_paged(q, k_pages, v_pages, block_table, kv_lens, out, k_scale, v_scale, q_lens)
     return _prefill_call(kv8, q, k_pages, v_pages, out, block_table, kv_lens, q_lens, causal,
-                         return_lse, stream, k_scale, v_scale)
+                         return_lse, stream, k_scale, v_scale, window)
 
 
 def _check_append(k_new, v_new, kname, k, vname, v, block_table, kv_lens, new_lens, k_scale, v_scale):
@@ -1093,26 +1186,28 @@ def _packed_call(name, kv8, x, y, extra, nseq, heads, k, v, block_table, kv_lens
 
 
 def _prefill_varlen(q, k, v, block_table, names, cu_seqlens_q, kv_lens, causal, out, return_lse, stream,
-                    k_scale, v_scale):
+                    k_scale, v_scale, window=0):
     import torch
 
+    win = (window,) if window else ()  # checked by the public function
     if out is None:
         out = torch.empty_like(q)
     kv8, nseq = _check_packed(q, "q", out, "out", names[0], k, names[1], v, block_table, cu_seqlens_q,
                               "cu_seqlens_q", kv_lens, k_scale, v_scale, False)
     total, hq = q.shape[0], q.shape[1]
     lse = torch.empty((hq, total), dtype=torch.float32, device=q.device) if return_lse else None
-    name = ("fa_prefill_varlen" + ("_paged" if block_table is not None else "") + ("_kv8" if kv8 else "")
+    name = ("fa_prefill_varlen" + ("_win" if win else "")
+            + ("_paged" if block_table is not None else "") + ("_kv8" if kv8 else "")
             + ("_bf16" if q.dtype is torch.bfloat16 else "_f16"))
     _packed_call(name, kv8, q, (), (out.data_ptr(), lse.data_ptr() if return_lse else None), nseq,
-                 (hq, k.shape[1]), k, v, block_table, kv_lens, cu_seqlens_q, (int(bool(causal)),), stream,
-                 k_scale, v_scale)
+                 (hq, k.shape[1]), k, v, block_table, kv_lens, cu_seqlens_q, (int(bool(causal)), *win),
+                 stream, k_scale, v_scale)
     return (out, lse) if return_lse else out
 
 
 def flash_attention_prefill_varlen(q, k_cache, v_cache, cu_seqlens_q, kv_lens=None, causal: bool = True,
                                    out=None, return_lse: bool = False, stream=None, k_scale=None,
-                                   v_scale=None):
+                                   v_scale=None, window: int = 0):
     """:func:`flash_attention_prefill` for a packed ragged batch
     (fa_prefill_varlen_f16 / _bf16, or fa_prefill_varlen_kv8_* over an FP8
     cache): what a serving stack holds after its QKV projection, taken as it
@@ -1131,23 +1226,30 @@ def flash_attention_prefill_varlen(q, k_cache, v_cache, cu_seqlens_q, kv_lens=No
     (the clamps); if they do not increase the result is unspecified.  Returns
     out [T, Hq, D], or (out, lse) with lse fp32 [Hq, T] when return_lse.
     Everything is read on the device: no sync, no workspace, graph-capturable.
+    window: the sliding window of :func:`flash_attention_prefill`
+    (fa_prefill_varlen_win_*), with the same bit-for-bit equality.
     """
+    window = _check_window(window, causal)  # before the tensors: a bad window is named whatever they are
     return _prefill_varlen(q, k_cache, v_cache, None, ("k_cache", "v_cache"), cu_seqlens_q, kv_lens,
-                           causal, out, return_lse, stream, k_scale, v_scale)
+                           causal, out, return_lse, stream, k_scale, v_scale, window)
 
 
 def flash_attention_prefill_varlen_paged(q, k_pages, v_pages, block_table, cu_seqlens_q, kv_lens=None,
                                          causal: bool = True, out=None, return_lse: bool = False,
-                                         stream=None, k_scale=None, v_scale=None):
+                                         stream=None, k_scale=None, v_scale=None, window: int = 0):
     """:func:`flash_attention_prefill_varlen` over the page pools of
     :func:`flash_attention_prefill_paged` (fa_prefill_varlen_paged_f16 / _bf16,
     or fa_prefill_varlen_paged_kv8_*).  B is the block table's row count; the
     result equals the contiguous function's on the gathered cache bit for bit.
+    window: the sliding window of :func:`flash_attention_prefill`
+    (fa_prefill_varlen_win_paged_*); block-table entries of pages wholly below
+    a query block's window are never read.
     """
+    window = _check_window(window, causal)  # before the tensors: a bad window is named whatever they are
     if block_table is None:
         raise FlashAttentionError(FA_ERR_NULL_POINTER, "block_table is required")
     return _prefill_varlen(q, k_pages, v_pages, block_table, ("k_pages", "v_pages"), cu_seqlens_q,
-                           kv_lens, causal, out, return_lse, stream, k_scale, v_scale)
+                           kv_lens, causal, out, return_lse, stream, k_scale, v_scale, window)
 
 
 def _append_varlen(k_new, v_new, k, v, block_table, names, cu_seqlens, kv_lens, k_scale, v_scale, stream):

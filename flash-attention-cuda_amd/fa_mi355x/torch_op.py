@@ -446,3 +446,78 @@ _LIB.impl("cache_append_varlen_paged", _cache_append_varlen_paged_cpu, "CPU")
 torch.library.register_fake(CACHE_APPEND_VARLEN_PAGED_OP_NAME, _cache_append_varlen_paged_fake, lib=_LIB)
 
 cache_append_varlen_paged = torch.ops.fa_mi355x.cache_append_varlen_paged
+
+# Sliding-window attention: the default overloads' schemas are pinned as they
+# stand, so `window` comes in a `.window` overload of each of the six decode /
+# prefill ops (the precedent is decode_paged.kv8): the default overload's
+# arguments (decode_paged: the .kv8 overload's, with the scales), then
+# `int window` (0: none; W >= 1: a row sees at most W keys, its own included,
+# causal only).  A call through the packet that names or passes `window`
+# resolves to it; every call an earlier overload accepts still resolves there.
+_REQUIRED = object()
+
+
+def _window_overload(name, args, wrapper, fake):
+    """Registers fa_mi355x::<name>.window.  args: the overload's arguments in
+    order as (schema type, name, default) -- _REQUIRED for none -- which are
+    also `wrapper`'s keyword names (the Python function the default overload
+    calls); fake: the default overload's fake implementation.  Tensors are made
+    contiguous but for the caches, which are taken as they are."""
+    names = [n for _, n, _ in args]
+    defaults = {n: d for _, n, d in args if d is not _REQUIRED}
+    caches = set(names[1:3])
+
+    def bind(a, kw):
+        vals = dict(defaults)
+        vals.update(zip(names, a))
+        vals.update(kw)
+        return vals
+
+    def gpu(*a, **kw):
+        vals = bind(a, kw)
+        _no_grad_needed(*(vals[n] for n in names[:3]))
+        for n, x in vals.items():
+            if isinstance(x, torch.Tensor) and n not in caches and "scale" not in n:
+                vals[n] = x.contiguous()
+        return wrapper(**vals)
+
+    def cpu(*a, **kw):
+        raise ValueError("fa_mi355x::%s needs GPU tensors (no CPU path)" % name)
+
+    def fake_impl(*a, **kw):
+        vals = bind(a, kw)
+        torch._check(vals.pop("window") >= 0, lambda: "expected window >= 0")
+        return fake(**vals)
+
+    def lit(d):
+        return "" if d is _REQUIRED else "=" + str(d)
+
+    _LIB.define("%s.window(%s) -> Tensor" % (name, ", ".join(f"{ty} {n}{lit(d)}" for ty, n, d in args)))
+    _LIB.impl(name + ".window", gpu, "CUDA")
+    _LIB.impl(name + ".window", torch.library.fallthrough_kernel, "Autograd")
+    _LIB.impl(name + ".window", cpu, "CPU")
+    torch.library.register_fake("fa_mi355x::" + name + ".window", fake_impl, lib=_LIB)
+
+
+def _T(n):
+    return ("Tensor", n, _REQUIRED)
+
+
+def _opt(n):
+    return ("Tensor?", n, None)
+
+
+_TAIL = [("bool", "causal", True), _opt("k_scale"), _opt("v_scale"), ("int", "window", 0)]
+_window_overload("decode", [_T("q"), _T("k_cache"), _T("v_cache"), _opt("kv_lens")] + _TAIL,
+                 flash_attention_decode, _decode_fake)
+_window_overload("decode_paged", [_T("q"), _T("k_pages"), _T("v_pages"), _T("block_table"), _opt("kv_lens")]
+                 + _TAIL, flash_attention_decode_paged, _decode_paged_fake)
+_window_overload("prefill", [_T("q"), _T("k_cache"), _T("v_cache"), _opt("kv_lens"), _opt("q_lens")] + _TAIL,
+                 flash_attention_prefill, _prefill_fake)
+_window_overload("prefill_paged", [_T("q"), _T("k_pages"), _T("v_pages"), _T("block_table"), _opt("kv_lens"),
+                                   _opt("q_lens")] + _TAIL, flash_attention_prefill_paged, _prefill_paged_fake)
+_window_overload("prefill_varlen", [_T("q"), _T("k_cache"), _T("v_cache"), _T("cu_seqlens_q"), _opt("kv_lens")]
+                 + _TAIL, flash_attention_prefill_varlen, _prefill_varlen_fake)
+_window_overload("prefill_varlen_paged", [_T("q"), _T("k_pages"), _T("v_pages"), _T("block_table"),
+                                          _T("cu_seqlens_q"), _opt("kv_lens")] + _TAIL,
+                 flash_attention_prefill_varlen_paged, _prefill_varlen_paged_fake)

@@ -35,6 +35,15 @@ the same bytes as a randomly permuted pool, page sizes 64 and 256, in the same
 rotation.
 
     python3 tools/decode_bench.py --kv8 [--out profiles/decode_kv8_bench.jsonl]
+
+--window W times the sliding-window entries fa_decode_win_* against fa_decode_*
+on the same cache (run_window): B=64 and B=1 at len 32768, contiguous and as a
+page pool (page 256), captured into HIP graphs and replayed alternately plain /
+windowed / plain / paged windowed, so every row carries its own A/A spread.
+The figure of record is win_over_plain beside plain_aa and tile_ratio, the
+share of 64-key tiles the windowed launch iterates, counted from the shape.
+
+    python3 tools/decode_bench.py --window 4096 [--out profiles/decode_window_bench.jsonl]
 """
 import argparse
 import json
@@ -465,6 +474,113 @@ def run_kv8(row, cus, rounds=9):
     return rec
 
 
+def window_shapes():
+    return [dict(name=f"window B={b} len=32768", b=b, hq=32, hkv=8, sq=1, d=128, n=32768) for b in (64, 1)]
+
+
+def run_window(row, window, cus, page_size=256, rounds=9):
+    """The windowed entry against the plain one on the same cache: us per call
+    from alternately replayed HIP graphs (plain, windowed, plain again, paged
+    windowed)."""
+    lib = fa_mi355x.load_library()
+    dt = torch.float16
+    b, hq, hkv, sq, d, cap = row["b"], row["hq"], row["hkv"], row["sq"], row["d"], row["n"]
+    mpp = cap // page_size
+    npages = b * mpp
+    kv_bytes = 2 * b * hkv * cap * d * 2
+    copies = max(1, min(32, -(-(512 << 20) // kv_bytes)))
+    gen = torch.Generator(device="cuda").manual_seed(1)
+
+    def rnd(*shape):
+        return (torch.rand(shape, generator=gen, device="cuda", dtype=torch.float32) * 2 - 1).to(dt)
+
+    ks, vs, kps, vps, tabs = [], [], [], [], []
+    for _ in range(copies):
+        k, v = rnd(b, hkv, cap, d), rnd(b, hkv, cap, d)
+        perm = torch.randperm(npages, generator=gen, device="cuda")
+        ks.append(k), vs.append(v)
+        for x, dst in ((k, kps), (v, vps)):
+            out = torch.empty((npages, hkv, page_size, d), dtype=dt, device="cuda")
+            out[perm] = x.view(b, hkv, mpp, page_size, d).permute(0, 2, 1, 3, 4).reshape(
+                npages, hkv, page_size, d)
+            dst.append(out)
+        tabs.append(perm.view(b, mpp).to(torch.int32).contiguous())
+    q = rnd(b, hq, sq, d)
+    wcap = fa_mi355x.decode_window_capacity(cap, sq, window)
+    plan = fa_mi355x.decode_num_splits(b, hq, hkv, sq, cap, d)
+    plan_w = fa_mi355x.decode_num_splits(b, hq, hkv, sq, wcap, d)
+    need = max(lib.fa_decode_ws_bytes(b, hq, hkv, sq, cap, d, 0), lib.fa_decode_ws_bytes(b, hq, hkv, sq, wcap, d, 0))
+    ws = torch.zeros(max(need, 1), dtype=torch.uint8, device="cuda")
+    wsp = ws.data_ptr() if need else None
+    outs = [torch.empty_like(q) for _ in range(3)]
+    iters = 20 if kv_bytes < (1 << 30) else 5
+
+    def plain(st):
+        for i in range(iters):
+            c = i % copies
+            rc = lib.fa_decode_f16(q.data_ptr(), ks[c].data_ptr(), vs[c].data_ptr(), outs[0].data_ptr(),
+                                   None, b, hq, hkv, sq, cap, d, None, 1, 0, wsp, need, st)
+            assert rc == 0, rc
+
+    def win(st):
+        for i in range(iters):
+            c = i % copies
+            rc = lib.fa_decode_win_f16(q.data_ptr(), ks[c].data_ptr(), vs[c].data_ptr(), outs[1].data_ptr(),
+                                       None, b, hq, hkv, sq, cap, d, None, 1, window, 0, wsp, need, st)
+            assert rc == 0, rc
+
+    def win_paged(st):
+        for i in range(iters):
+            c = i % copies
+            rc = lib.fa_decode_win_paged_f16(q.data_ptr(), kps[c].data_ptr(), vps[c].data_ptr(),
+                                             outs[2].data_ptr(), None, b, hq, hkv, sq, d, npages, page_size,
+                                             tabs[c].data_ptr(), mpp, None, 1, window, 0, wsp, need, st)
+            assert rc == 0, rc
+
+    fns = (plain, win, win_paged)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):  # first-launch set-up outside the captures
+        for fn in fns:
+            fn(side.cuda_stream)
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    same = bool(torch.equal(outs[1], outs[2]))
+    graphs = []
+    for fn in fns:
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            fn(torch.cuda.current_stream().cuda_stream)
+        g.replay()
+        graphs.append(g)
+    torch.cuda.synchronize()
+    legs = (0, 1, 0, 2)
+    ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+           for _ in range(rounds)] for _ in legs]
+    for r in range(rounds):
+        for j, gi in enumerate(legs):
+            ev[j][r][0].record()
+            graphs[gi].replay()
+            ev[j][r][1].record()
+    torch.cuda.synchronize()
+    ts = [sorted(a.elapsed_time(c) * 1e3 / iters for a, c in e) for e in ev]
+    med = [t[len(t) // 2] for t in ts]
+    tiles = -(-cap // 64)
+    tiles_w = tiles - max(0, cap - sq + 1 - window) // 64
+    win_bytes = 2 * b * hkv * min(cap, window + sq - 1) * d * 2
+    return dict(name=row["name"], window=window, batch=b, heads_q=hq, heads_kv=hkv, seqlen_q=sq, head_dim=d,
+                dtype="float16", kv_len=cap, page_size=page_size, copies=copies, num_splits=plan,
+                num_splits_window=plan_w, rounds=rounds, iters=iters, paged_bit_identical=same,
+                plain_us=round(med[0], 2), win_us=round(med[1], 2), plain2_us=round(med[2], 2),
+                win_paged_us=round(med[3], 2), plain_min_us=round(min(ts[0][0], ts[2][0]), 2),
+                plain_max_us=round(max(ts[0][-1], ts[2][-1]), 2), win_min_us=round(ts[1][0], 2),
+                win_max_us=round(ts[1][-1], 2), win_over_plain=round(med[1] / med[0], 4),
+                win_paged_over_plain=round(med[3] / med[0], 4), plain_aa=round(med[2] / med[0], 4),
+                tiles=tiles, tiles_window=tiles_w, tile_ratio=round(tiles_w / tiles, 4),
+                win_share_of_copy_rate=round(win_bytes / (med[1] * 1e-6) / COPY_RATE, 4),
+                plain_share_of_copy_rate=round(kv_bytes / (med[0] * 1e-6) / COPY_RATE, 4))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="default profiles/decode_bench.jsonl "
@@ -475,18 +591,23 @@ def main():
                     help="paged against contiguous decode, page sizes 64 and 256")
     ap.add_argument("--kv8", action="store_true",
                     help="the FP8-cache entries against the 16-bit ones on the same shapes")
+    ap.add_argument("--window", type=int, default=0,
+                    help="the sliding-window entries at this W against the plain ones")
     ap.add_argument("--placement", choices=("random", "identity"), default="random",
                     help="--paged: pool pages under a random permutation (default) or in logical order")
     args = ap.parse_args()
     if args.out is None:
         args.out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "profiles",
+                                "decode_window_bench.jsonl" if args.window else
                                 "decode_kv8_bench.jsonl" if args.kv8 else
                                 "decode_paged_bench.jsonl" if args.paged else "decode_bench.jsonl")
     if not torch.cuda.is_available():
         sys.exit("decode_bench.py needs a GPU")
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    if args.kv8:
+    if args.window:
+        jobs = [(run_window, (row, args.window, cus)) for row in window_shapes()]
+    elif args.kv8:
         jobs = [(run_kv8, (row, cus)) for row in kv8_shapes()]
     elif args.paged:
         jobs = [(run_paged, (row, ps, cus, args.placement)) for row in paged_shapes() for ps in (64, 256)]

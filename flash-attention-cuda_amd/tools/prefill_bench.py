@@ -36,6 +36,14 @@ Hkv = 8, three arms on the same lengths and cache, alternated the same way:
             torch's caching allocator inside the arm).
 
     timeout 300 python3 tools/prefill_bench.py --varlen skewed [--out profiles/prefill_varlen_bench.jsonl]
+
+--window W (with --shape): the sliding-window entry at this W against the entry
+without a window on the same inputs, alternated the same way, plain / windowed
+/ plain, so every row carries its own A/A spread.  The figure of record is
+win_over_plain beside plain_aa and tile_ratio, the share of (query block, key
+tile) pairs the windowed launch iterates, counted from the shape.
+
+    timeout 300 python3 tools/prefill_bench.py --shape s32k --window 4096 [--out profiles/prefill_window_bench.jsonl]
 """
 import argparse
 import json
@@ -56,6 +64,10 @@ SHAPES = {
     "prefix": (8, 32, 8, 2048, 6144),
     "long": (1, 32, 8, 8192, 0),
     "short_chunk": (16, 32, 8, 512, 8192),
+    # one long prompt (the --window rows)
+    "s8k": (1, 32, 8, 8192, 0),
+    "s16k": (1, 32, 8, 16384, 0),
+    "s32k": (1, 32, 8, 32768, 0),
 }
 FORMS = ("contig", "paged", "contig_kv8", "paged_kv8")
 
@@ -203,6 +215,79 @@ def run(shape, dt, form, rounds, iters):
     return rec
 
 
+def window_tiles(sq, prefix, window, bm=128, bn=64):
+    """(key tiles the plain launch iterates per head, those of the windowed one)."""
+    plain = win = 0
+    for q0 in range(0, sq, bm):
+        nt = -(-min(prefix + sq, prefix + q0 + bm) // bn)
+        plain += nt
+        win += nt - max(0, prefix + q0 - window + 1) // bn
+    return plain, win
+
+
+def run_window(shape, dt, form, window, rounds, iters):
+    b, hq, hkv, sq, prefix = SHAPES[shape]
+    d = 128
+    skv = prefix + sq
+    gen = torch.Generator(device="cuda").manual_seed(1)
+
+    def rnd(*s):
+        return (torch.rand(s, generator=gen, device="cuda", dtype=torch.float32) * 2 - 1).to(dt)
+
+    q = rnd(b, hq, sq, d)
+    k, v = rnd(b, hkv, skv, d), rnd(b, hkv, skv, d)
+    kv_lens = torch.full((b,), skv, dtype=torch.int32, device="cuda")
+    q_lens = torch.full((b,), sq, dtype=torch.int32, device="cuda")
+    kv8, paged = form.endswith("kv8"), form.startswith("paged")
+    scales = {}
+    if kv8:
+        ks = torch.tensor([2.0 ** -(3 - (h & 1)) for h in range(hkv)], dtype=torch.float32, device="cuda")
+        vs = torch.tensor([2.0 ** -(2 + (h & 1)) for h in range(hkv)], dtype=torch.float32, device="cuda")
+        k = (k.float() / ks[None, :, None, None]).to(FP8)
+        v = (v.float() / vs[None, :, None, None]).to(FP8)
+        scales = dict(k_scale=ks, v_scale=vs)
+    table = None
+    if paged:
+        mpp = skv // PAGE
+        perm = torch.randperm(b * mpp, generator=gen, device="cuda")
+
+        def pool(x):
+            out = torch.empty((b * mpp, hkv, PAGE, d), dtype=x.dtype, device="cuda")
+            src = x.view(b, hkv, mpp, PAGE, d).permute(0, 2, 1, 3, 4).reshape(b * mpp, hkv, PAGE, d)
+            out.view(torch.uint8)[perm] = src.contiguous().view(torch.uint8)
+            return out
+
+        k, v = pool(k), pool(v)
+        table = perm.view(b, mpp).to(torch.int32).contiguous()
+    outs = [torch.empty_like(q), torch.empty_like(q)]
+
+    def arm(w, o):
+        def fn():
+            if paged:
+                return fa_mi355x.flash_attention_prefill_paged(q, k, v, table, kv_lens, q_lens, out=o,
+                                                               window=w, **scales)
+            return fa_mi355x.flash_attention_prefill(q, k, v, kv_lens, q_lens, out=o, window=w, **scales)
+        return fn
+
+    plain, win = arm(0, outs[0]), arm(window, outs[1])
+    ts = time_arms([plain, win, plain], iters, rounds)
+    tp, tw = window_tiles(sq, prefix, window)
+    rec = dict(shape=shape, form=form, window=window, dtype=str(dt).split(".")[-1], batch=b, heads_q=hq,
+               heads_kv=hkv, seqlen_q=sq, prefix=prefix, head_dim=d, page_size=PAGE if paged else None,
+               rounds=rounds, iters=iters)
+    for name, (med, lo, hi) in zip(("plain", "win", "plain2"), ts):
+        rec[name + "_ms"] = round(med, 4)
+        rec[name + "_min_ms"] = round(lo, 4)
+        rec[name + "_max_ms"] = round(hi, 4)
+    rec["win_over_plain"] = round(ts[1][0] / ts[0][0], 4)
+    rec["plain_aa"] = round(ts[2][0] / ts[0][0], 4)
+    rec["tiles"], rec["tiles_window"], rec["tile_ratio"] = tp, tw, round(tw / tp, 4)
+    # rows whose window covers every key they see must agree exactly
+    rec["head_rows_bit_identical"] = bool(torch.equal(outs[0][:, :, :min(sq, window)],
+                                                      outs[1][:, :, :min(sq, window)]))
+    return rec
+
+
 def run_varlen(name, dt, form, rounds, iters):
     n, prefix = varlen_lengths(name)
     b, hq, hkv, d = len(n), 32, 8, 128
@@ -290,6 +375,8 @@ def main():
     ap.add_argument("--varlen", choices=VARLEN, help="a packed ragged batch instead of --shape")
     ap.add_argument("--dtype", choices=("fp16", "bf16"), default="fp16")
     ap.add_argument("--forms", default=",".join(FORMS))
+    ap.add_argument("--window", type=int, default=0,
+                    help="with --shape: the sliding-window entry at this W against the plain one")
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=2)
     ap.add_argument("--out", default=None, help="appended to; default profiles/prefill_bench.jsonl")
@@ -300,7 +387,8 @@ def main():
         ap.error("one of --shape and --varlen is required")
     if args.out is None:
         args.out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "profiles",
-                                "prefill_varlen_bench.jsonl" if args.varlen else "prefill_bench.jsonl")
+                                "prefill_varlen_bench.jsonl" if args.varlen else
+                                "prefill_window_bench.jsonl" if args.window else "prefill_bench.jsonl")
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     dt = torch.bfloat16 if args.dtype == "bf16" else torch.float16
     cus = torch.cuda.get_device_properties(0).multi_processor_count
@@ -309,6 +397,8 @@ def main():
             assert form in FORMS, form
             if args.varlen:
                 rec = run_varlen(args.varlen, dt, form, args.rounds, args.iters)
+            elif args.window:
+                rec = run_window(args.shape, dt, form, args.window, args.rounds, args.iters)
             else:
                 rec = run(args.shape, dt, form, args.rounds, args.iters)
             rec["cus"] = cus

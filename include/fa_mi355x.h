@@ -596,6 +596,163 @@ int fa_cache_append_varlen_paged_kv8_bf16(const void* k_new, const void* v_new, 
                                           void* hip_stream, const float* k_scale,
                                           const float* v_scale);
 
+/* Sliding-window attention: the twelve fa_decode_*, fa_prefill_* and
+ * fa_prefill_varlen_* entry pairs above with `int window` inserted directly
+ * after `causal` (`_win` follows the family name).  window = W is the largest
+ * number of keys a row may see, its own included:
+ *   W = 0  no window: the entry computes what its twin without `_win` computes
+ *   W < 0  FA_ERR_BAD_SHAPE (returned with the negative counts)
+ *   W > 0 with causal == 0  FA_ERR_BAD_SHAPE (returned right after the seqlen_q
+ *          / total_q check; there are no look-ahead windows)
+ * With pos = off_b + t (prefill: off_b = len_b - n_b; decode: pos = len_b -
+ * seqlen_q + t) row t sees the keys j with
+ *   max(0, pos - W + 1) <= j <= min(pos, len_b - 1)
+ * which is Hugging Face's sliding_window = W and flash-attn's window_size =
+ * (W - 1, 0).  A row that sees no key gives zeros and LSE = -inf.  Everything
+ * else is the twin's contract: lengths, tables and scales read on the device,
+ * no sync, no workspace for prefill, graph-capturable, rows past q_lens not
+ * written, every other argument error in the twin's place and order.  A W at or
+ * past every len_b gives the twin's O and LSE bit for bit (decode: at the same
+ * num_splits); the packed entries equal the padded ones and the paged ones the
+ * contiguous ones on the gathered cache bit for bit, as without a window.
+ * What is never read (callers may rely on it):
+ *   - cache rows outside [lo, hi): lo = max(0, off_b + q0 - W + 1) for the
+ *     128-row query block that starts at row q0 (decode: row 0's lower bound,
+ *     max(0, len_b - seqlen_q - W + 1)), hi the twin's upper end;
+ *   - paged: block-table entries of pages lying wholly below lo, so a server
+ *     may free or reuse the pages every later query has slid past.
+ * Decode splits the tiles [lo / 64, ceil(len_b / 64)) into its pieces, not the
+ * whole cache.  With num_splits = 0 a call with W > 0 plans from the capacity
+ * a window can touch,
+ *   cap_w = min(kv_capacity, 64 * ceil((W + seqlen_q - 1) / 64) + 64)
+ * so its pieces and its workspace are fa_decode_num_splits() and
+ * fa_decode_ws_bytes() called with cap_w in kv_capacity's place (a forced
+ * num_splits needs fa_decode_ws_bytes() of that count, as for the twin). */
+int fa_decode_win_f16(const void* q, const void* k, const void* v, void* o, float* lse, int batch,
+                      int heads_q, int heads_kv, int seqlen_q, int kv_capacity, int head_dim,
+                      const int* kv_lens, int causal, int window, int num_splits, void* workspace,
+                      unsigned long long ws_bytes, void* hip_stream);
+int fa_decode_win_bf16(const void* q, const void* k, const void* v, void* o, float* lse, int batch,
+                       int heads_q, int heads_kv, int seqlen_q, int kv_capacity, int head_dim,
+                       const int* kv_lens, int causal, int window, int num_splits, void* workspace,
+                       unsigned long long ws_bytes, void* hip_stream);
+int fa_decode_win_paged_f16(const void* q, const void* k_pages, const void* v_pages, void* o,
+                            float* lse, int batch, int heads_q, int heads_kv, int seqlen_q,
+                            int head_dim, int num_pages, int page_size, const int* block_table,
+                            int max_pages_per_seq, const int* kv_lens, int causal, int window,
+                            int num_splits, void* workspace, unsigned long long ws_bytes,
+                            void* hip_stream);
+int fa_decode_win_paged_bf16(const void* q, const void* k_pages, const void* v_pages, void* o,
+                             float* lse, int batch, int heads_q, int heads_kv, int seqlen_q,
+                             int head_dim, int num_pages, int page_size, const int* block_table,
+                             int max_pages_per_seq, const int* kv_lens, int causal, int window,
+                             int num_splits, void* workspace, unsigned long long ws_bytes,
+                             void* hip_stream);
+int fa_decode_win_kv8_f16(const void* q, const void* k, const void* v, void* o, float* lse,
+                          int batch, int heads_q, int heads_kv, int seqlen_q, int kv_capacity,
+                          int head_dim, const int* kv_lens, int causal, int window, int num_splits,
+                          void* workspace, unsigned long long ws_bytes, void* hip_stream,
+                          const float* k_scale, const float* v_scale);
+int fa_decode_win_kv8_bf16(const void* q, const void* k, const void* v, void* o, float* lse,
+                           int batch, int heads_q, int heads_kv, int seqlen_q, int kv_capacity,
+                           int head_dim, const int* kv_lens, int causal, int window, int num_splits,
+                           void* workspace, unsigned long long ws_bytes, void* hip_stream,
+                           const float* k_scale, const float* v_scale);
+int fa_decode_win_paged_kv8_f16(const void* q, const void* k_pages, const void* v_pages, void* o,
+                                float* lse, int batch, int heads_q, int heads_kv, int seqlen_q,
+                                int head_dim, int num_pages, int page_size, const int* block_table,
+                                int max_pages_per_seq, const int* kv_lens, int causal, int window,
+                                int num_splits, void* workspace, unsigned long long ws_bytes,
+                                void* hip_stream, const float* k_scale, const float* v_scale);
+int fa_decode_win_paged_kv8_bf16(const void* q, const void* k_pages, const void* v_pages, void* o,
+                                 float* lse, int batch, int heads_q, int heads_kv, int seqlen_q,
+                                 int head_dim, int num_pages, int page_size, const int* block_table,
+                                 int max_pages_per_seq, const int* kv_lens, int causal, int window,
+                                 int num_splits, void* workspace, unsigned long long ws_bytes,
+                                 void* hip_stream, const float* k_scale, const float* v_scale);
+int fa_prefill_win_f16(const void* q, const void* k, const void* v, void* o, float* lse, int batch,
+                       int heads_q, int heads_kv, int seqlen_q, int kv_capacity, int head_dim,
+                       const int* kv_lens, const int* q_lens, int causal, int window,
+                       void* hip_stream);
+int fa_prefill_win_bf16(const void* q, const void* k, const void* v, void* o, float* lse, int batch,
+                        int heads_q, int heads_kv, int seqlen_q, int kv_capacity, int head_dim,
+                        const int* kv_lens, const int* q_lens, int causal, int window,
+                        void* hip_stream);
+int fa_prefill_win_paged_f16(const void* q, const void* k_pages, const void* v_pages, void* o,
+                             float* lse, int batch, int heads_q, int heads_kv, int seqlen_q,
+                             int head_dim, int num_pages, int page_size, const int* block_table,
+                             int max_pages_per_seq, const int* kv_lens, const int* q_lens,
+                             int causal, int window, void* hip_stream);
+int fa_prefill_win_paged_bf16(const void* q, const void* k_pages, const void* v_pages, void* o,
+                              float* lse, int batch, int heads_q, int heads_kv, int seqlen_q,
+                              int head_dim, int num_pages, int page_size, const int* block_table,
+                              int max_pages_per_seq, const int* kv_lens, const int* q_lens,
+                              int causal, int window, void* hip_stream);
+int fa_prefill_win_kv8_f16(const void* q, const void* k, const void* v, void* o, float* lse,
+                           int batch, int heads_q, int heads_kv, int seqlen_q, int kv_capacity,
+                           int head_dim, const int* kv_lens, const int* q_lens, int causal,
+                           int window, void* hip_stream, const float* k_scale, const float* v_scale);
+int fa_prefill_win_kv8_bf16(const void* q, const void* k, const void* v, void* o, float* lse,
+                            int batch, int heads_q, int heads_kv, int seqlen_q, int kv_capacity,
+                            int head_dim, const int* kv_lens, const int* q_lens, int causal,
+                            int window, void* hip_stream, const float* k_scale, const float* v_scale);
+int fa_prefill_win_paged_kv8_f16(const void* q, const void* k_pages, const void* v_pages, void* o,
+                                 float* lse, int batch, int heads_q, int heads_kv, int seqlen_q,
+                                 int head_dim, int num_pages, int page_size, const int* block_table,
+                                 int max_pages_per_seq, const int* kv_lens, const int* q_lens,
+                                 int causal, int window, void* hip_stream, const float* k_scale,
+                                 const float* v_scale);
+int fa_prefill_win_paged_kv8_bf16(const void* q, const void* k_pages, const void* v_pages, void* o,
+                                  float* lse, int batch, int heads_q, int heads_kv, int seqlen_q,
+                                  int head_dim, int num_pages, int page_size,
+                                  const int* block_table, int max_pages_per_seq, const int* kv_lens,
+                                  const int* q_lens, int causal, int window, void* hip_stream,
+                                  const float* k_scale, const float* v_scale);
+int fa_prefill_varlen_win_f16(const void* q, const void* k, const void* v, void* o, float* lse,
+                              int batch, int heads_q, int heads_kv, int total_q, int kv_capacity,
+                              int head_dim, const int* kv_lens, const int* cu_seqlens_q, int causal,
+                              int window, void* hip_stream);
+int fa_prefill_varlen_win_bf16(const void* q, const void* k, const void* v, void* o, float* lse,
+                               int batch, int heads_q, int heads_kv, int total_q, int kv_capacity,
+                               int head_dim, const int* kv_lens, const int* cu_seqlens_q,
+                               int causal, int window, void* hip_stream);
+int fa_prefill_varlen_win_paged_f16(const void* q, const void* k_pages, const void* v_pages,
+                                    void* o, float* lse, int batch, int heads_q, int heads_kv,
+                                    int total_q, int head_dim, int num_pages, int page_size,
+                                    const int* block_table, int max_pages_per_seq,
+                                    const int* kv_lens, const int* cu_seqlens_q, int causal,
+                                    int window, void* hip_stream);
+int fa_prefill_varlen_win_paged_bf16(const void* q, const void* k_pages, const void* v_pages,
+                                     void* o, float* lse, int batch, int heads_q, int heads_kv,
+                                     int total_q, int head_dim, int num_pages, int page_size,
+                                     const int* block_table, int max_pages_per_seq,
+                                     const int* kv_lens, const int* cu_seqlens_q, int causal,
+                                     int window, void* hip_stream);
+int fa_prefill_varlen_win_kv8_f16(const void* q, const void* k, const void* v, void* o, float* lse,
+                                  int batch, int heads_q, int heads_kv, int total_q,
+                                  int kv_capacity, int head_dim, const int* kv_lens,
+                                  const int* cu_seqlens_q, int causal, int window, void* hip_stream,
+                                  const float* k_scale, const float* v_scale);
+int fa_prefill_varlen_win_kv8_bf16(const void* q, const void* k, const void* v, void* o, float* lse,
+                                   int batch, int heads_q, int heads_kv, int total_q,
+                                   int kv_capacity, int head_dim, const int* kv_lens,
+                                   const int* cu_seqlens_q, int causal, int window,
+                                   void* hip_stream, const float* k_scale, const float* v_scale);
+int fa_prefill_varlen_win_paged_kv8_f16(const void* q, const void* k_pages, const void* v_pages,
+                                        void* o, float* lse, int batch, int heads_q, int heads_kv,
+                                        int total_q, int head_dim, int num_pages, int page_size,
+                                        const int* block_table, int max_pages_per_seq,
+                                        const int* kv_lens, const int* cu_seqlens_q, int causal,
+                                        int window, void* hip_stream, const float* k_scale,
+                                        const float* v_scale);
+int fa_prefill_varlen_win_paged_kv8_bf16(const void* q, const void* k_pages, const void* v_pages,
+                                         void* o, float* lse, int batch, int heads_q, int heads_kv,
+                                         int total_q, int head_dim, int num_pages, int page_size,
+                                         const int* block_table, int max_pages_per_seq,
+                                         const int* kv_lens, const int* cu_seqlens_q, int causal,
+                                         int window, void* hip_stream, const float* k_scale,
+                                         const float* v_scale);
+
 /* The dispatcher's decision (ref tier table :620-661): config id used by
  * fa_fwd_f16 for this shape.  The _ws entries may run the causal split tier
  * instead: check fa_fwd_split_pieces() first (> 0: the split tier runs with
