@@ -94,6 +94,18 @@ inline bool decode_fill_empty(void* o, float* lse, size_t nrow, int head_dim, hi
   return !lse || hipMemsetD32Async((hipDeviceptr_t)lse, (int)0xff800000u, nrow, stream) == hipSuccess;
 }
 
+// the same with sinks: O = 0, LSE = the row's head's sink (read on the device:
+// one small kernel).  PACKED: the packed prefill's [Hq][T] LSE.
+template <bool PACKED>
+inline bool decode_fill_empty_sink(void* o, float* lse, const float* sinks, size_t nrow, int heads_q,
+                                   int seqlen_q, int head_dim, hipStream_t stream) {
+  if (!sinks || !lse) return decode_fill_empty(o, lse, nrow, head_dim, stream);
+  if (hipMemsetAsync(o, 0, nrow * head_dim * 2, stream) != hipSuccess) return false;
+  hipLaunchKernelGGL((fa_sink_fill_lse_kernel<PACKED>), dim3((unsigned)((nrow + 255) / 256)), dim3(256), 0,
+                     stream, lse, sinks, nrow, heads_q, seqlen_q);
+  return hipGetLastError() == hipSuccess;
+}
+
 // the workspace's three regions for a launch of ns > 1 pieces
 template <class Params>
 inline void decode_set_workspace(Params& p, const DecodeGeom& ge, int ns, void* ws) {
@@ -160,15 +172,20 @@ struct DecodePages {
 // after the seqlen_q check, W = 0 (no window) runs as W = capacity, which
 // masks nothing, and num_splits = 0 plans from decode_window_capacity().
 // Without WIN `window` is not looked at (the entries pass 0).
-template <bool PAGED, bool KV8, bool WIN = false>
+// SINK (the fa_decode_sink_* entries, fa_decode_sink*.hip; with WIN): `sinks`
+// goes to the Sinked<Windowed<>> instantiations (nullptr: no sinks); the
+// statuses, the plan and the workspace are the windowed twin's.
+template <bool PAGED, bool KV8, bool WIN = false, bool SINK = false>
 static int decode_entry(int dtype, const void* q, const void* k, const void* v, void* o, float* lse,
                         int batch, int heads_q, int heads_kv, int seqlen_q, int kv_capacity,
                         int head_dim, const DecodePages& pg, const int* kv_lens, int causal,
                         int window, int num_splits, void* ws, unsigned long long ws_bytes,
-                        void* hip_stream, const float* k_scale, const float* v_scale) {
+                        void* hip_stream, const float* k_scale, const float* v_scale,
+                        [[maybe_unused]] const float* sinks = nullptr) {
+  static_assert(WIN || !SINK, "the sink kernels are instantiated over the windowed ones");
   using P0 = std::conditional_t<PAGED, std::conditional_t<KV8, DecodePagedKv8Params, DecodePagedParams>,
                                 std::conditional_t<KV8, DecodeKv8Params, DecodeParams>>;
-  using P = std::conditional_t<WIN, Windowed<P0>, P0>;
+  using P = std::conditional_t<SINK, Sinked<Windowed<P0>>, std::conditional_t<WIN, Windowed<P0>, P0>>;
   if (batch < 0 || heads_q < 0 || heads_kv < 0 || kv_capacity < 0 || head_dim < 0 || num_splits < 0)
     return FA_ERR_BAD_SHAPE;
   if (WIN && window < 0) return FA_ERR_BAD_SHAPE;
@@ -203,6 +220,10 @@ static int decode_entry(int dtype, const void* q, const void* k, const void* v, 
   if (kv_capacity == 0) {
     // rows but no keys: O = 0, LSE = -inf; nothing else runs
     if (!o) return FA_ERR_NULL_POINTER;
+    if constexpr (SINK)
+      return decode_fill_empty_sink<false>(o, lse, sinks, nrow, heads_q, seqlen_q, head_dim, stream)
+                 ? FA_OK
+                 : FA_ERR_HIP;
     return decode_fill_empty(o, lse, nrow, head_dim, stream) ? FA_OK : FA_ERR_HIP;
   }
   if (!q || !k || !v || !o || (PAGED && !pg.block_table)) return FA_ERR_NULL_POINTER;
@@ -240,6 +261,7 @@ static int decode_entry(int dtype, const void* q, const void* k, const void* v, 
   p.c = 1.4426950408889634f / sqrtf((float)head_dim);
   if (ns > 1) decode_set_workspace(p, ge, ns, ws);
   if constexpr (WIN) p.window = window > 0 ? std::min(window, kv_capacity) : kv_capacity;
+  if constexpr (SINK) p.sinks = sinks;
   if constexpr (PAGED) {
     p.table = pg.block_table;
     p.max_pages = pg.max_pages_per_seq;

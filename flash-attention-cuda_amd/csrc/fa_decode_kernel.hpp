@@ -115,6 +115,37 @@ template <class P>
 struct ParamsWindowed : std::false_type {};
 template <class Base>
 struct ParamsWindowed<Windowed<Base>> : std::true_type {};
+// The attention-sink entries (fa_decode_sink_*, fa_prefill[_varlen]_sink_*)
+// pass Sinked<Windowed<...>>: `sinks` is a device array of Hq floats (nullptr:
+// no sinks), one logit per query head in natural-log units that joins the
+// softmax denominator and carries no value:
+//   den = exp(sinks[h]) + sum_j exp(s_j),  O = sum_j exp(s_j) v_j / den,
+//   LSE = log(den);  a row that sees no key: O = 0, LSE = sinks[h].
+// The kernels take SINK from the type as they take WIN, and the sink enters
+// once, where a row's (m, l) becomes 1 / l and the LSE (sink_fold() of
+// fa_fwd_kernel.hpp).
+template <class Base>
+struct Sinked : Base {
+  const float* sinks;
+};
+template <class P>
+struct ParamsSinked : std::false_type {};
+template <class Base>
+struct ParamsSinked<Sinked<Base>> : std::true_type {};
+template <class Base>
+struct ParamsWindowed<Sinked<Base>> : ParamsWindowed<Base> {};
+
+// Rows but no keys, with sinks: LSE[row] = sinks[head of the row].  Padded
+// layouts [B][Hq][Sq] (head = row / sq % hq); PACKED: [Hq][T] (head = row / sq,
+// sq = T).
+template <bool PACKED>
+__global__ void fa_sink_fill_lse_kernel(float* lse, const float* sinks, size_t nrow, int hq, int sq) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= nrow) return;
+  const size_t h = PACKED ? i / (size_t)sq : i / (size_t)sq % (size_t)hq;
+  lse[i] = sinks[h];
+}
+
 // an offset no K/V descriptor's range reaches: the load returns zeros and
 // moves no memory.  The windowed kernels give it to the lanes whose row of the
 // first tile lies below the window, so those rows are not read at all.
@@ -152,10 +183,14 @@ constexpr int decode_lds_bytes() {
 // The last-arriving piece's merge of a unit's NS partials, in piece order:
 //   O = sum_s 2^(lse_s - M) O_s / sum_s 2^(lse_s - M),  M = max_s lse_s.
 // Thread = one 16-B chunk (4 fp32) of one row; every slab load is sc1.
-template <class T, int HDIM, int NB>
+// SINK: the row's sink is one more term, with O = 0 and log2-sum-exp sink2 (the
+// pieces' partials carry none of it, so it counts once).
+template <class T, int HDIM, int NB, bool SINK = false>
 __device__ __forceinline__ void decode_merge_pieces(const DecodeParams& p, size_t unit, int ns,
                                                     __amdgpu_buffer_rsrc_t ro, float* lse_out,
-                                                    int row0, int tid) {
+                                                    int row0, int tid,
+                                                    [[maybe_unused]] const float* sinks = nullptr,
+                                                    [[maybe_unused]] int hk = 0) {
   constexpr int kSc1 = 16, RW = 16 * NB, CH = HDIM / 4;
   typedef typename Elem<T>::x4 tx4;
   const __amdgpu_buffer_rsrc_t rs =
@@ -164,12 +199,19 @@ __device__ __forceinline__ void decode_merge_pieces(const DecodeParams& p, size_
   for (int idx = tid; idx < RW * CH; idx += 256) {
     const int row = idx / CH, ch = idx - row * CH;
     float M = ninf();
+    if constexpr (SINK) {
+      // row r of the K/V head's group * Sq rows belongs to head hk * group + r / Sq
+      if (sinks)
+        M = sinks[hk * p.group + min(row0 + row, p.rows - 1) / p.sq] * 1.4426950408889634f;
+    }
+    [[maybe_unused]] const float sink2 = M;
 #pragma unroll 4
     for (int s = 0; s < ns; ++s)
       M = fmaxf(M, __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
                                                  rls, (s * RW + row) * 4, 0, kSc1)));
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     float den = 0.f;
+    if constexpr (SINK) den = sink2 == ninf() ? 0.f : __builtin_amdgcn_exp2f(sink2 - M);
 #pragma unroll 4
     for (int s = 0; s < ns; ++s) {
       const float l = __builtin_bit_cast(
@@ -218,6 +260,7 @@ __global__ __launch_bounds__(256, 1) void fa_decode_kernel(P p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr bool KV8 = !std::is_same<KV, T>::value;
   constexpr bool WIN = ParamsWindowed<P>::value;
+  constexpr bool SINK = ParamsSinked<P>::value;
   static_assert(!KV8 || std::is_same<KV, unsigned char>::value, "the cache holds T or E4M3 bytes");
   constexpr int ROW = 2 * HDIM;      // bytes per Q/O row
   constexpr int CROW = KV8 ? HDIM : 2 * HDIM;  // bytes per K/V cache row
@@ -668,9 +711,22 @@ __global__ __launch_bounds__(256, 1) void fa_decode_kernel(P p) {
       mw[w] = M == ninf() ? 0.f : __builtin_amdgcn_exp2f(mw[w] - M);  // now the weight
       L = __builtin_fmaf(mw[w], lw[w], L);
     }
-    const float inv = KV8 ? (L > 0.f ? 1.0f / L : 0.f) * vsc : L > 0.f ? 1.0f / L : 0.f;
-    const float lse2 = L > 0.f ? M + __builtin_log2f(L) : ninf();
+    float inv = KV8 ? (L > 0.f ? 1.0f / L : 0.f) * vsc : L > 0.f ? 1.0f / L : 0.f;
+    float lse2 = L > 0.f ? M + __builtin_log2f(L) : ninf();
     const int row = 16 * nb + er16;
+    if constexpr (SINK) {
+      // the row's sink (rows of one workgroup span several heads), folded in
+      // here only when this workgroup's normalisation is the final one; a
+      // piece's partial carries none of it (decode_merge_pieces adds it once)
+      float sink2 = ninf();
+      if (p.sinks && !split)
+        sink2 = p.sinks[hk * p.group + min(row0 + row, p.rows - 1) / p.sq] * 1.4426950408889634f;
+      float f, Mp;
+      const float Lp = sink_fold(M, L, sink2, f, Mp);
+      const float invp = Lp > 0.f ? 1.0f / Lp : 0.f;
+      inv = f * (KV8 ? invp * vsc : invp);
+      lse2 = Lp > 0.f ? Mp + __builtin_log2f(Lp) : ninf();
+    }
 #pragma unroll
     for (int ee = 0; ee < EW; ++ee) {
       const int e = wave * EW + ee;
@@ -713,7 +769,10 @@ __global__ __launch_bounds__(256, 1) void fa_decode_kernel(P p) {
   }
   __syncthreads();
   if (!*last) return;
-  decode_merge_pieces<T, HDIM, NB>(p, unit, ns, ro, lse_out, row0, etid);
+  if constexpr (SINK)
+    decode_merge_pieces<T, HDIM, NB, true>(p, unit, ns, ro, lse_out, row0, etid, p.sinks, hk);
+  else
+    decode_merge_pieces<T, HDIM, NB>(p, unit, ns, ro, lse_out, row0, etid);
   if (etid == 0) __hip_atomic_store(p.ws_ctr + unit, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 

@@ -184,6 +184,20 @@ __device__ __forceinline__ f16x4 lds_read_tr(const char* base, int off) {
 }
 
 __device__ __forceinline__ float ninf() { return -__builtin_inff(); }
+// An attention sink's fold into a row's final (M, l) (the Sinked<> kernels of
+// fa_decode_kernel.hpp and fa_prefill_kernel.hpp), both in log2 units (l relative to
+// M; l == 0: the row saw no key and M is not looked at).  Relative to the safe
+// maximum M' = max(M, sink2), never as 2^(sink2 - M) alone:
+//   f  = 2^(M - M')                 the factor on O and l
+//   l' = l f + 2^(sink2 - M')       (>= 1 when there is a sink)
+// Returns l' and sets f and M'.  sink2 = -inf gives f = 1, M' = M, l' = l.
+__device__ __forceinline__ float sink_fold(float M, float l, float sink2, float& f, float& Mp) {
+  const bool any = l > 0.f;
+  Mp = any ? fmaxf(M, sink2) : sink2;
+  f = any ? __builtin_amdgcn_exp2f(M - Mp) : 0.f;
+  const float es = sink2 == ninf() ? 0.f : __builtin_amdgcn_exp2f(sink2 - Mp);
+  return __builtin_fmaf(l, f, es);
+}
 
 // Cache policy of the O stores: sc1 (write-through; the line leaves the
 // XCD's L2 with the store).  O is written once and never re-read by the
@@ -272,7 +286,11 @@ struct Elem {
 // and the ones . P MFMAs are not issued: l then carries none of T's rounding
 // of P, which an LSE of a row with few keys would show.  The default keeps
 // the matrix-pipe sums; no other instantiation changes.
-template <int BN_, class T = f16, int HDIM_ = 128, int QB_ = 2, bool L32_ = false>
+// RTS_ (the prefill kernel's fp16 Sinked<> instantiations): whether the scores
+// are scaled in fp32 (kScaleS's arithmetic) is the wave-uniform member
+// scale_s_rt, set after init(): false is the fp16 arithmetic of every other
+// fp16 instantiation, bit for bit.  The default is the code without it.
+template <int BN_, class T = f16, int HDIM_ = 128, int QB_ = 2, bool L32_ = false, bool RTS_ = false>
 struct M16 {
   static_assert(QB_ == 2, "two 16-row query blocks per wave (the merge layouts assume it)");
   static_assert(HDIM_ == 64 || HDIM_ == 128, "head_dim 64 or 128");
@@ -307,6 +325,7 @@ struct M16 {
   float l32[QB];      // L32_: this lane's share of l (fp32 exponentials)
   bool have_ref;     // wave-uniform: a tile has set m_ref
   bool seen[QB];     // softmax<.., WIN>: per row, a tile has set m_ref
+  bool scale_s_rt;   // RTS_: scale the fp32 scores, not Q (wave-uniform)
   float c;
 
   __device__ __forceinline__ void init(int lane_, float c_) {
@@ -347,6 +366,12 @@ struct M16 {
             tx8, buf_load16(rq, (qw + 16 * b + r16) * rs + (4 * t + g) * 16));
   }
   __device__ __forceinline__ void scale_q() {
+    if constexpr (RTS_) {
+      if (scale_s_rt) {
+        pin_q();
+        return;
+      }
+    }
     if constexpr (kScaleS) {
       pin_q();
       return;
@@ -465,6 +490,14 @@ struct M16 {
   template <bool CAUSAL, bool WIN = false>
   __device__ __forceinline__ void softmax(int kv0, int kv_hi, int qw, float /*c*/, bool need_mask,
                                           [[maybe_unused]] int win = 0) {
+    if constexpr (RTS_) {
+      if (scale_s_rt) {
+#pragma unroll
+        for (int b = 0; b < QB; ++b)
+#pragma unroll
+          for (int cb = 0; cb < NKB; ++cb) s[b][cb] *= c;
+      }
+    }
     if constexpr (kScaleS) {
 #pragma unroll
       for (int b = 0; b < QB; ++b)
@@ -535,7 +568,8 @@ struct M16 {
 #pragma unroll
         for (int cb = 0; cb < NKB; ++cb) s[b][cb] -= sh;
         m_ref[b] += sh;
-        const float nm = kScaleS ? -m_ref[b] / c : -m_ref[b];
+        float nm = kScaleS ? -m_ref[b] / c : -m_ref[b];
+        if constexpr (RTS_) nm = scale_s_rt ? -m_ref[b] / c : -m_ref[b];
         negm[b] = f32x4{nm, nm, nm, nm};
       }
       have_ref = true;
@@ -617,13 +651,21 @@ struct M16 {
   // row blocks [B0, B1), d-block pairs [EP0, EP1) (symmetric merges store a part each)
   // osc: a factor on the normalisation (the FP8 cache's V scale, fa_prefill_kernel.hpp)
   // rs: bytes between consecutive rows, as for issue_q
-  template <int B0 = 0, int B1 = QB, int EP0 = 0, int EP1 = NE / 2>
+  // SINK (the prefill kernel's Sinked<> instantiations): an attention sink of
+  // sink2 (log2 units) joins every row's denominator, sink_fold(); the default
+  // is the code without one.
+  template <int B0 = 0, int B1 = QB, int EP0 = 0, int EP1 = NE / 2, bool SINK = false>
   __device__ __forceinline__ void store_o(__amdgpu_buffer_rsrc_t ro, int qw, float osc = 1.0f,
-                                          int rs = ROW) {
+                                          int rs = ROW, [[maybe_unused]] float sink2 = 0.f) {
 #pragma unroll
     for (int b = B0; b < B1; ++b) {
       const float lt = row_sum(b);  // already the full row sum (MFMA over all keys)
-      const float inv = (lt > 0.f ? 1.0f / lt : 0.f) * osc;
+      float inv = (lt > 0.f ? 1.0f / lt : 0.f) * osc;
+      if constexpr (SINK) {
+        float f, mp;
+        const float lp = sink_fold(m_ref[b], lt, sink2, f, mp);
+        inv = f * ((lp > 0.f ? 1.0f / lp : 0.f) * osc);
+      }
       const int rowb = (qw + 16 * b + r16) * rs;
       const int dlane = 16 * (g & 1) + 8 * (g >> 1);
 #pragma unroll

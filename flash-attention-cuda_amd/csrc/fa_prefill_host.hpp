@@ -40,15 +40,19 @@ static int prefill_launch_inst(const P& p, unsigned grid, hipStream_t stream) {
 // with decode_entry's rules: a negative W is refused with the negative shapes,
 // W > 0 without causal right after the seqlen_q check, and W = 0 (no window)
 // runs as W = capacity.  Without WIN `window` is not looked at.
-template <bool PAGED, bool KV8, bool VARLEN = false, bool WIN = false>
+// SINK (the fa_prefill[_varlen]_sink_* entries, fa_prefill*_sink*.hip; with
+// WIN): `sinks` goes to the Sinked<Windowed<>> instantiations (nullptr: no
+// sinks); every status is the windowed twin's.
+template <bool PAGED, bool KV8, bool VARLEN = false, bool WIN = false, bool SINK = false>
 static int prefill_entry(int dtype, const void* q, const void* k, const void* v, void* o, float* lse,
                          int batch, int heads_q, int heads_kv, int seqlen_q, int kv_capacity,
                          int head_dim, const DecodePages& pg, const int* kv_lens, const int* q_lens,
                          int causal, int window, void* hip_stream, const float* k_scale,
-                         const float* v_scale) {
+                         const float* v_scale, [[maybe_unused]] const float* sinks = nullptr) {
+  static_assert(WIN || !SINK, "the sink kernels are instantiated over the windowed ones");
   using P0 = std::conditional_t<PAGED, std::conditional_t<KV8, PrefillPagedKv8Params, PrefillPagedParams>,
                                 std::conditional_t<KV8, PrefillKv8Params, PrefillParams>>;
-  using P = std::conditional_t<WIN, Windowed<P0>, P0>;
+  using P = std::conditional_t<SINK, Sinked<Windowed<P0>>, std::conditional_t<WIN, Windowed<P0>, P0>>;
   if (batch < 0 || heads_q < 0 || heads_kv < 0 || kv_capacity < 0 || head_dim < 0)
     return FA_ERR_BAD_SHAPE;
   if (WIN && window < 0) return FA_ERR_BAD_SHAPE;
@@ -92,6 +96,10 @@ static int prefill_entry(int dtype, const void* q, const void* k, const void* v,
     // rows but no keys: O = 0, LSE = -inf for every row; nothing else runs
     if (!o) return FA_ERR_NULL_POINTER;
     const size_t nrow = (VARLEN ? (size_t)1 : (size_t)batch) * heads_q * seqlen_q;
+    if constexpr (SINK)
+      return decode_fill_empty_sink<VARLEN>(o, lse, sinks, nrow, heads_q, seqlen_q, head_dim, stream)
+                 ? FA_OK
+                 : FA_ERR_HIP;
     return decode_fill_empty(o, lse, nrow, head_dim, stream) ? FA_OK : FA_ERR_HIP;
   }
   if (!q || !k || !v || !o || (PAGED && !pg.block_table) || (VARLEN && !q_lens))
@@ -114,6 +122,7 @@ static int prefill_entry(int dtype, const void* q, const void* k, const void* v,
   p.causal = causal ? 1 : 0;
   p.c = 1.4426950408889634f / sqrtf((float)head_dim);
   if constexpr (WIN) p.window = window > 0 ? std::min(window, kv_capacity) : kv_capacity;
+  if constexpr (SINK) p.sinks = sinks;
   if constexpr (PAGED) {
     p.table = pg.block_table;
     p.max_pages = pg.max_pages_per_seq;

@@ -114,6 +114,9 @@ struct PrefillIsPacked<PrefillPacked<Base>> : std::true_type {};
 // the packed windowed entries pass PrefillPacked<Windowed<Base>>
 template <class Base>
 struct ParamsWindowed<PrefillPacked<Base>> : ParamsWindowed<Base> {};
+// ... and the packed sink entries PrefillPacked<Sinked<Windowed<Base>>>
+template <class Base>
+struct ParamsSinked<PrefillPacked<Base>> : ParamsSinked<Base> {};
 
 // WIN (P = [PrefillPacked<]Windowed<...>[>], the fa_prefill[_varlen]_win_*
 // entries; without causal the host admits W = 0 alone and the kernel applies
@@ -127,14 +130,27 @@ struct ParamsWindowed<PrefillPacked<Base>> : ParamsWindowed<Base> {};
 // rows (it still stages and takes the barrier), and the softmax reference is
 // set per row (M16::softmax<.., WIN>).  All of it sits under
 // `if constexpr (WIN)`: the other instantiations carry none of it.
+//
+// SINK (P = [PrefillPacked<]Sinked<Windowed<...>>[>], the
+// fa_prefill[_varlen]_sink_* entries): all rows of a workgroup share query
+// head hq, so the sink is one scalar, sink2 = sinks[hq] log2(e), folded into
+// the epilogue relative to max(m_ref, sink2) (sink_fold(): m_ref is a lazy
+// reference, so 2^(sink2 - m_ref) alone overflows).  sinks = nullptr or -inf:
+// the factor is 1 and l' = l, the windowed kernel's bits.  fp16: a head with a
+// sink takes the fp32 score scaling (M16's RTS_): a sink is compared with the
+// scores on their absolute level, which fp16's rounded Q c misses by 2^-11.
 template <class T, int HDIM, bool PAGED = false, class P = PrefillParams, class KV = T>
 __global__ __launch_bounds__(256, 2) void fa_prefill_kernel(P p) {
   constexpr bool VARLEN = PrefillIsPacked<P>::value;
   constexpr bool WIN = ParamsWindowed<P>::value;
+  constexpr bool SINK = ParamsSinked<P>::value;
   __shared__ __attribute__((aligned(16))) char smem[kPrefillLdsBytes];
   constexpr bool KV8 = !std::is_same<KV, T>::value;
   static_assert(!KV8 || std::is_same<KV, unsigned char>::value, "the cache holds T or E4M3 bytes");
-  using Pol = M16<64, T, HDIM, 2, std::is_same<T, __bf16>::value>;
+  // fp16 with sinks: whether the scores are scaled in fp32 is decided per
+  // workgroup, from its head's sink (RTS, below)
+  constexpr bool RTS = SINK && !std::is_same<T, __bf16>::value;
+  using Pol = M16<64, T, HDIM, 2, std::is_same<T, __bf16>::value, RTS>;
   constexpr int BN = 64, WAVES = 4, RW = Pol::RW, BM = kPrefillBM;
   static_assert(WAVES * RW == BM, "four waves of 32 rows");
   constexpr int ROW = 2 * HDIM;                // bytes per Q/O row
@@ -236,8 +252,19 @@ __global__ __launch_bounds__(256, 2) void fa_prefill_kernel(P p) {
     if (p.v_scale) vsc = p.v_scale[hk];
   }
 
+  // SINK: the head's sink in log2 units (a wave-uniform load)
+  [[maybe_unused]] float sink2 = ninf();
+  if constexpr (SINK) {
+    if (p.sinks) sink2 = p.sinks[hq] * 1.4426950408889634f;
+  }
   Pol pol;
   pol.init(lane, csc);
+  // RTS: a head with a sink scales its fp32 scores by c, as the bf16 kernels
+  // do, instead of rounding Q c to fp16 (2^-11 of every score: an offset that
+  // cancels in O without a sink and weighs the sink wrongly beside one); a
+  // head without one (-inf, or sinks == nullptr) keeps the windowed kernel's
+  // arithmetic and so its bits
+  if constexpr (RTS) pol.scale_s_rt = sink2 != ninf();
   pol.issue_q(rq, qwl, qs);  // scaled once tile 0's loads are in flight
 
   // Staging.  16-bit: the policy's lanes (K natural row-major, V two rows of
@@ -412,13 +439,22 @@ __global__ __launch_bounds__(256, 2) void fa_prefill_kernel(P p) {
   }
   if (j < ntiles) step(j, std::integral_constant<int, 0>{});
 
-  pol.store_o(ro, qwl, vsc, qs);
+  if constexpr (SINK) {
+    pol.template store_o<0, Pol::QB, 0, Pol::NE / 2, true>(ro, qwl, vsc, qs, sink2);
+  } else {
+    pol.store_o(ro, qwl, vsc, qs);
+  }
   if (p.lse) {
     const __amdgpu_buffer_rsrc_t rl = make_rsrc(p.lse + lrow0, qrows * 4);
 #pragma unroll
     for (int bb = 0; bb < Pol::QB; ++bb) {
-      const float l = pol.row_sum(bb);
-      const float lse = l > 0.f ? (pol.m_ref[bb] + __builtin_log2f(l)) * 0.6931471805599453f : ninf();
+      float l = pol.row_sum(bb);
+      float mr = pol.m_ref[bb];
+      if constexpr (SINK) {
+        float f;
+        l = sink_fold(pol.m_ref[bb], l, sink2, f, mr);
+      }
+      const float lse = l > 0.f ? (mr + __builtin_log2f(l)) * 0.6931471805599453f : ninf();
       if (pol.g == 0)
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, lse), rl,
                                               (qwl + 16 * bb + pol.r16) * 4, 0, 0);

@@ -110,6 +110,30 @@ EXPORTED_SYMBOLS = (
     "fa_prefill_varlen_win_kv8_bf16",
     "fa_prefill_varlen_win_paged_kv8_f16",
     "fa_prefill_varlen_win_paged_kv8_bf16",
+    "fa_decode_sink_f16",
+    "fa_decode_sink_bf16",
+    "fa_decode_sink_paged_f16",
+    "fa_decode_sink_paged_bf16",
+    "fa_decode_sink_kv8_f16",
+    "fa_decode_sink_kv8_bf16",
+    "fa_decode_sink_paged_kv8_f16",
+    "fa_decode_sink_paged_kv8_bf16",
+    "fa_prefill_sink_f16",
+    "fa_prefill_sink_bf16",
+    "fa_prefill_sink_paged_f16",
+    "fa_prefill_sink_paged_bf16",
+    "fa_prefill_sink_kv8_f16",
+    "fa_prefill_sink_kv8_bf16",
+    "fa_prefill_sink_paged_kv8_f16",
+    "fa_prefill_sink_paged_kv8_bf16",
+    "fa_prefill_varlen_sink_f16",
+    "fa_prefill_varlen_sink_bf16",
+    "fa_prefill_varlen_sink_paged_f16",
+    "fa_prefill_varlen_sink_paged_bf16",
+    "fa_prefill_varlen_sink_kv8_f16",
+    "fa_prefill_varlen_sink_kv8_bf16",
+    "fa_prefill_varlen_sink_paged_kv8_f16",
+    "fa_prefill_varlen_sink_paged_kv8_bf16",
     "fa_select_config",
     "fa_num_configs",
     "fa_config_info",
@@ -262,6 +286,10 @@ def load_library() -> ctypes.CDLL:
                 at = len(base) - after - (2 if "kv8" in form else 0)  # causal's successor
                 fn = getattr(lib, fam + "_win" + form + ty)
                 fn.argtypes = base[:at] + [i] + base[at:]
+                fn.restype = i
+                # the attention-sink twins of those: `const float* sinks` directly after `window`
+                fn = getattr(lib, fam + "_sink" + form + ty)
+                fn.argtypes = base[:at] + [i, vp] + base[at:]
                 fn.restype = i
     lib.fa_decode_num_splits.argtypes = [i, i, i, i, i, i]
     lib.fa_decode_num_splits.restype = i
@@ -543,14 +571,16 @@ def _check_table_type(block_table):
 
 
 def _check_decode_tail(q, kname, k, vname, v, out, k_scale, v_scale, block_table, kv_lens,
-                       qname="q", oname="out", batch=None):
+                       qname="q", oname="out", batch=None, sinks=None):
     """What both decode checks end with, after the family's own shape checks:
     Hq % Hkv, each scale (if given) a contiguous float32 [Hkv] tensor, the
     block table (paged only: None otherwise), kv_lens, and then where all of
     them live.  The append checks end with it too, with k_new and v_new
     (`qname`, `oname`) in the places of q and out.  `batch`: the number of
     sequences where q's first extent is not it (the packed wrappers, whose q is
-    [T,Hq,D]: heads are extent 1 there too)."""
+    [T,Hq,D]: heads are extent 1 there too).  `sinks` (the decode and prefill
+    wrappers only): a contiguous float32 [Hq] tensor, checked after the scales
+    and like them; its values are not looked at."""
     import torch
 
     if batch is None:
@@ -568,6 +598,14 @@ def _check_decode_tail(q, kname, k, vname, v, out, k_scale, v_scale, block_table
             raise FlashAttentionError(
                 FA_ERR_BAD_SHAPE,
                 f"{name} must be a contiguous float32 [Hkv = {heads_kv}] tensor, got {got}")
+    if sinks is not None:
+        t = sinks
+        if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 1
+                or t.shape[0] != q.shape[1] or not t.is_contiguous()):
+            got = f"{t.dtype} {list(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+            raise FlashAttentionError(
+                FA_ERR_BAD_SHAPE,
+                f"sinks must be a contiguous float32 [Hq = {q.shape[1]}] tensor, got {got}")
     if block_table is not None:
         _check_table_type(block_table)
         if block_table.shape[0] != batch:
@@ -591,6 +629,8 @@ def _check_decode_tail(q, kname, k, vname, v, out, k_scale, v_scale, block_table
         if t is not None and (not t.is_cuda or t.device != q.device):
             raise FlashAttentionError(FA_ERR_NULL_POINTER, f"{name} must be a tensor on {q.device}")
     _check_scales_device(q, k_scale, v_scale)
+    if sinks is not None and (not sinks.is_cuda or sinks.device != q.device):
+        raise FlashAttentionError(FA_ERR_NULL_POINTER, f"sinks must be a tensor on {q.device}")
 
 
 def _check_q_lens(q, q_lens, where):
@@ -611,7 +651,7 @@ def _check_q_lens(q, q_lens, where):
         raise FlashAttentionError(FA_ERR_BAD_SHAPE, "q_lens must be a contiguous [B] tensor")
 
 
-def _check_decode(q, k_cache, v_cache, kv_lens, out, k_scale=None, v_scale=None, q_lens=None):
+def _check_decode(q, k_cache, v_cache, kv_lens, out, k_scale=None, v_scale=None, q_lens=None, sinks=None):
     """Raise FlashAttentionError unless q/out are contiguous [B,Hq,Sq,D] and
     k_cache/v_cache contiguous [B,Hkv,cap,D] device tensors of one 16-bit dtype
     (or both torch.float8_e4m3fn beside a 16-bit q, with optional float32
@@ -626,13 +666,14 @@ def _check_decode(q, k_cache, v_cache, kv_lens, out, k_scale=None, v_scale=None,
     if k_cache.shape[0] != q.shape[0] or k_cache.shape[3] != q.shape[3]:
         raise FlashAttentionError(FA_ERR_BAD_SHAPE, "q and the caches must agree in batch and head_dim")
     _check_q_lens(q, q_lens, False)
-    _check_decode_tail(q, "k_cache", k_cache, "v_cache", v_cache, out, k_scale, v_scale, None, kv_lens)
+    _check_decode_tail(q, "k_cache", k_cache, "v_cache", v_cache, out, k_scale, v_scale, None, kv_lens,
+                       sinks=sinks)
     _check_q_lens(q, q_lens, True)
     return kv8
 
 
 def _check_decode_paged(q, k_pages, v_pages, block_table, kv_lens, out, k_scale=None, v_scale=None,
-                        q_lens=None):
+                        q_lens=None, sinks=None):
     """Raise FlashAttentionError unless q/out are contiguous [B,Hq,Sq,D],
     k_pages/v_pages contiguous [num_pages,Hkv,page_size,D] pools of q's 16-bit
     dtype (or both torch.float8_e4m3fn, with optional float32 [Hkv] scales:
@@ -653,7 +694,7 @@ def _check_decode_paged(q, k_pages, v_pages, block_table, kv_lens, out, k_scale=
                                   f"page_size {k_pages.shape[2]} is not a positive multiple of 64")
     _check_q_lens(q, q_lens, False)
     _check_decode_tail(q, "k_pages", k_pages, "v_pages", v_pages, out, k_scale, v_scale, block_table,
-                       kv_lens)
+                       kv_lens, sinks=sinks)
     _check_q_lens(q, q_lens, True)
     return kv8
 
@@ -682,21 +723,31 @@ def decode_window_capacity(kv_capacity: int, seqlen_q: int, window: int) -> int:
     return min(kv_capacity, 64 * ((window + seqlen_q - 1 + 63) // 64) + 64)
 
 
-_DEC_ENTRY = {}  # (paged, kv8, bf16, windowed) -> the C entry
+def _entry_variant(window, sinks):
+    """Which twin of an entry a call takes and what it passes after `causal`:
+    sinks given: the `_sink` entry with (window, sinks), window 0 included;
+    else window > 0: the `_win` entry with (window,); else the plain entry."""
+    if sinks is not None:
+        return "_sink", (window, sinks.data_ptr())
+    return ("_win", (window,)) if window else ("", ())
+
+
+_DEC_ENTRY = {}  # (paged, kv8, bf16, "" / "_win" / "_sink") -> the C entry
 
 
 def _decode_call(kv8, q, k, v, out, block_table, kv_lens, causal, return_lse, num_splits, stream,
-                 k_scale, v_scale, window=0):
+                 k_scale, v_scale, window=0, sinks=None):
     """The call of both decode functions after their checks: the stream, the
     optional LSE, the split workspace and the C entry of q's dtype.
     block_table: None when k, v are a contiguous cache (the fa_decode_*
     entries), the table when they are page pools (the fa_decode_paged_*
     entries); kv8: the _kv8 entries, which also take the two scales; window >
     0: the fa_decode_win_* entries, whose plan and workspace follow
-    :func:`decode_window_capacity`."""
+    :func:`decode_window_capacity`; sinks: the fa_decode_sink_* entries, at any
+    window."""
     import torch
 
-    win = (window,) if window else ()  # checked by the public function
+    variant, win = _entry_variant(window, sinks)  # checked by the public function
     b, hq, sq, d = q.shape
     hkv, cap = k.shape[1], k.shape[2]
     paged = block_table is not None
@@ -707,10 +758,10 @@ def _decode_call(kv8, q, k, v, out, block_table, kv_lens, causal, return_lse, nu
     else:
         cache = (cap, d)
     lib = _lib or load_library()
-    which = (paged, kv8, q.dtype is torch.bfloat16, bool(win))
+    which = (paged, kv8, q.dtype is torch.bfloat16, variant)
     fn = _DEC_ENTRY.get(which)
     if fn is None:
-        fn = _DEC_ENTRY[which] = getattr(lib, "fa_decode" + ("_win" if win else "")
+        fn = _DEC_ENTRY[which] = getattr(lib, "fa_decode" + variant
                                          + ("_paged" if paged else "")
                                          + ("_kv8" if kv8 else "") + ("_bf16" if which[2] else "_f16"))
     tail = ()
@@ -728,7 +779,7 @@ def _decode_call(kv8, q, k, v, out, block_table, kv_lens, causal, return_lse, nu
         need = 0
         if not paged or cap <= 0x7fffffff - 64:  # (past it the paged entry itself refuses the shape)
             # a windowed call plans (and needs a workspace) as for the window's capacity
-            pcap = decode_window_capacity(cap, sq, win[0]) if win else cap
+            pcap = decode_window_capacity(cap, sq, window)
             key = (dev, b, hq, hkv, sq, pcap, d, ns)
             need = _DEC_NEED.get(key)
             if need is None:
@@ -745,7 +796,7 @@ def _decode_call(kv8, q, k, v, out, block_table, kv_lens, causal, return_lse, nu
 
 def flash_attention_decode(q, k_cache, v_cache, kv_lens=None, causal: bool = True, out=None,
                            return_lse: bool = False, num_splits: int = 0, stream=None,
-                           k_scale=None, v_scale=None, window: int = 0):
+                           k_scale=None, v_scale=None, window: int = 0, sinks=None):
     """Decode attention over a K/V cache (fa_decode_f16 / fa_decode_bf16, or
     fa_decode_kv8_* over an FP8 cache).
 
@@ -775,20 +826,33 @@ def flash_attention_decode(q, k_cache, v_cache, kv_lens=None, causal: bool = Tru
     freed or reused.
     With num_splits = 0 a windowed call is planned from
     :func:`decode_window_capacity`, the keys it can touch.
+
+    sinks: None, or attention sinks: a contiguous float32 [Hq] tensor on q's
+    device, one learned logit per query head that joins the softmax
+    denominator and contributes no value (the fa_decode_sink_* entries, at any
+    window, 0 included, and with causal=False when window=0).  With s_j the
+    row's scaled scores (after 1/sqrt(D) and k_scale) over the keys it sees --
+    the same keys as without sinks -- den = exp(sinks[h]) + sum_j exp(s_j),
+    out = sum_j exp(s_j) v_j / den and lse = log(den); the sink takes neither
+    1/sqrt(D) nor k_scale.  A row that sees no key gives zeros and lse =
+    sinks[h]; -inf is "no sink for that head".  The values are read on the
+    device, so a captured graph follows them; the split plan and the workspace
+    are unchanged.  lse includes the sink: a caller merging partial states by
+    their lse must pass sinks to ONE partial only.
     """
     window = _check_window(window, causal)  # before the tensors: a bad window is named whatever they are
     if out is None:
         import torch
 
         out = torch.empty_like(q)
-    kv8 = _check_decode(q, k_cache, v_cache, kv_lens, out, k_scale, v_scale)
+    kv8 = _check_decode(q, k_cache, v_cache, kv_lens, out, k_scale, v_scale, sinks=sinks)
     return _decode_call(kv8, q, k_cache, v_cache, out, None, kv_lens, causal, return_lse, num_splits,
-                        stream, k_scale, v_scale, window)
+                        stream, k_scale, v_scale, window, sinks)
 
 
 def flash_attention_decode_paged(q, k_pages, v_pages, block_table, kv_lens=None, causal: bool = True,
                                  out=None, return_lse: bool = False, num_splits: int = 0, stream=None,
-                                 k_scale=None, v_scale=None, window: int = 0):
+                                 k_scale=None, v_scale=None, window: int = 0, sinks=None):
     """Decode attention over a paged K/V cache (fa_decode_paged_f16 / _bf16, or
     fa_decode_paged_kv8_* over an FP8 pool).
 
@@ -807,31 +871,34 @@ def flash_attention_decode_paged(q, k_pages, v_pages, block_table, kv_lens=None,
     whose result on the gathered cache this one equals bit for bit.  Pools of
     torch.float8_e4m3fn with k_scale / v_scale, and window: as for that
     function (fa_decode_win_paged_*); block-table entries of pages wholly
-    below the window are never read.
+    below the window are never read.  sinks: as for that function
+    (fa_decode_sink_paged_*): pass them to one partial only when merging by lse.
     """
     window = _check_window(window, causal)  # before the tensors: a bad window is named whatever they are
     if out is None:
         import torch
 
         out = torch.empty_like(q)
-    kv8 = _check_decode_paged(q, k_pages, v_pages, block_table, kv_lens, out, k_scale, v_scale)
+    kv8 = _check_decode_paged(q, k_pages, v_pages, block_table, kv_lens, out, k_scale, v_scale,
+                              sinks=sinks)
     return _decode_call(kv8, q, k_pages, v_pages, out, block_table, kv_lens, causal, return_lse,
-                        num_splits, stream, k_scale, v_scale, window)
+                        num_splits, stream, k_scale, v_scale, window, sinks)
 
 
-_PRE_ENTRY = {}  # (paged, kv8, bf16, windowed) -> the C entry
+_PRE_ENTRY = {}  # (paged, kv8, bf16, "" / "_win" / "_sink") -> the C entry
 
 
 def _prefill_call(kv8, q, k, v, out, block_table, kv_lens, q_lens, causal, return_lse, stream, k_scale,
-                  v_scale, window=0):
+                  v_scale, window=0, sinks=None):
     """The call of both prefill functions after their checks (the twin of
     :func:`_decode_call`, without a workspace): the stream, the optional LSE
     and the C entry of the cache form and q's dtype.  The LSE is allocated
     with empty(): rows past q_lens are not written.  window > 0: the
-    fa_prefill_win_* entries."""
+    fa_prefill_win_* entries; sinks: the fa_prefill_sink_* entries, at any
+    window."""
     import torch
 
-    win = (window,) if window else ()  # checked by the public function
+    variant, win = _entry_variant(window, sinks)  # checked by the public function
     b, hq, sq, d = q.shape
     hkv = k.shape[1]
     paged = block_table is not None
@@ -840,10 +907,10 @@ def _prefill_call(kv8, q, k, v, out, block_table, kv_lens, q_lens, causal, retur
     else:
         cache = (k.shape[2], d)
     lib = _lib or load_library()
-    which = (paged, kv8, q.dtype is torch.bfloat16, bool(win))
+    which = (paged, kv8, q.dtype is torch.bfloat16, variant)
     fn = _PRE_ENTRY.get(which)
     if fn is None:
-        fn = _PRE_ENTRY[which] = getattr(lib, "fa_prefill" + ("_win" if win else "")
+        fn = _PRE_ENTRY[which] = getattr(lib, "fa_prefill" + variant
                                          + ("_paged" if paged else "")
                                          + ("_kv8" if kv8 else "") + ("_bf16" if which[2] else "_f16"))
     tail = ()
@@ -867,7 +934,7 @@ def _prefill_call(kv8, q, k, v, out, block_table, kv_lens, q_lens, causal, retur
 
 def flash_attention_prefill(q, k_cache, v_cache, kv_lens=None, q_lens=None, causal: bool = True,
                             out=None, return_lse: bool = False, stream=None, k_scale=None,
-                            v_scale=None, window: int = 0):
+                            v_scale=None, window: int = 0, sinks=None):
     """Prefill attention over a K/V cache (fa_prefill_f16 / fa_prefill_bf16, or
     fa_prefill_kv8_* over an FP8 cache): a prompt, or a chunk of one behind a
     cached prefix, against the cache :func:`flash_attention_cache_append` wrote
@@ -896,20 +963,33 @@ def flash_attention_prefill(q, k_cache, v_cache, kv_lens=None, q_lens=None, caus
     are the table entries of pages lying wholly below it: those pages may be
     freed or reused.
     pos = kv_lens[b] - n_b + t.
+
+    sinks: None, or attention sinks: a contiguous float32 [Hq] tensor on q's
+    device, one learned logit per query head that joins the softmax
+    denominator and contributes no value (the fa_prefill_sink_* entries, at
+    any window, 0 included, and with causal=False when window=0).  With s_j
+    the row's scaled scores (after 1/sqrt(D) and k_scale) over the keys it
+    sees -- the same keys as without sinks -- den = exp(sinks[h]) + sum_j
+    exp(s_j), out = sum_j exp(s_j) v_j / den and lse = log(den); the sink takes
+    neither 1/sqrt(D) nor k_scale.  A row that sees no key gives zeros and lse
+    = sinks[h]; -inf is "no sink for that head".  The values are read on the
+    device, so a captured graph follows them.  lse includes the sink: a caller
+    merging partial states by their lse (chunks of one cache attended
+    separately) must pass sinks to ONE partial only.
     """
     window = _check_window(window, causal)  # before the tensors: a bad window is named whatever they are
     if out is None:
         import torch
 
         out = torch.empty_like(q)
-    kv8 = _check_decode(q, k_cache, v_cache, kv_lens, out, k_scale, v_scale, q_lens)
+    kv8 = _check_decode(q, k_cache, v_cache, kv_lens, out, k_scale, v_scale, q_lens, sinks)
     return _prefill_call(kv8, q, k_cache, v_cache, out, None, kv_lens, q_lens, causal, return_lse,
-                         stream, k_scale, v_scale, window)
+                         stream, k_scale, v_scale, window, sinks)
 
 
 def flash_attention_prefill_paged(q, k_pages, v_pages, block_table, kv_lens=None, q_lens=None,
                                   causal: bool = True, out=None, return_lse: bool = False, stream=None,
-                                  k_scale=None, v_scale=None, window: int = 0):
+                                  k_scale=None, v_scale=None, window: int = 0, sinks=None):
     """:func:`flash_attention_prefill` over the page pools
     :func:`flash_attention_decode_paged` reads (fa_prefill_paged_f16 / _bf16, or
     fa_prefill_paged_kv8_* over an FP8 pool).
@@ -921,7 +1001,9 @@ def flash_attention_prefill_paged(q, k_pages, v_pages, block_table, kv_lens=None
     :func:`flash_attention_prefill` on the gathered cache bit for bit.  Rows
     t >= n_b of out and lse are not written (unspecified with out=None).
     window: as for that function (fa_prefill_win_paged_*); block-table entries
-    of pages wholly below a query block's window are never read.
+    of pages wholly below a query block's window are never read.  sinks: as
+    for that function (fa_prefill_sink_paged_*): pass them to one partial only
+    when merging by lse.
     """
     window = _check_window(window, causal)  # before the tensors: a bad window is named whatever they are
     if block_table is None:
@@ -930,9 +1012,10 @@ def flash_attention_prefill_paged(q, k_pages, v_pages, block_table, kv_lens=None
         import torch
 
         out = torch.empty_like(q)
-    kv8 = _check_decode_paged(q, k_pages, v_pages, block_table, kv_lens, out, k_scale, v_scale, q_lens)
+    kv8 = _check_decode_paged(q, k_pages, v_pages, block_table, kv_lens, out, k_scale, v_scale, q_lens,
+                              sinks)
     return _prefill_call(kv8, q, k_pages, v_pages, out, block_table, kv_lens, q_lens, causal,
-                         return_lse, stream, k_scale, v_scale, window)
+                         return_lse, stream, k_scale, v_scale, window, sinks)
 
 
 def _check_append(k_new, v_new, kname, k, vname, v, block_table, kv_lens, new_lens, k_scale, v_scale):
@@ -1097,7 +1180,7 @@ def _check_cu_seqlens(cu, name, nseq, ref, where):
 
 
 def _check_packed(x, xname, y, yname, kname, k, vname, v, block_table, cu, cuname, kv_lens, k_scale,
-                  v_scale, need_kv_lens):
+                  v_scale, need_kv_lens, sinks=None):
     """What the four packed wrappers check.  x, y: q and out [T,Hq,D] (prefill)
     or k_new and v_new [T,Hkv,D] (append), contiguous, of one 16-bit dtype and
     shape; the caches (`kname`, `vname`: [B,Hkv,cap,D], or with a block table
@@ -1149,7 +1232,7 @@ def _check_packed(x, xname, y, yname, kname, k, vname, v, block_table, cu, cunam
             "kv_lens is required: the int32 [B] lengths after the append (what decode takes next)")
     _check_cu_seqlens(cu, cuname, nseq, x, False)
     _check_decode_tail(x, kname, k, vname, v, y, k_scale, v_scale, block_table, kv_lens,
-                       qname=xname, oname=yname, batch=nseq)
+                       qname=xname, oname=yname, batch=nseq, sinks=sinks)
     _check_cu_seqlens(cu, cuname, nseq, x, True)
     return kv8, nseq
 
@@ -1186,17 +1269,17 @@ def _packed_call(name, kv8, x, y, extra, nseq, heads, k, v, block_table, kv_lens
 
 
 def _prefill_varlen(q, k, v, block_table, names, cu_seqlens_q, kv_lens, causal, out, return_lse, stream,
-                    k_scale, v_scale, window=0):
+                    k_scale, v_scale, window=0, sinks=None):
     import torch
 
-    win = (window,) if window else ()  # checked by the public function
     if out is None:
         out = torch.empty_like(q)
     kv8, nseq = _check_packed(q, "q", out, "out", names[0], k, names[1], v, block_table, cu_seqlens_q,
-                              "cu_seqlens_q", kv_lens, k_scale, v_scale, False)
+                              "cu_seqlens_q", kv_lens, k_scale, v_scale, False, sinks)
+    variant, win = _entry_variant(window, sinks)  # window: checked by the public function
     total, hq = q.shape[0], q.shape[1]
     lse = torch.empty((hq, total), dtype=torch.float32, device=q.device) if return_lse else None
-    name = ("fa_prefill_varlen" + ("_win" if win else "")
+    name = ("fa_prefill_varlen" + variant
             + ("_paged" if block_table is not None else "") + ("_kv8" if kv8 else "")
             + ("_bf16" if q.dtype is torch.bfloat16 else "_f16"))
     _packed_call(name, kv8, q, (), (out.data_ptr(), lse.data_ptr() if return_lse else None), nseq,
@@ -1207,7 +1290,7 @@ def _prefill_varlen(q, k, v, block_table, names, cu_seqlens_q, kv_lens, causal, 
 
 def flash_attention_prefill_varlen(q, k_cache, v_cache, cu_seqlens_q, kv_lens=None, causal: bool = True,
                                    out=None, return_lse: bool = False, stream=None, k_scale=None,
-                                   v_scale=None, window: int = 0):
+                                   v_scale=None, window: int = 0, sinks=None):
     """:func:`flash_attention_prefill` for a packed ragged batch
     (fa_prefill_varlen_f16 / _bf16, or fa_prefill_varlen_kv8_* over an FP8
     cache): what a serving stack holds after its QKV projection, taken as it
@@ -1227,29 +1310,34 @@ def flash_attention_prefill_varlen(q, k_cache, v_cache, cu_seqlens_q, kv_lens=No
     out [T, Hq, D], or (out, lse) with lse fp32 [Hq, T] when return_lse.
     Everything is read on the device: no sync, no workspace, graph-capturable.
     window: the sliding window of :func:`flash_attention_prefill`
-    (fa_prefill_varlen_win_*), with the same bit-for-bit equality.
+    (fa_prefill_varlen_win_*), with the same bit-for-bit equality.  sinks: the
+    attention sinks of :func:`flash_attention_prefill` (fa_prefill_varlen_sink_*),
+    float32 [Hq], with the same equality; pass them to one partial only when
+    merging by lse.
     """
     window = _check_window(window, causal)  # before the tensors: a bad window is named whatever they are
     return _prefill_varlen(q, k_cache, v_cache, None, ("k_cache", "v_cache"), cu_seqlens_q, kv_lens,
-                           causal, out, return_lse, stream, k_scale, v_scale, window)
+                           causal, out, return_lse, stream, k_scale, v_scale, window, sinks)
 
 
 def flash_attention_prefill_varlen_paged(q, k_pages, v_pages, block_table, cu_seqlens_q, kv_lens=None,
                                          causal: bool = True, out=None, return_lse: bool = False,
-                                         stream=None, k_scale=None, v_scale=None, window: int = 0):
+                                         stream=None, k_scale=None, v_scale=None, window: int = 0, sinks=None):
     """:func:`flash_attention_prefill_varlen` over the page pools of
     :func:`flash_attention_prefill_paged` (fa_prefill_varlen_paged_f16 / _bf16,
     or fa_prefill_varlen_paged_kv8_*).  B is the block table's row count; the
     result equals the contiguous function's on the gathered cache bit for bit.
     window: the sliding window of :func:`flash_attention_prefill`
     (fa_prefill_varlen_win_paged_*); block-table entries of pages wholly below
-    a query block's window are never read.
+    a query block's window are never read.  sinks: as for that function
+    (fa_prefill_varlen_sink_paged_*): pass them to one partial only when merging
+    by lse.
     """
     window = _check_window(window, causal)  # before the tensors: a bad window is named whatever they are
     if block_table is None:
         raise FlashAttentionError(FA_ERR_NULL_POINTER, "block_table is required")
     return _prefill_varlen(q, k_pages, v_pages, block_table, ("k_pages", "v_pages"), cu_seqlens_q,
-                           kv_lens, causal, out, return_lse, stream, k_scale, v_scale, window)
+                           kv_lens, causal, out, return_lse, stream, k_scale, v_scale, window, sinks)
 
 
 def _append_varlen(k_new, v_new, k, v, block_table, names, cu_seqlens, kv_lens, k_scale, v_scale, stream):

@@ -457,8 +457,8 @@ cache_append_varlen_paged = torch.ops.fa_mi355x.cache_append_varlen_paged
 _REQUIRED = object()
 
 
-def _window_overload(name, args, wrapper, fake):
-    """Registers fa_mi355x::<name>.window.  args: the overload's arguments in
+def _window_overload(name, args, wrapper, fake, overload="window"):
+    """Registers fa_mi355x::<name>.window (or .<overload>).  args: the overload's arguments in
     order as (schema type, name, default) -- _REQUIRED for none -- which are
     also `wrapper`'s keyword names (the Python function the default overload
     calls); fake: the default overload's fake implementation.  Tensors are made
@@ -487,16 +487,19 @@ def _window_overload(name, args, wrapper, fake):
     def fake_impl(*a, **kw):
         vals = bind(a, kw)
         torch._check(vals.pop("window") >= 0, lambda: "expected window >= 0")
+        sinks = vals.pop("sinks", None)
+        torch._check(sinks is None or sinks.dim() == 1, lambda: "expected a [Hq] sinks")
         return fake(**vals)
 
     def lit(d):
         return "" if d is _REQUIRED else "=" + str(d)
 
-    _LIB.define("%s.window(%s) -> Tensor" % (name, ", ".join(f"{ty} {n}{lit(d)}" for ty, n, d in args)))
-    _LIB.impl(name + ".window", gpu, "CUDA")
-    _LIB.impl(name + ".window", torch.library.fallthrough_kernel, "Autograd")
-    _LIB.impl(name + ".window", cpu, "CPU")
-    torch.library.register_fake("fa_mi355x::" + name + ".window", fake_impl, lib=_LIB)
+    full = name + "." + overload
+    _LIB.define("%s(%s) -> Tensor" % (full, ", ".join(f"{ty} {n}{lit(d)}" for ty, n, d in args)))
+    _LIB.impl(full, gpu, "CUDA")
+    _LIB.impl(full, torch.library.fallthrough_kernel, "Autograd")
+    _LIB.impl(full, cpu, "CPU")
+    torch.library.register_fake("fa_mi355x::" + full, fake_impl, lib=_LIB)
 
 
 def _T(n):
@@ -521,3 +524,25 @@ _window_overload("prefill_varlen", [_T("q"), _T("k_cache"), _T("v_cache"), _T("c
 _window_overload("prefill_varlen_paged", [_T("q"), _T("k_pages"), _T("v_pages"), _T("block_table"),
                                           _T("cu_seqlens_q"), _opt("kv_lens")] + _TAIL,
                  flash_attention_prefill_varlen_paged, _prefill_varlen_paged_fake)
+
+# Attention sinks: a `.sinks` overload of the same six ops, the `.window`
+# overload's arguments and then `Tensor? sinks=None` (float32 [Hq]: one logit
+# per query head that joins the softmax denominator and contributes no value;
+# the Python functions' `sinks`).  Registered after `.window`, so a call
+# that names or passes `sinks` resolves to it and every call an earlier overload
+# accepts still resolves there.
+_SINKS = _TAIL + [_opt("sinks")]
+_window_overload("decode", [_T("q"), _T("k_cache"), _T("v_cache"), _opt("kv_lens")] + _SINKS,
+                 flash_attention_decode, _decode_fake, "sinks")
+_window_overload("decode_paged", [_T("q"), _T("k_pages"), _T("v_pages"), _T("block_table"), _opt("kv_lens")]
+                 + _SINKS, flash_attention_decode_paged, _decode_paged_fake, "sinks")
+_window_overload("prefill", [_T("q"), _T("k_cache"), _T("v_cache"), _opt("kv_lens"), _opt("q_lens")] + _SINKS,
+                 flash_attention_prefill, _prefill_fake, "sinks")
+_window_overload("prefill_paged", [_T("q"), _T("k_pages"), _T("v_pages"), _T("block_table"), _opt("kv_lens"),
+                                   _opt("q_lens")] + _SINKS, flash_attention_prefill_paged, _prefill_paged_fake,
+                 "sinks")
+_window_overload("prefill_varlen", [_T("q"), _T("k_cache"), _T("v_cache"), _T("cu_seqlens_q"), _opt("kv_lens")]
+                 + _SINKS, flash_attention_prefill_varlen, _prefill_varlen_fake, "sinks")
+_window_overload("prefill_varlen_paged", [_T("q"), _T("k_pages"), _T("v_pages"), _T("block_table"),
+                                          _T("cu_seqlens_q"), _opt("kv_lens")] + _SINKS,
+                 flash_attention_prefill_varlen_paged, _prefill_varlen_paged_fake, "sinks")

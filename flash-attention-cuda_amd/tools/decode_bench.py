@@ -44,6 +44,15 @@ The figure of record is win_over_plain beside plain_aa and tile_ratio, the
 share of 64-key tiles the windowed launch iterates, counted from the shape.
 
     python3 tools/decode_bench.py --window 4096 [--out profiles/decode_window_bench.jsonl]
+
+--sinks (composable with --window) times the attention-sink entries
+fa_decode_sink_* (sinks drawn from N(0, 2) per head) against the entries a call
+without sinks takes at the same window -- fa_decode_* at 0, where the `_sink`
+entry runs the windowed kernel at W = capacity, fa_decode_win_* otherwise -- on
+the --window rows and in the same way (run_sinks): base / sinks / base / paged
+sinks, sink_over_base beside base_aa.
+
+    python3 tools/decode_bench.py --sinks [--window 4096] [--out profiles/decode_sinks_bench.jsonl]
 """
 import argparse
 import json
@@ -581,6 +590,111 @@ def run_window(row, window, cus, page_size=256, rounds=9):
                 plain_share_of_copy_rate=round(kv_bytes / (med[0] * 1e-6) / COPY_RATE, 4))
 
 
+def run_sinks(row, window, cus, page_size=256, rounds=9):
+    """The `_sink` entry at `window` (0 included: the windowed kernel at W =
+    capacity) against the entry a call without sinks takes at the same window
+    (fa_decode_f16 at 0, fa_decode_win_f16 otherwise): us per call from
+    alternately replayed HIP graphs (base, sinks, base again, paged sinks)."""
+    lib = fa_mi355x.load_library()
+    dt = torch.float16
+    b, hq, hkv, sq, d, cap = row["b"], row["hq"], row["hkv"], row["sq"], row["d"], row["n"]
+    mpp = cap // page_size
+    npages = b * mpp
+    kv_bytes = 2 * b * hkv * cap * d * 2
+    copies = max(1, min(32, -(-(512 << 20) // kv_bytes)))
+    gen = torch.Generator(device="cuda").manual_seed(1)
+
+    def rnd(*shape):
+        return (torch.rand(shape, generator=gen, device="cuda", dtype=torch.float32) * 2 - 1).to(dt)
+
+    ks, vs, kps, vps, tabs = [], [], [], [], []
+    for _ in range(copies):
+        k, v = rnd(b, hkv, cap, d), rnd(b, hkv, cap, d)
+        perm = torch.randperm(npages, generator=gen, device="cuda")
+        ks.append(k), vs.append(v)
+        for x, dst in ((k, kps), (v, vps)):
+            out = torch.empty((npages, hkv, page_size, d), dtype=dt, device="cuda")
+            out[perm] = x.view(b, hkv, mpp, page_size, d).permute(0, 2, 1, 3, 4).reshape(
+                npages, hkv, page_size, d)
+            dst.append(out)
+        tabs.append(perm.view(b, mpp).to(torch.int32).contiguous())
+    q = rnd(b, hq, sq, d)
+    sinks = torch.randn(hq, generator=gen, device="cuda", dtype=torch.float32) * 2.0 ** 0.5
+    wcap = fa_mi355x.decode_window_capacity(cap, sq, window)
+    plan = fa_mi355x.decode_num_splits(b, hq, hkv, sq, wcap, d)
+    need = lib.fa_decode_ws_bytes(b, hq, hkv, sq, wcap, d, 0)
+    ws = torch.zeros(max(need, 1), dtype=torch.uint8, device="cuda")
+    wsp = ws.data_ptr() if need else None
+    outs = [torch.empty_like(q) for _ in range(3)]
+    iters = 20 if kv_bytes < (1 << 30) else 5
+
+    def base(st):
+        for i in range(iters):
+            c = i % copies
+            if window:
+                rc = lib.fa_decode_win_f16(q.data_ptr(), ks[c].data_ptr(), vs[c].data_ptr(), outs[0].data_ptr(),
+                                           None, b, hq, hkv, sq, cap, d, None, 1, window, 0, wsp, need, st)
+            else:
+                rc = lib.fa_decode_f16(q.data_ptr(), ks[c].data_ptr(), vs[c].data_ptr(), outs[0].data_ptr(),
+                                       None, b, hq, hkv, sq, cap, d, None, 1, 0, wsp, need, st)
+            assert rc == 0, rc
+
+    def sink(st):
+        for i in range(iters):
+            c = i % copies
+            rc = lib.fa_decode_sink_f16(q.data_ptr(), ks[c].data_ptr(), vs[c].data_ptr(), outs[1].data_ptr(),
+                                        None, b, hq, hkv, sq, cap, d, None, 1, window, sinks.data_ptr(), 0, wsp,
+                                        need, st)
+            assert rc == 0, rc
+
+    def sink_paged(st):
+        for i in range(iters):
+            c = i % copies
+            rc = lib.fa_decode_sink_paged_f16(q.data_ptr(), kps[c].data_ptr(), vps[c].data_ptr(),
+                                              outs[2].data_ptr(), None, b, hq, hkv, sq, d, npages, page_size,
+                                              tabs[c].data_ptr(), mpp, None, 1, window, sinks.data_ptr(), 0, wsp,
+                                              need, st)
+            assert rc == 0, rc
+
+    fns = (base, sink, sink_paged)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):  # first-launch set-up outside the captures
+        for fn in fns:
+            fn(side.cuda_stream)
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    same = bool(torch.equal(outs[1], outs[2]))
+    graphs = []
+    for fn in fns:
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            fn(torch.cuda.current_stream().cuda_stream)
+        g.replay()
+        graphs.append(g)
+    torch.cuda.synchronize()
+    legs = (0, 1, 0, 2)
+    ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+           for _ in range(rounds)] for _ in legs]
+    for r in range(rounds):
+        for j, gi in enumerate(legs):
+            ev[j][r][0].record()
+            graphs[gi].replay()
+            ev[j][r][1].record()
+    torch.cuda.synchronize()
+    ts = [sorted(a.elapsed_time(c) * 1e3 / iters for a, c in e) for e in ev]
+    med = [t[len(t) // 2] for t in ts]
+    return dict(name=row["name"].replace("window", "sinks"), window=window, sinks=True, batch=b, heads_q=hq,
+                heads_kv=hkv, seqlen_q=sq, head_dim=d, dtype="float16", kv_len=cap, page_size=page_size,
+                copies=copies, num_splits=plan, rounds=rounds, iters=iters, paged_bit_identical=same,
+                base_entry="win" if window else "plain", base_us=round(med[0], 2), sink_us=round(med[1], 2),
+                base2_us=round(med[2], 2), sink_paged_us=round(med[3], 2),
+                base_min_us=round(min(ts[0][0], ts[2][0]), 2), base_max_us=round(max(ts[0][-1], ts[2][-1]), 2),
+                sink_min_us=round(ts[1][0], 2), sink_max_us=round(ts[1][-1], 2),
+                sink_over_base=round(med[1] / med[0], 4), sink_paged_over_base=round(med[3] / med[0], 4),
+                base_aa=round(med[2] / med[0], 4))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="default profiles/decode_bench.jsonl "
@@ -593,11 +707,15 @@ def main():
                     help="the FP8-cache entries against the 16-bit ones on the same shapes")
     ap.add_argument("--window", type=int, default=0,
                     help="the sliding-window entries at this W against the plain ones")
+    ap.add_argument("--sinks", action="store_true",
+                    help="the attention-sink entries at --window (0 included) against the entries without "
+                         "sinks at the same window")
     ap.add_argument("--placement", choices=("random", "identity"), default="random",
                     help="--paged: pool pages under a random permutation (default) or in logical order")
     args = ap.parse_args()
     if args.out is None:
         args.out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "profiles",
+                                "decode_sinks_bench.jsonl" if args.sinks else
                                 "decode_window_bench.jsonl" if args.window else
                                 "decode_kv8_bench.jsonl" if args.kv8 else
                                 "decode_paged_bench.jsonl" if args.paged else "decode_bench.jsonl")
@@ -605,7 +723,9 @@ def main():
         sys.exit("decode_bench.py needs a GPU")
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    if args.window:
+    if args.sinks:
+        jobs = [(run_sinks, (row, args.window, cus)) for row in window_shapes()]
+    elif args.window:
         jobs = [(run_window, (row, args.window, cus)) for row in window_shapes()]
     elif args.kv8:
         jobs = [(run_kv8, (row, cus)) for row in kv8_shapes()]

@@ -44,6 +44,14 @@ win_over_plain beside plain_aa and tile_ratio, the share of (query block, key
 tile) pairs the windowed launch iterates, counted from the shape.
 
     timeout 300 python3 tools/prefill_bench.py --shape s32k --window 4096 [--out profiles/prefill_window_bench.jsonl]
+
+--sinks (with --shape, composable with --window): the attention-sink entry
+(sinks drawn from N(0, 2) per head) against the entry a call without sinks takes
+at the same --window (0: the plain entry, against which the `_sink` entry runs
+the windowed kernel at W = capacity), base / sinks / base: sink_over_base beside
+base_aa.
+
+    timeout 300 python3 tools/prefill_bench.py --shape s32k --window 4096 --sinks [--out profiles/prefill_sinks_bench.jsonl]
 """
 import argparse
 import json
@@ -225,7 +233,8 @@ def window_tiles(sq, prefix, window, bm=128, bn=64):
     return plain, win
 
 
-def run_window(shape, dt, form, window, rounds, iters):
+def window_inputs(shape, dt, form):
+    """(q, k, v, table, kv_lens, q_lens, scales) of the --window / --sinks rows."""
     b, hq, hkv, sq, prefix = SHAPES[shape]
     d = 128
     skv = prefix + sq
@@ -259,17 +268,28 @@ def run_window(shape, dt, form, window, rounds, iters):
 
         k, v = pool(k), pool(v)
         table = perm.view(b, mpp).to(torch.int32).contiguous()
+    return q, k, v, table, kv_lens, q_lens, scales
+
+
+def window_arm(inputs, w, o, sinks=None):
+    q, k, v, table, kv_lens, q_lens, scales = inputs
+
+    def fn():
+        if table is not None:
+            return fa_mi355x.flash_attention_prefill_paged(q, k, v, table, kv_lens, q_lens, out=o, window=w,
+                                                           sinks=sinks, **scales)
+        return fa_mi355x.flash_attention_prefill(q, k, v, kv_lens, q_lens, out=o, window=w, sinks=sinks,
+                                                 **scales)
+    return fn
+
+
+def run_window(shape, dt, form, window, rounds, iters):
+    b, hq, hkv, sq, prefix = SHAPES[shape]
+    d, paged = 128, form.startswith("paged")
+    inputs = window_inputs(shape, dt, form)
+    q = inputs[0]
     outs = [torch.empty_like(q), torch.empty_like(q)]
-
-    def arm(w, o):
-        def fn():
-            if paged:
-                return fa_mi355x.flash_attention_prefill_paged(q, k, v, table, kv_lens, q_lens, out=o,
-                                                               window=w, **scales)
-            return fa_mi355x.flash_attention_prefill(q, k, v, kv_lens, q_lens, out=o, window=w, **scales)
-        return fn
-
-    plain, win = arm(0, outs[0]), arm(window, outs[1])
+    plain, win = window_arm(inputs, 0, outs[0]), window_arm(inputs, window, outs[1])
     ts = time_arms([plain, win, plain], iters, rounds)
     tp, tw = window_tiles(sq, prefix, window)
     rec = dict(shape=shape, form=form, window=window, dtype=str(dt).split(".")[-1], batch=b, heads_q=hq,
@@ -285,6 +305,34 @@ def run_window(shape, dt, form, window, rounds, iters):
     # rows whose window covers every key they see must agree exactly
     rec["head_rows_bit_identical"] = bool(torch.equal(outs[0][:, :, :min(sq, window)],
                                                       outs[1][:, :, :min(sq, window)]))
+    return rec
+
+
+def run_sinks(shape, dt, form, window, rounds, iters):
+    """The `_sink` entry at `window` (0 included: the Windowed kernel at W =
+    capacity) against the entry a call without sinks takes at the same window
+    (the plain one at 0), base / sinks / base."""
+    b, hq, hkv, sq, prefix = SHAPES[shape]
+    d, paged = 128, form.startswith("paged")
+    inputs = window_inputs(shape, dt, form)
+    q = inputs[0]
+    outs = [torch.empty_like(q), torch.empty_like(q)]
+    gen = torch.Generator(device="cuda").manual_seed(2)
+    sinks = torch.randn(hq, generator=gen, device="cuda", dtype=torch.float32) * 2.0 ** 0.5
+    base, snk = window_arm(inputs, window, outs[0]), window_arm(inputs, window, outs[1], sinks)
+    ts = time_arms([base, snk, base], iters, rounds)
+    rec = dict(shape=shape, form=form, window=window, sinks=True, dtype=str(dt).split(".")[-1], batch=b,
+               heads_q=hq, heads_kv=hkv, seqlen_q=sq, prefix=prefix, head_dim=d,
+               page_size=PAGE if paged else None, rounds=rounds, iters=iters,
+               base_entry="win" if window else "plain")
+    for name, (med, lo, hi) in zip(("base", "sink", "base2"), ts):
+        rec[name + "_ms"] = round(med, 4)
+        rec[name + "_min_ms"] = round(lo, 4)
+        rec[name + "_max_ms"] = round(hi, 4)
+    rec["sink_over_base"] = round(ts[1][0] / ts[0][0], 4)
+    rec["base_aa"] = round(ts[2][0] / ts[0][0], 4)
+    # a sink only ever shrinks a row: |O| <= |O without|, and somewhere strictly
+    rec["shrinks"] = bool((outs[1].float().abs() <= outs[0].float().abs() + 1e-3).all())
     return rec
 
 
@@ -377,6 +425,9 @@ def main():
     ap.add_argument("--forms", default=",".join(FORMS))
     ap.add_argument("--window", type=int, default=0,
                     help="with --shape: the sliding-window entry at this W against the plain one")
+    ap.add_argument("--sinks", action="store_true",
+                    help="with --shape: the attention-sink entry at --window (0 included) against the entry "
+                         "without sinks at the same window")
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=2)
     ap.add_argument("--out", default=None, help="appended to; default profiles/prefill_bench.jsonl")
@@ -388,6 +439,7 @@ def main():
     if args.out is None:
         args.out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "profiles",
                                 "prefill_varlen_bench.jsonl" if args.varlen else
+                                "prefill_sinks_bench.jsonl" if args.sinks else
                                 "prefill_window_bench.jsonl" if args.window else "prefill_bench.jsonl")
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     dt = torch.bfloat16 if args.dtype == "bf16" else torch.float16
@@ -397,6 +449,8 @@ def main():
             assert form in FORMS, form
             if args.varlen:
                 rec = run_varlen(args.varlen, dt, form, args.rounds, args.iters)
+            elif args.sinks:
+                rec = run_sinks(args.shape, dt, form, args.window, args.rounds, args.iters)
             elif args.window:
                 rec = run_window(args.shape, dt, form, args.window, args.rounds, args.iters)
             else:

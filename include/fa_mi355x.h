@@ -753,6 +753,166 @@ int fa_prefill_varlen_win_paged_kv8_bf16(const void* q, const void* k_pages, con
                                          int window, void* hip_stream, const float* k_scale,
                                          const float* v_scale);
 
+/* Attention sinks: the twenty-four `_win` entries above with
+ * `const float* sinks` inserted directly after `window` (`_sink` in `_win`'s
+ * place).  sinks is a device array of heads_q floats, read on the device (a
+ * captured graph follows its values), or NULL for no sinks: one learned logit
+ * per query head that joins the softmax denominator and contributes no value.
+ * With s_j the scaled scores (natural-log units, after 1/sqrt(head_dim) and
+ * k_scale) of the keys a row of head h sees -- exactly the `_win` twin's keys:
+ * causal, kv_lens, q_lens and window unchanged --
+ *   den = exp(sinks[h]) + sum_j exp(s_j)
+ *   O   = sum_j exp(s_j) v_j / den          (times v_scale for an FP8 cache)
+ *   LSE = log(den)                          (the sink is included)
+ * The sink is not multiplied by 1/sqrt(head_dim) or by k_scale.  A row that
+ * sees no key gives O = 0 and LSE = sinks[h] on every path, kv_capacity == 0
+ * included.  sinks[h] = -inf is "no sink for that head"; NaN is unspecified.
+ * With sinks == NULL, or every sink -inf, O and LSE are the `_win` twin's bit
+ * for bit.  window keeps the twin's meaning and statuses (0: no window; the
+ * kernels then run as W = capacity, causal or not), and every other argument
+ * error arrives in the twin's place and order; there are no new status codes,
+ * no sync, and no workspace beyond the twin's: decode's pieces, workspace,
+ * fa_decode_num_splits() and fa_decode_ws_bytes() are unchanged, and the sink
+ * enters once, in the final normalisation.  Rows past q_lens are not written.
+ * LSE includes the sink, so a caller that merges partial states by their LSE
+ * (chunks of one cache attended separately) must pass sinks to ONE partial
+ * only: each partial given the sink would count it again. */
+int fa_decode_sink_f16(const void* q, const void* k, const void* v, void* o, float* lse, int batch,
+                       int heads_q, int heads_kv, int seqlen_q, int kv_capacity, int head_dim,
+                       const int* kv_lens, int causal, int window, const float* sinks,
+                       int num_splits, void* workspace, unsigned long long ws_bytes,
+                       void* hip_stream);
+int fa_decode_sink_bf16(const void* q, const void* k, const void* v, void* o, float* lse, int batch,
+                        int heads_q, int heads_kv, int seqlen_q, int kv_capacity, int head_dim,
+                        const int* kv_lens, int causal, int window, const float* sinks,
+                        int num_splits, void* workspace, unsigned long long ws_bytes,
+                        void* hip_stream);
+int fa_decode_sink_paged_f16(const void* q, const void* k_pages, const void* v_pages, void* o,
+                             float* lse, int batch, int heads_q, int heads_kv, int seqlen_q,
+                             int head_dim, int num_pages, int page_size, const int* block_table,
+                             int max_pages_per_seq, const int* kv_lens, int causal, int window,
+                             const float* sinks, int num_splits, void* workspace,
+                             unsigned long long ws_bytes, void* hip_stream);
+int fa_decode_sink_paged_bf16(const void* q, const void* k_pages, const void* v_pages, void* o,
+                              float* lse, int batch, int heads_q, int heads_kv, int seqlen_q,
+                              int head_dim, int num_pages, int page_size, const int* block_table,
+                              int max_pages_per_seq, const int* kv_lens, int causal, int window,
+                              const float* sinks, int num_splits, void* workspace,
+                              unsigned long long ws_bytes, void* hip_stream);
+int fa_decode_sink_kv8_f16(const void* q, const void* k, const void* v, void* o, float* lse,
+                           int batch, int heads_q, int heads_kv, int seqlen_q, int kv_capacity,
+                           int head_dim, const int* kv_lens, int causal, int window,
+                           const float* sinks, int num_splits, void* workspace,
+                           unsigned long long ws_bytes, void* hip_stream, const float* k_scale,
+                           const float* v_scale);
+int fa_decode_sink_kv8_bf16(const void* q, const void* k, const void* v, void* o, float* lse,
+                            int batch, int heads_q, int heads_kv, int seqlen_q, int kv_capacity,
+                            int head_dim, const int* kv_lens, int causal, int window,
+                            const float* sinks, int num_splits, void* workspace,
+                            unsigned long long ws_bytes, void* hip_stream, const float* k_scale,
+                            const float* v_scale);
+int fa_decode_sink_paged_kv8_f16(const void* q, const void* k_pages, const void* v_pages, void* o,
+                                 float* lse, int batch, int heads_q, int heads_kv, int seqlen_q,
+                                 int head_dim, int num_pages, int page_size, const int* block_table,
+                                 int max_pages_per_seq, const int* kv_lens, int causal, int window,
+                                 const float* sinks, int num_splits, void* workspace,
+                                 unsigned long long ws_bytes, void* hip_stream,
+                                 const float* k_scale, const float* v_scale);
+int fa_decode_sink_paged_kv8_bf16(const void* q, const void* k_pages, const void* v_pages, void* o,
+                                  float* lse, int batch, int heads_q, int heads_kv, int seqlen_q,
+                                  int head_dim, int num_pages, int page_size,
+                                  const int* block_table, int max_pages_per_seq, const int* kv_lens,
+                                  int causal, int window, const float* sinks, int num_splits,
+                                  void* workspace, unsigned long long ws_bytes, void* hip_stream,
+                                  const float* k_scale, const float* v_scale);
+int fa_prefill_sink_f16(const void* q, const void* k, const void* v, void* o, float* lse, int batch,
+                        int heads_q, int heads_kv, int seqlen_q, int kv_capacity, int head_dim,
+                        const int* kv_lens, const int* q_lens, int causal, int window,
+                        const float* sinks, void* hip_stream);
+int fa_prefill_sink_bf16(const void* q, const void* k, const void* v, void* o, float* lse,
+                         int batch, int heads_q, int heads_kv, int seqlen_q, int kv_capacity,
+                         int head_dim, const int* kv_lens, const int* q_lens, int causal,
+                         int window, const float* sinks, void* hip_stream);
+int fa_prefill_sink_paged_f16(const void* q, const void* k_pages, const void* v_pages, void* o,
+                              float* lse, int batch, int heads_q, int heads_kv, int seqlen_q,
+                              int head_dim, int num_pages, int page_size, const int* block_table,
+                              int max_pages_per_seq, const int* kv_lens, const int* q_lens,
+                              int causal, int window, const float* sinks, void* hip_stream);
+int fa_prefill_sink_paged_bf16(const void* q, const void* k_pages, const void* v_pages, void* o,
+                               float* lse, int batch, int heads_q, int heads_kv, int seqlen_q,
+                               int head_dim, int num_pages, int page_size, const int* block_table,
+                               int max_pages_per_seq, const int* kv_lens, const int* q_lens,
+                               int causal, int window, const float* sinks, void* hip_stream);
+int fa_prefill_sink_kv8_f16(const void* q, const void* k, const void* v, void* o, float* lse,
+                            int batch, int heads_q, int heads_kv, int seqlen_q, int kv_capacity,
+                            int head_dim, const int* kv_lens, const int* q_lens, int causal,
+                            int window, const float* sinks, void* hip_stream, const float* k_scale,
+                            const float* v_scale);
+int fa_prefill_sink_kv8_bf16(const void* q, const void* k, const void* v, void* o, float* lse,
+                             int batch, int heads_q, int heads_kv, int seqlen_q, int kv_capacity,
+                             int head_dim, const int* kv_lens, const int* q_lens, int causal,
+                             int window, const float* sinks, void* hip_stream, const float* k_scale,
+                             const float* v_scale);
+int fa_prefill_sink_paged_kv8_f16(const void* q, const void* k_pages, const void* v_pages, void* o,
+                                  float* lse, int batch, int heads_q, int heads_kv, int seqlen_q,
+                                  int head_dim, int num_pages, int page_size,
+                                  const int* block_table, int max_pages_per_seq, const int* kv_lens,
+                                  const int* q_lens, int causal, int window, const float* sinks,
+                                  void* hip_stream, const float* k_scale, const float* v_scale);
+int fa_prefill_sink_paged_kv8_bf16(const void* q, const void* k_pages, const void* v_pages, void* o,
+                                   float* lse, int batch, int heads_q, int heads_kv, int seqlen_q,
+                                   int head_dim, int num_pages, int page_size,
+                                   const int* block_table, int max_pages_per_seq,
+                                   const int* kv_lens, const int* q_lens, int causal, int window,
+                                   const float* sinks, void* hip_stream, const float* k_scale,
+                                   const float* v_scale);
+int fa_prefill_varlen_sink_f16(const void* q, const void* k, const void* v, void* o, float* lse,
+                               int batch, int heads_q, int heads_kv, int total_q, int kv_capacity,
+                               int head_dim, const int* kv_lens, const int* cu_seqlens_q,
+                               int causal, int window, const float* sinks, void* hip_stream);
+int fa_prefill_varlen_sink_bf16(const void* q, const void* k, const void* v, void* o, float* lse,
+                                int batch, int heads_q, int heads_kv, int total_q, int kv_capacity,
+                                int head_dim, const int* kv_lens, const int* cu_seqlens_q,
+                                int causal, int window, const float* sinks, void* hip_stream);
+int fa_prefill_varlen_sink_paged_f16(const void* q, const void* k_pages, const void* v_pages,
+                                     void* o, float* lse, int batch, int heads_q, int heads_kv,
+                                     int total_q, int head_dim, int num_pages, int page_size,
+                                     const int* block_table, int max_pages_per_seq,
+                                     const int* kv_lens, const int* cu_seqlens_q, int causal,
+                                     int window, const float* sinks, void* hip_stream);
+int fa_prefill_varlen_sink_paged_bf16(const void* q, const void* k_pages, const void* v_pages,
+                                      void* o, float* lse, int batch, int heads_q, int heads_kv,
+                                      int total_q, int head_dim, int num_pages, int page_size,
+                                      const int* block_table, int max_pages_per_seq,
+                                      const int* kv_lens, const int* cu_seqlens_q, int causal,
+                                      int window, const float* sinks, void* hip_stream);
+int fa_prefill_varlen_sink_kv8_f16(const void* q, const void* k, const void* v, void* o, float* lse,
+                                   int batch, int heads_q, int heads_kv, int total_q,
+                                   int kv_capacity, int head_dim, const int* kv_lens,
+                                   const int* cu_seqlens_q, int causal, int window,
+                                   const float* sinks, void* hip_stream, const float* k_scale,
+                                   const float* v_scale);
+int fa_prefill_varlen_sink_kv8_bf16(const void* q, const void* k, const void* v, void* o,
+                                    float* lse, int batch, int heads_q, int heads_kv, int total_q,
+                                    int kv_capacity, int head_dim, const int* kv_lens,
+                                    const int* cu_seqlens_q, int causal, int window,
+                                    const float* sinks, void* hip_stream, const float* k_scale,
+                                    const float* v_scale);
+int fa_prefill_varlen_sink_paged_kv8_f16(const void* q, const void* k_pages, const void* v_pages,
+                                         void* o, float* lse, int batch, int heads_q, int heads_kv,
+                                         int total_q, int head_dim, int num_pages, int page_size,
+                                         const int* block_table, int max_pages_per_seq,
+                                         const int* kv_lens, const int* cu_seqlens_q, int causal,
+                                         int window, const float* sinks, void* hip_stream,
+                                         const float* k_scale, const float* v_scale);
+int fa_prefill_varlen_sink_paged_kv8_bf16(const void* q, const void* k_pages, const void* v_pages,
+                                          void* o, float* lse, int batch, int heads_q, int heads_kv,
+                                          int total_q, int head_dim, int num_pages, int page_size,
+                                          const int* block_table, int max_pages_per_seq,
+                                          const int* kv_lens, const int* cu_seqlens_q, int causal,
+                                          int window, const float* sinks, void* hip_stream,
+                                          const float* k_scale, const float* v_scale);
+
 /* The dispatcher's decision (ref tier table :620-661): config id used by
  * fa_fwd_f16 for this shape.  The _ws entries may run the causal split tier
  * instead: check fa_fwd_split_pieces() first (> 0: the split tier runs with
