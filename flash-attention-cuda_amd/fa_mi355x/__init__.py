@@ -134,6 +134,22 @@ EXPORTED_SYMBOLS = (
     "fa_prefill_varlen_sink_kv8_bf16",
     "fa_prefill_varlen_sink_paged_kv8_f16",
     "fa_prefill_varlen_sink_paged_kv8_bf16",
+    "fa_rope_append_f16",
+    "fa_rope_append_bf16",
+    "fa_rope_append_paged_f16",
+    "fa_rope_append_paged_bf16",
+    "fa_rope_append_kv8_f16",
+    "fa_rope_append_kv8_bf16",
+    "fa_rope_append_paged_kv8_f16",
+    "fa_rope_append_paged_kv8_bf16",
+    "fa_rope_append_varlen_f16",
+    "fa_rope_append_varlen_bf16",
+    "fa_rope_append_varlen_paged_f16",
+    "fa_rope_append_varlen_paged_bf16",
+    "fa_rope_append_varlen_kv8_f16",
+    "fa_rope_append_varlen_kv8_bf16",
+    "fa_rope_append_varlen_paged_kv8_f16",
+    "fa_rope_append_varlen_paged_kv8_bf16",
     "fa_select_config",
     "fa_num_configs",
     "fa_config_info",
@@ -263,6 +279,15 @@ def load_library() -> ctypes.CDLL:
     for name in EXPORTED_SYMBOLS:
         if name.startswith("fa_cache_append"):
             getattr(lib, name).restype = i
+    # the fused RoPE twins: the append's list (FP8: with the scales), then
+    # q, q_out, heads_q, cos, sin, rope_len, rotary_dim, interleaved
+    for fam in ("", "_varlen"):
+        for form, base in (("", "_16"), ("_paged", "_paged_16"), ("_kv8", "_kv8_f16"),
+                           ("_paged_kv8", "_paged_kv8_f16")):
+            for ty in ("_f16", "_bf16"):
+                fn = getattr(lib, "fa_rope_append" + fam + form + ty)
+                fn.argtypes = getattr(lib, "fa_cache_append" + base).argtypes + [vp, vp, i, vp, vp, i, i, i]
+                fn.restype = i
     for fn in (lib.fa_prefill_f16, lib.fa_prefill_bf16):
         fn.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, vp, vp, i, vp]
     for fn in (lib.fa_prefill_paged_f16, lib.fa_prefill_paged_bf16):
@@ -1381,6 +1406,216 @@ def flash_attention_cache_append_varlen_paged(k_new, v_new, k_pages, v_pages, bl
         raise FlashAttentionError(FA_ERR_NULL_POINTER, "block_table is required")
     _append_varlen(k_new, v_new, k_pages, v_pages, block_table, ("k_pages", "v_pages"), cu_seqlens,
                    kv_lens, k_scale, v_scale, stream)
+
+
+def _check_rope(x, xname, rank, q, q_out, cos, sin, where):
+    """What the four rope_append wrappers check beyond the append's own checks.
+    `where` false (before the append's checks, so before any device is looked
+    at): cos and sin are contiguous float32 tensors of one shape [rope_len,
+    R/2] with rope_len >= 1 and R a multiple of 16 in [16, D]; q (if given) and
+    q_out (if given) are contiguous, of x's dtype and of x's shape but for the
+    heads (x: k_new, [B,Hkv,Sn,D] with rank 4 or [T,Hkv,D] with rank 3).
+    `where` true (after them): all four live on x's device and the tables are
+    16-byte aligned."""
+    import torch
+
+    if where:
+        for name, t in (("q", q), ("q_out", q_out), ("cos", cos), ("sin", sin)):
+            if t is not None and (not t.is_cuda or t.device != x.device):
+                raise FlashAttentionError(FA_ERR_NULL_POINTER, f"{name} must be a tensor on {x.device}")
+        for name, t in (("cos", cos), ("sin", sin)):
+            if t.data_ptr() % 16 != 0:
+                raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be 16-byte aligned")
+        return
+    for name, t in (("cos", cos), ("sin", sin)):
+        if not isinstance(t, torch.Tensor):
+            raise FlashAttentionError(FA_ERR_NULL_POINTER,
+                                      f"{name} is required: the float32 [rope_len, R/2] table")
+        if t.dtype != torch.float32:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be float32, got {t.dtype}")
+        if t.dim() != 2 or not t.is_contiguous():
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE,
+                                      f"{name} must be a contiguous [rope_len, R/2] tensor")
+    if cos.shape != sin.shape:
+        raise FlashAttentionError(
+            FA_ERR_BAD_SHAPE, f"cos and sin must have one shape, got {list(cos.shape)} and {list(sin.shape)}")
+    if cos.shape[0] < 1:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, "cos and sin hold no position (rope_len must be >= 1)")
+    r = 2 * cos.shape[1]
+    d = x.shape[-1] if x.dim() == rank else None
+    if r < 16 or r % 16 != 0 or (d is not None and r > d):
+        raise FlashAttentionError(
+            FA_ERR_BAD_SHAPE,
+            f"rotary_dim {r} (twice the tables' columns) is not a multiple of 16 in [16, head_dim]")
+    if q is None:
+        if q_out is not None:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, "q_out goes with q only")
+        return
+    layout = "[B,Hq,Sn,D]" if rank == 4 else "[T,Hq,D]"
+    for name, t in (("q", q), ("q_out", q_out)):
+        if t is None:
+            continue
+        if t.dtype != x.dtype:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be {x.dtype} like {xname}, got {t.dtype}")
+        if t.dim() != rank or not t.is_contiguous():
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be a contiguous {layout} tensor")
+    if x.dim() == rank and (q.shape[:1] + q.shape[2:]) != (x.shape[:1] + x.shape[2:]):
+        raise FlashAttentionError(
+            FA_ERR_BAD_SHAPE,
+            f"q must be {layout} with {xname}'s extents but for the heads, got {list(q.shape)} beside "
+            f"{list(x.shape)}")
+    if q_out is not None and q_out.shape != q.shape:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, "q_out must have q's shape")
+
+
+def _rope_tail(q, q_out, cos, sin, interleaved):
+    """The C entries' rotary arguments, after the append's."""
+    return (q.data_ptr() if q is not None else None, q_out.data_ptr() if q is not None else None,
+            q.shape[1] if q is not None else 0, cos.data_ptr(), sin.data_ptr(), cos.shape[0],
+            2 * cos.shape[1], int(bool(interleaved)))
+
+
+def _rope_append(q, k_new, v_new, k, v, block_table, names, kv_lens, cos, sin, new_lens, interleaved,
+                 q_out, k_scale, v_scale, stream):
+    import torch
+
+    _check_rope(k_new, "k_new", 4, q, q_out, cos, sin, False)
+    kv8 = _check_append(k_new, v_new, names[0], k, names[1], v, block_table, kv_lens, new_lens,
+                        k_scale, v_scale)
+    if q is not None and q_out is None:
+        q_out = torch.empty_like(q)
+    _check_rope(k_new, "k_new", 4, q, q_out, cos, sin, True)
+    b, hkv, sn, d = k_new.shape
+    if block_table is not None:
+        cache = (d, k.shape[0], k.shape[2], block_table.data_ptr(), block_table.shape[1])
+    else:
+        cache = (k.shape[2], d)
+    name = ("fa_rope_append" + ("_paged" if block_table is not None else "") + ("_kv8" if kv8 else "")
+            + ("_bf16" if k_new.dtype is torch.bfloat16 else "_f16"))
+    tail = ()
+    if kv8:
+        tail = (k_scale.data_ptr() if k_scale is not None else None,
+                v_scale.data_ptr() if v_scale is not None else None)
+    dev = k_new.device.index
+    if stream is None:
+        st = torch._C._cuda_getCurrentRawStream(dev)
+    else:
+        st = stream if isinstance(stream, int) else stream.cuda_stream
+    lib = _lib or load_library()
+    with torch.cuda.device(dev):
+        rc = getattr(lib, name)(k_new.data_ptr(), v_new.data_ptr(), k.data_ptr(), v.data_ptr(), b, hkv,
+                                sn, *cache, kv_lens.data_ptr(),
+                                new_lens.data_ptr() if new_lens is not None else None, st, *tail,
+                                *_rope_tail(q, q_out, cos, sin, interleaved))
+    _check(rc)
+    return q_out
+
+
+def flash_attention_rope_append(q, k_new, v_new, k_cache, v_cache, kv_lens, cos, sin, new_lens=None,
+                                interleaved: bool = False, q_out=None, k_scale=None, v_scale=None,
+                                stream=None):
+    """Rotary position embedding of Q and K fused with
+    :func:`flash_attention_cache_append` (fa_rope_append_f16 / _bf16, or
+    fa_rope_append_kv8_* into an FP8 cache): Q and K rotated, K and V appended,
+    one launch.
+
+    k_new, v_new, k_cache, v_cache, kv_lens, new_lens, the scales: as for
+    :func:`flash_attention_cache_append`.  q: [B, Hq, Sn, D] of k_new's dtype,
+    contiguous, or None (K/V only); Hq need not be a multiple of Hkv.  cos,
+    sin: float32 [rope_len, R/2] device tensors, contiguous; R = rotary_dim, a
+    multiple of 16 in [16, D].  Token t of element b has position pos =
+    kv_lens[b] - n_b + t, the cache row the append writes (no positions tensor).
+    interleaved False: NeoX / Hugging Face rotate_half pairs (x[i], x[i +
+    R/2]); True: GPT-J pairs (x[2i], x[2i + 1]).  With c = cos[pos, i], s =
+    sin[pos, i]: a' = a c - b s, b' = b c + a s, every product and sum one fp32
+    operation, the result rounded once to the 16-bit type -- bit for bit what
+    ``(a.float() * c - b.float() * s).to(dtype)`` gives on the CPU.  Elements
+    at or past R are bit copies; V is appended unchanged.  The rotated 16-bit K
+    row is what the append's contract stores, so the caches equal "rotate, then
+    flash_attention_cache_append" byte for byte in all four forms.
+
+    A K/V row is written iff the append's rule holds and pos < rope_len; a
+    row of q_out iff 0 <= pos < rope_len (rows t >= n_b are not written:
+    unspecified with q_out=None).  Returns q_out ([B, Hq, Sn, D]; allocated
+    when None; ``q_out=q`` rotates in place), or None with q=None.  Everything
+    is read on the device: no sync, no workspace, graph-capturable.
+    """
+    return _rope_append(q, k_new, v_new, k_cache, v_cache, None, ("k_cache", "v_cache"), kv_lens, cos,
+                        sin, new_lens, interleaved, q_out, k_scale, v_scale, stream)
+
+
+def flash_attention_rope_append_paged(q, k_new, v_new, k_pages, v_pages, block_table, kv_lens, cos, sin,
+                                      new_lens=None, interleaved: bool = False, q_out=None,
+                                      k_scale=None, v_scale=None, stream=None):
+    """:func:`flash_attention_rope_append` into the page pools of
+    :func:`flash_attention_cache_append_paged` (fa_rope_append_paged_* /
+    fa_rope_append_paged_kv8_*).  An out-of-pool page id drops the K/V row, not
+    the row of q_out."""
+    if block_table is None:
+        raise FlashAttentionError(FA_ERR_NULL_POINTER, "block_table is required")
+    return _rope_append(q, k_new, v_new, k_pages, v_pages, block_table, ("k_pages", "v_pages"), kv_lens,
+                        cos, sin, new_lens, interleaved, q_out, k_scale, v_scale, stream)
+
+
+def _rope_append_varlen(q, k_new, v_new, k, v, block_table, names, cu_seqlens, kv_lens, cos, sin,
+                        interleaved, q_out, k_scale, v_scale, stream):
+    import torch
+
+    _check_rope(k_new, "k_new", 3, q, q_out, cos, sin, False)
+    kv8, nseq = _check_packed(k_new, "k_new", v_new, "v_new", names[0], k, names[1], v, block_table,
+                              cu_seqlens, "cu_seqlens", kv_lens, k_scale, v_scale, True)
+    if q is not None and q_out is None:
+        q_out = torch.empty_like(q)
+    _check_rope(k_new, "k_new", 3, q, q_out, cos, sin, True)
+    name = ("fa_rope_append_varlen" + ("_paged" if block_table is not None else "")
+            + ("_kv8" if kv8 else "") + ("_bf16" if k_new.dtype is torch.bfloat16 else "_f16"))
+    total, d = k_new.shape[0], k_new.shape[2]
+    if block_table is not None:
+        cache = (d, k.shape[0], k.shape[2], block_table.data_ptr(), block_table.shape[1])
+    else:
+        cache = (k.shape[2], d)
+    tail = ()
+    if kv8:
+        tail = (k_scale.data_ptr() if k_scale is not None else None,
+                v_scale.data_ptr() if v_scale is not None else None)
+    dev = k_new.device.index
+    if stream is None:
+        st = torch._C._cuda_getCurrentRawStream(dev)
+    else:
+        st = stream if isinstance(stream, int) else stream.cuda_stream
+    lib = _lib or load_library()
+    with torch.cuda.device(dev):
+        rc = getattr(lib, name)(k_new.data_ptr(), v_new.data_ptr(), k.data_ptr(), v.data_ptr(), nseq,
+                                k_new.shape[1], total, *cache, kv_lens.data_ptr(), cu_seqlens.data_ptr(),
+                                st, *tail, *_rope_tail(q, q_out, cos, sin, interleaved))
+    _check(rc)
+    return q_out
+
+
+def flash_attention_rope_append_varlen(q, k_new, v_new, k_cache, v_cache, cu_seqlens, kv_lens, cos, sin,
+                                       interleaved: bool = False, q_out=None, k_scale=None,
+                                       v_scale=None, stream=None):
+    """:func:`flash_attention_rope_append` for a packed ragged batch
+    (fa_rope_append_varlen_*): q [T, Hq, D] (or None), k_new and v_new [T, Hkv,
+    D], token-major; cu_seqlens and kv_lens as for
+    :func:`flash_attention_cache_append_varlen`.  Token t of sequence b (packed
+    row s_b + t) has position kv_lens[b] - n_b + t.  The caches and the rows of
+    q_out equal the padded function's bit for bit; rows of q_out that belong to
+    no sequence are not written.  Returns q_out [T, Hq, D], or None."""
+    return _rope_append_varlen(q, k_new, v_new, k_cache, v_cache, None, ("k_cache", "v_cache"),
+                               cu_seqlens, kv_lens, cos, sin, interleaved, q_out, k_scale, v_scale, stream)
+
+
+def flash_attention_rope_append_varlen_paged(q, k_new, v_new, k_pages, v_pages, block_table, cu_seqlens,
+                                             kv_lens, cos, sin, interleaved: bool = False, q_out=None,
+                                             k_scale=None, v_scale=None, stream=None):
+    """:func:`flash_attention_rope_append_varlen` into the page pools of
+    :func:`flash_attention_cache_append_paged` (fa_rope_append_varlen_paged_*);
+    B is the block table's row count."""
+    if block_table is None:
+        raise FlashAttentionError(FA_ERR_NULL_POINTER, "block_table is required")
+    return _rope_append_varlen(q, k_new, v_new, k_pages, v_pages, block_table, ("k_pages", "v_pages"),
+                               cu_seqlens, kv_lens, cos, sin, interleaved, q_out, k_scale, v_scale, stream)
 
 
 def splitkv_buffers(batch: int, heads: int, seq_len: int, num_splits: int, device="cuda"):

@@ -14,6 +14,8 @@ rank 3: the wrapper that puts the kernel beside PyTorch SDPA on one box).
     o = torch.ops.fa_mi355x.prefill_varlen_paged(q_packed, k_pages, v_pages, block_table, cu_seqlens_q, kv_lens)
     torch.ops.fa_mi355x.cache_append_varlen(k_packed, v_packed, k_cache, v_cache, cu_seqlens, kv_lens)
     torch.ops.fa_mi355x.cache_append_varlen_paged(k_packed, v_packed, k_pages, v_pages, block_table, cu_seqlens, kv_lens)
+    q_rot = torch.ops.fa_mi355x.rope_append(q, k_new, v_new, k_cache, v_cache, kv_lens, cos, sin)  # RoPE + append
+    (and rope_append_paged, rope_append_varlen, rope_append_varlen_paged)
 
 ``q, k, v``: fp16 or bf16 ``[B, H, S, D]`` (D = 128 or 64) tensors on the GPU (BHSD, the
 reference layout, flash_attention.cu:119-122); returns a new tensor of the same shape and dtype.
@@ -37,7 +39,9 @@ from . import (flash_attention_cache_append, flash_attention_cache_append_paged,
                flash_attention_cache_append_varlen, flash_attention_cache_append_varlen_paged,
                flash_attention_decode, flash_attention_decode_paged, flash_attention_fwd,
                flash_attention_prefill, flash_attention_prefill_paged,
-               flash_attention_prefill_varlen, flash_attention_prefill_varlen_paged)
+               flash_attention_prefill_varlen, flash_attention_prefill_varlen_paged,
+               flash_attention_rope_append, flash_attention_rope_append_paged,
+               flash_attention_rope_append_varlen, flash_attention_rope_append_varlen_paged)
 
 OP_NAME = "fa_mi355x::fwd"
 
@@ -546,3 +550,73 @@ _window_overload("prefill_varlen", [_T("q"), _T("k_cache"), _T("v_cache"), _T("c
 _window_overload("prefill_varlen_paged", [_T("q"), _T("k_pages"), _T("v_pages"), _T("block_table"),
                                           _T("cu_seqlens_q"), _opt("kv_lens")] + _SINKS,
                  flash_attention_prefill_varlen_paged, _prefill_varlen_paged_fake, "sinks")
+
+# Fused RoPE + cache append: rope_append(q, k_new, v_new, the caches, kv_lens,
+# cos, sin: float32 [rope_len, R/2]) and its paged / packed twins:
+# fa_mi355x.flash_attention_rope_append[_varlen][_paged] behind the
+# cache_append kind of registration.  The caches are mutated in place and the
+# rotated Q comes back as a NEW tensor (the functions' q_out=None; for the
+# in-place form call the Python function with q_out=q).
+_ROPE_TAIL = ("Tensor cos, Tensor sin, {lens}bool interleaved=False, Tensor? k_scale=None, "
+              "Tensor? v_scale=None) -> Tensor")
+
+
+def _rope_op(name, fn, cache_args, packed):
+    """Registers fa_mi355x::<name>.  cache_args: the schema's names between
+    v_new and cos, in the Python function's order; `packed`: q / k_new / v_new
+    are [T,H,D] and there is no new_lens."""
+    names = cache_args.replace("Tensor(a!) ", "").replace("Tensor(b!) ", "").replace("Tensor ", "").split(", ")
+    _LIB.define(f"{name}(Tensor q, Tensor k_new, Tensor v_new, {cache_args}, "
+                + _ROPE_TAIL.format(lens="" if packed else "Tensor? new_lens=None, "))
+    rank = 3 if packed else 4
+    # the op's arguments in order: they are the Python function's keyword names
+    order = (["q", "k_new", "v_new"] + names + ["cos", "sin"] + ([] if packed else ["new_lens"])
+             + ["interleaved", "k_scale", "v_scale"])
+
+    def bind(args, kw):
+        a = dict(zip(order, args))
+        a.update(kw)
+        return a
+
+    def gpu(*args, **kw):
+        a = bind(args, kw)
+        # the caches are taken as they are (a strided cache raises), the rest made contiguous
+        a = {k: (v.contiguous() if isinstance(v, torch.Tensor) and k not in names[:2] else v)
+             for k, v in a.items()}
+        return fn(**a)
+
+    def cpu(*args, **kw):
+        raise ValueError(f"fa_mi355x::{name} needs GPU tensors (no CPU path)")
+
+    def fake(*args, **kw):
+        a = bind(args, kw)
+        q, k_new = a["q"], a["k_new"]
+        torch._check(k_new.dim() == rank and k_new.shape[-1] in (64, 128),
+                     lambda: "expected [T, Hkv, 64|128]" if packed else "expected [B, Hkv, Sn, 64|128]")
+        torch._check(k_new.dtype in (torch.float16, torch.bfloat16), lambda: "expected fp16 or bf16")
+        torch._check(q.dim() == rank and q.dtype == k_new.dtype, lambda: "expected q like k_new but for the heads")
+        torch._check(a[names[0]].dim() == 4 and a[names[1]].dim() == 4, lambda: "expected 4-D caches")
+        if "block_table" in a:
+            torch._check(a["block_table"].dim() == 2, lambda: "expected a [B, max_pages_per_seq] block table")
+        torch._check(a["cos"].dim() == 2 and a["cos"].dtype == torch.float32,
+                     lambda: "expected float32 [rope_len, R/2] tables")
+        return torch.empty_like(q, memory_format=torch.contiguous_format)
+
+    _LIB.impl(name, gpu, "CUDA")
+    _LIB.impl(name, cpu, "CPU")
+    torch.library.register_fake("fa_mi355x::" + name, fake, lib=_LIB)
+
+
+_rope_op("rope_append", flash_attention_rope_append,
+         "Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor kv_lens", False)
+_rope_op("rope_append_paged", flash_attention_rope_append_paged,
+         "Tensor(a!) k_pages, Tensor(b!) v_pages, Tensor block_table, Tensor kv_lens", False)
+_rope_op("rope_append_varlen", flash_attention_rope_append_varlen,
+         "Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor cu_seqlens, Tensor kv_lens", True)
+_rope_op("rope_append_varlen_paged", flash_attention_rope_append_varlen_paged,
+         "Tensor(a!) k_pages, Tensor(b!) v_pages, Tensor block_table, Tensor cu_seqlens, Tensor kv_lens", True)
+
+rope_append = torch.ops.fa_mi355x.rope_append
+rope_append_paged = torch.ops.fa_mi355x.rope_append_paged
+rope_append_varlen = torch.ops.fa_mi355x.rope_append_varlen
+rope_append_varlen_paged = torch.ops.fa_mi355x.rope_append_varlen_paged

@@ -32,6 +32,13 @@ padded append with new_lens -- by the same protocol, on the three ragged
 batches of tools/prefill_bench.py --varlen (Hkv = 8, D = 128), into a
 contiguous cache and a pool of page size 256, 16-bit and kv8; written to
 profiles/cache_append_varlen_bench.jsonl.
+
+--rope: the fused flash_attention_rope_append[_paged] (Hq = 32, NeoX style, R =
+D) against torch RoPE of Q and K followed by the existing append, and the
+existing append alone, by the same protocol (fused, composition, fused again,
+append), on the two shapes above into a contiguous 16-bit cache and a kv8 pool
+of page size 256.  bytes = Q in + Q out + K, V in + cache rows written; written
+to profiles/cache_append_rope_bench.jsonl.
 """
 import argparse
 import json
@@ -274,6 +281,132 @@ def run_varlen(name, page_size, kv8, rounds=9, copies=2, iters=4):
                 packed_share_of_copy_rate=round(nbytes / (med[0] * 1e-6) / COPY_RATE, 4))
 
 
+def run_rope(row, page_size, kv8, hq=32, rounds=9):
+    """--rope: flash_attention_rope_append[_paged] (NeoX style, R = D) against
+    what a caller does today -- RoPE of Q and K as torch kernels (the contract's
+    fp32 expression on cos / sin rows gathered per token OUTSIDE the timed
+    region, which flatters the composition), then the existing append -- and
+    the existing append alone.  Legs: fused, composition, fused again, append."""
+    dt = torch.float16
+    b, hkv, sn, d, cap = row["b"], row["hkv"], row["sn"], row["d"], row["cap"]
+    copies, iters = row["copies"], row["iters"]
+    paged = page_size > 0
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    cdt = torch.uint8 if kv8 else dt
+    if sn == cap:
+        lens = torch.full((b,), sn, dtype=torch.int32, device="cuda")
+    else:
+        lens = torch.randint(sn, cap + 1, (b,), generator=gen, device="cuda").to(torch.int32)
+    pos = lens.long()[:, None] - sn + torch.arange(sn, device="cuda")[None, :]  # [B, Sn]
+    inv_freq = 1.0 / (10000.0 ** (torch.arange(0, d, 2, dtype=torch.float32, device="cuda") / d))
+    ang = torch.outer(torch.arange(cap, dtype=torch.float32, device="cuda"), inv_freq)
+    cos, sin = ang.cos().contiguous(), ang.sin().contiguous()       # [cap, D/2]
+    ctok, stok = cos[pos][:, None].contiguous(), sin[pos][:, None].contiguous()  # [B, 1, Sn, D/2]
+    if paged:
+        mpp = cap // page_size
+        npages = b * mpp
+        shape = (npages, hkv, page_size, d)
+    else:
+        shape = (b, hkv, cap, d)
+    k_scale = torch.tensor([2.0 ** -(3 - (h & 1)) * 1.3 for h in range(hkv)], dtype=torch.float32, device="cuda")
+    v_scale = torch.tensor([2.0 ** -(2 + (h & 1)) * 0.7 for h in range(hkv)], dtype=torch.float32, device="cuda")
+    scales = dict(k_scale=k_scale, v_scale=v_scale) if kv8 else {}
+
+    def rnd(*s):
+        return (torch.rand(s, generator=gen, device="cuda", dtype=torch.float32) * 2 - 1).to(dt)
+
+    srcs = [(rnd(b, hq, sn, d), rnd(b, hkv, sn, d), rnd(b, hkv, sn, d)) for _ in range(copies)]
+    # [0]: the fused call's caches and q_out, [1]: the composition's, [2]: the plain append's
+    caches = [[(torch.zeros(shape, dtype=cdt, device="cuda"), torch.zeros(shape, dtype=cdt, device="cuda"))
+               for _ in range(copies)] for _ in range(3)]
+    qouts = [[torch.zeros((b, hq, sn, d), dtype=dt, device="cuda") for _ in range(copies)] for _ in range(2)]
+    tabs = [torch.randperm(npages, generator=gen, device="cuda").view(b, mpp).to(torch.int32).contiguous()
+            if paged else None for _ in range(copies)]
+
+    def typed(c):
+        return c.view(FP8) if kv8 else c
+
+    def plain(kn, vn, kc, vc, tab):
+        if paged:
+            fa_mi355x.flash_attention_cache_append_paged(kn, vn, typed(kc), typed(vc), tab, lens, **scales)
+        else:
+            fa_mi355x.flash_attention_cache_append(kn, vn, typed(kc), typed(vc), lens, **scales)
+
+    def fused(i):
+        c = i % copies
+        (q, kn, vn), (kc, vc) = srcs[c], caches[0][c]
+        if paged:
+            fa_mi355x.flash_attention_rope_append_paged(q, kn, vn, typed(kc), typed(vc), tabs[c], lens, cos, sin,
+                                                        q_out=qouts[0][c], **scales)
+        else:
+            fa_mi355x.flash_attention_rope_append(q, kn, vn, typed(kc), typed(vc), lens, cos, sin,
+                                                  q_out=qouts[0][c], **scales)
+
+    def rope_torch(x, out=None):
+        a, bb = x[..., :d // 2].float(), x[..., d // 2:].float()
+        y = torch.cat((a * ctok - bb * stok, bb * ctok + a * stok), -1)
+        return y.to(dt) if out is None else out.copy_(y)
+
+    def composition(i):
+        c = i % copies
+        (q, kn, vn), (kc, vc) = srcs[c], caches[1][c]
+        rope_torch(q, qouts[1][c])
+        plain(rope_torch(kn), vn, kc, vc, tabs[c])
+
+    def append_alone(i):
+        c = i % copies
+        (_, kn, vn), (kc, vc) = srcs[c], caches[2][c]
+        plain(kn, vn, kc, vc, tabs[c])
+
+    legs_fn = (fused, composition, append_alone)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):  # first-launch set-up outside the captures
+        for fn in legs_fn:
+            for i in range(copies):
+                fn(i)
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    same = all(torch.equal(a[0], c[0]) and torch.equal(a[1], c[1]) for a, c in zip(caches[0], caches[1])) \
+        and all(torch.equal(a, c) for a, c in zip(*qouts))
+    graphs = []
+    for fn in legs_fn:
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            for i in range(iters):
+                fn(i)
+        g.replay()
+        graphs.append(g)
+    torch.cuda.synchronize()
+    legs = (0, 1, 0, 2)  # fused, composition, fused again (the A/A leg), the plain append
+    ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+           for _ in range(rounds)] for _ in legs]
+    for r in range(rounds):
+        for j, gi in enumerate(legs):
+            ev[j][r][0].record()
+            graphs[gi].replay()
+            ev[j][r][1].record()
+    torch.cuda.synchronize()
+    ts = [sorted(a.elapsed_time(c) * 1e3 / iters for a, c in e) for e in ev]
+    med = [t[len(t) // 2] for t in ts]
+    kv_elems = 2 * b * hkv * sn * d  # K and V
+    q_elems = b * hq * sn * d
+    nbytes = 2 * q_elems * 2 + kv_elems * 2 + kv_elems * (1 if kv8 else 2)  # Q in + Q out + K, V in + rows written
+    plain_bytes = kv_elems * 2 + kv_elems * (1 if kv8 else 2)
+    return dict(name=row["name"], rope="neox R=D", cache="kv8" if kv8 else "16-bit", page_size=page_size, batch=b,
+                heads_q=hq, heads_kv=hkv, seqlen_new=sn, head_dim=d, kv_capacity=cap, copies=copies, iters=iters,
+                rounds=rounds, bytes_moved=nbytes, bit_identical_to_composition=same,
+                fused_us=round(med[0], 2), composition_us=round(med[1], 2), fused2_us=round(med[2], 2),
+                append_alone_us=round(med[3], 2),
+                fused_min_us=round(min(ts[0][0], ts[2][0]), 2), fused_max_us=round(max(ts[0][-1], ts[2][-1]), 2),
+                composition_min_us=round(ts[1][0], 2), composition_max_us=round(ts[1][-1], 2),
+                fused_aa=round(med[2] / med[0], 4), composition_over_fused=round(med[1] / med[0], 3),
+                fused_gb_per_s=round(nbytes / med[0] / 1e3, 1),
+                fused_share_of_copy_rate=round(nbytes / (med[0] * 1e-6) / COPY_RATE, 4),
+                append_alone_share_of_copy_rate=round(plain_bytes / (med[3] * 1e-6) / COPY_RATE, 4),
+                gate_faster_beyond_aa=bool(med[1] - med[0] > abs(med[2] - med[0])))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..",
@@ -282,9 +415,25 @@ def main():
     ap.add_argument("--varlen", action="store_true",
                     help="the packed entry against scatter + padded append (default --out: "
                          "profiles/cache_append_varlen_bench.jsonl)")
+    ap.add_argument("--rope", action="store_true",
+                    help="the fused RoPE + append against torch RoPE + the append (default --out: "
+                         "profiles/cache_append_rope_bench.jsonl)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("cache_append_bench.py needs a GPU")
+    if args.rope:
+        if args.out == ap.get_default("out"):
+            args.out = os.path.join(os.path.dirname(args.out), "cache_append_rope_bench.jsonl")
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            for row in shapes(args.quick):
+                for page_size, kv8 in ((0, False), (256, True)):
+                    rec = run_rope(row, page_size, kv8, hq=4 if args.quick else 32)
+                    f.write(json.dumps(rec) + "\n")
+                    f.flush()
+                    print(json.dumps(rec), flush=True)
+                    torch.cuda.empty_cache()
+        return
     if args.varlen and args.out == ap.get_default("out"):
         args.out = os.path.join(os.path.dirname(args.out), "cache_append_varlen_bench.jsonl")
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

@@ -596,6 +596,162 @@ int fa_cache_append_varlen_paged_kv8_bf16(const void* k_new, const void* v_new, 
                                           void* hip_stream, const float* k_scale,
                                           const float* v_scale);
 
+/* Fused rotary position embedding + cache append: Q and K rotated, K and V
+ * appended, one launch -- the step between the QKV projection and
+ * fa_prefill_* / fa_decode_*.  Each entry takes what the fa_cache_append_* /
+ * fa_cache_append_varlen_* entry of its cache form takes (with its meaning:
+ * n_b, kv_lens AFTER the append, the cache forms, the FP8 scales), followed by
+ *   q, q_out    [batch][heads_q][seqlen_new][head_dim], or packed
+ *               [total_new][heads_q][head_dim]; of k_new's 16-bit type,
+ *               contiguous.  q_out may be q (in place: a wave owns whole rows
+ *               and loads them before it stores them).  heads_q = 0 with
+ *               q = q_out = NULL rotates K only.  heads_q need not be a
+ *               multiple of heads_kv.
+ *   cos, sin    DEVICE float32 [rope_len][rotary_dim / 2], contiguous, 16-byte
+ *               aligned
+ *   rotary_dim  R, a multiple of 16 in [16, head_dim]
+ *   interleaved 0: NeoX / Hugging Face rotate_half pairs; 1: GPT-J pairs
+ * For token t < n_b of element b:
+ *   pos = kv_lens[b] - n_b + t     the cache row the append writes; no
+ *                                  positions tensor is taken
+ *   pairs, i in [0, R/2):  interleaved = 0:  a = x[i],  b = x[i + R/2]
+ *                          interleaved = 1:  a = x[2i], b = x[2i + 1]
+ *   c = cos[pos][i], s = sin[pos][i]
+ *   a' = a c - b s,  b' = b c + a s
+ * Each product and each sum is an IEEE fp32 operation rounded on its own
+ * (nothing is contracted into an fma) and the result is rounded once to the
+ * 16-bit type, to nearest even; elements at or past R are bit copies.  This is
+ * exactly what the torch expression (a.float() * c - b.float() * s).to(dtype)
+ * gives on the CPU, so a caller's result does not change by a bit when they
+ * switch over.  The equality is promised for finite inputs and tables whose
+ * fp32 products are normal or zero; non-finite inputs give an unspecified
+ * value, memory-safely.
+ * K: the rotated 16-bit row is what the append's contract then stores: a
+ * 16-bit cache takes it as it is, an FP8 cache applies E4M3(clamp(float(y) *
+ * (1.0f / s), +-448)) to the ROUNDED 16-bit value y.  Fused equals "rotate,
+ * then fa_cache_append_*" byte for byte in all four cache forms.  V is
+ * appended unchanged.  A 16-bit cache is no longer a bit copy, so every form
+ * has an _f16 and a _bf16 entry (the suffix is the type of k_new, v_new, q).
+ * Q: row t of every query head is rotated with the same pos into q_out.
+ * Which rows are written: a K/V row if and only if fa_cache_append_*'s rule
+ * holds (row in [0, kv_capacity), paged id in the pool) AND pos < rope_len; a
+ * q_out row if and only if t < n_b and 0 <= pos < rope_len (whatever the
+ * capacity and the page ids are).  Nothing else is stored to, and no table row
+ * outside [0, rope_len) is read.  kv_lens, new_lens / cu_seqlens, the block
+ * table, the scales and the tables are read on the device: no host read, no
+ * sync, no workspace, graph-capturable.
+ * Argument errors, all before any launch, in fa_cache_append_*'s order with
+ * the rotary ones among them: a negative size (heads_q included):
+ * FA_ERR_BAD_SHAPE; head_dim; seqlen_new / total_new; then rotary_dim not a
+ * multiple of 16 in [16, head_dim] or rope_len < 1: FA_ERR_BAD_SHAPE; the page
+ * geometry; batch == 0, heads_kv == heads_q == 0 (or total_new == 0): FA_OK,
+ * nothing enqueued; the capacity and grid ranges; a capacity of 0 leaves no
+ * K/V row (FA_OK, nothing enqueued with heads_q == 0; otherwise Q alone is
+ * rotated and the K/V pointers are not looked at); k_new, v_new, a cache,
+ * block_table, kv_lens (cu_seqlens), then cos or sin, then q or q_out with
+ * heads_q > 0 NULL: FA_ERR_NULL_POINTER; a table not 16-byte aligned:
+ * FA_ERR_BAD_SHAPE. */
+int fa_rope_append_f16(const void* k_new, const void* v_new, void* k_cache, void* v_cache, int batch,
+                       int heads_kv, int seqlen_new, int kv_capacity, int head_dim,
+                       const int* kv_lens, const int* new_lens, void* hip_stream, const void* q,
+                       void* q_out, int heads_q, const float* cos, const float* sin, int rope_len,
+                       int rotary_dim, int interleaved);
+int fa_rope_append_bf16(const void* k_new, const void* v_new, void* k_cache, void* v_cache, int batch,
+                        int heads_kv, int seqlen_new, int kv_capacity, int head_dim,
+                        const int* kv_lens, const int* new_lens, void* hip_stream, const void* q,
+                        void* q_out, int heads_q, const float* cos, const float* sin, int rope_len,
+                        int rotary_dim, int interleaved);
+int fa_rope_append_paged_f16(const void* k_new, const void* v_new, void* k_pages, void* v_pages,
+                             int batch, int heads_kv, int seqlen_new, int head_dim, int num_pages,
+                             int page_size, const int* block_table, int max_pages_per_seq,
+                             const int* kv_lens, const int* new_lens, void* hip_stream,
+                             const void* q, void* q_out, int heads_q, const float* cos,
+                             const float* sin, int rope_len, int rotary_dim, int interleaved);
+int fa_rope_append_paged_bf16(const void* k_new, const void* v_new, void* k_pages, void* v_pages,
+                              int batch, int heads_kv, int seqlen_new, int head_dim, int num_pages,
+                              int page_size, const int* block_table, int max_pages_per_seq,
+                              const int* kv_lens, const int* new_lens, void* hip_stream,
+                              const void* q, void* q_out, int heads_q, const float* cos,
+                              const float* sin, int rope_len, int rotary_dim, int interleaved);
+int fa_rope_append_kv8_f16(const void* k_new, const void* v_new, void* k_cache, void* v_cache,
+                           int batch, int heads_kv, int seqlen_new, int kv_capacity, int head_dim,
+                           const int* kv_lens, const int* new_lens, void* hip_stream,
+                           const float* k_scale, const float* v_scale, const void* q, void* q_out,
+                           int heads_q, const float* cos, const float* sin, int rope_len,
+                           int rotary_dim, int interleaved);
+int fa_rope_append_kv8_bf16(const void* k_new, const void* v_new, void* k_cache, void* v_cache,
+                            int batch, int heads_kv, int seqlen_new, int kv_capacity, int head_dim,
+                            const int* kv_lens, const int* new_lens, void* hip_stream,
+                            const float* k_scale, const float* v_scale, const void* q, void* q_out,
+                            int heads_q, const float* cos, const float* sin, int rope_len,
+                            int rotary_dim, int interleaved);
+int fa_rope_append_paged_kv8_f16(const void* k_new, const void* v_new, void* k_pages, void* v_pages,
+                                 int batch, int heads_kv, int seqlen_new, int head_dim,
+                                 int num_pages, int page_size, const int* block_table,
+                                 int max_pages_per_seq, const int* kv_lens, const int* new_lens,
+                                 void* hip_stream, const float* k_scale, const float* v_scale,
+                                 const void* q, void* q_out, int heads_q, const float* cos,
+                                 const float* sin, int rope_len, int rotary_dim, int interleaved);
+int fa_rope_append_paged_kv8_bf16(const void* k_new, const void* v_new, void* k_pages, void* v_pages,
+                                  int batch, int heads_kv, int seqlen_new, int head_dim,
+                                  int num_pages, int page_size, const int* block_table,
+                                  int max_pages_per_seq, const int* kv_lens, const int* new_lens,
+                                  void* hip_stream, const float* k_scale, const float* v_scale,
+                                  const void* q, void* q_out, int heads_q, const float* cos,
+                                  const float* sin, int rope_len, int rotary_dim, int interleaved);
+int fa_rope_append_varlen_f16(const void* k_new, const void* v_new, void* k_cache, void* v_cache,
+                              int batch, int heads_kv, int total_new, int kv_capacity, int head_dim,
+                              const int* kv_lens, const int* cu_seqlens, void* hip_stream,
+                              const void* q, void* q_out, int heads_q, const float* cos,
+                              const float* sin, int rope_len, int rotary_dim, int interleaved);
+int fa_rope_append_varlen_bf16(const void* k_new, const void* v_new, void* k_cache, void* v_cache,
+                               int batch, int heads_kv, int total_new, int kv_capacity, int head_dim,
+                               const int* kv_lens, const int* cu_seqlens, void* hip_stream,
+                               const void* q, void* q_out, int heads_q, const float* cos,
+                               const float* sin, int rope_len, int rotary_dim, int interleaved);
+int fa_rope_append_varlen_paged_f16(const void* k_new, const void* v_new, void* k_pages,
+                                    void* v_pages, int batch, int heads_kv, int total_new,
+                                    int head_dim, int num_pages, int page_size,
+                                    const int* block_table, int max_pages_per_seq,
+                                    const int* kv_lens, const int* cu_seqlens, void* hip_stream,
+                                    const void* q, void* q_out, int heads_q, const float* cos,
+                                    const float* sin, int rope_len, int rotary_dim, int interleaved);
+int fa_rope_append_varlen_paged_bf16(const void* k_new, const void* v_new, void* k_pages,
+                                     void* v_pages, int batch, int heads_kv, int total_new,
+                                     int head_dim, int num_pages, int page_size,
+                                     const int* block_table, int max_pages_per_seq,
+                                     const int* kv_lens, const int* cu_seqlens, void* hip_stream,
+                                     const void* q, void* q_out, int heads_q, const float* cos,
+                                     const float* sin, int rope_len, int rotary_dim, int interleaved);
+int fa_rope_append_varlen_kv8_f16(const void* k_new, const void* v_new, void* k_cache, void* v_cache,
+                                  int batch, int heads_kv, int total_new, int kv_capacity,
+                                  int head_dim, const int* kv_lens, const int* cu_seqlens,
+                                  void* hip_stream, const float* k_scale, const float* v_scale,
+                                  const void* q, void* q_out, int heads_q, const float* cos,
+                                  const float* sin, int rope_len, int rotary_dim, int interleaved);
+int fa_rope_append_varlen_kv8_bf16(const void* k_new, const void* v_new, void* k_cache, void* v_cache,
+                                   int batch, int heads_kv, int total_new, int kv_capacity,
+                                   int head_dim, const int* kv_lens, const int* cu_seqlens,
+                                   void* hip_stream, const float* k_scale, const float* v_scale,
+                                   const void* q, void* q_out, int heads_q, const float* cos,
+                                   const float* sin, int rope_len, int rotary_dim, int interleaved);
+int fa_rope_append_varlen_paged_kv8_f16(const void* k_new, const void* v_new, void* k_pages,
+                                        void* v_pages, int batch, int heads_kv, int total_new,
+                                        int head_dim, int num_pages, int page_size,
+                                        const int* block_table, int max_pages_per_seq,
+                                        const int* kv_lens, const int* cu_seqlens, void* hip_stream,
+                                        const float* k_scale, const float* v_scale, const void* q,
+                                        void* q_out, int heads_q, const float* cos, const float* sin,
+                                        int rope_len, int rotary_dim, int interleaved);
+int fa_rope_append_varlen_paged_kv8_bf16(const void* k_new, const void* v_new, void* k_pages,
+                                         void* v_pages, int batch, int heads_kv, int total_new,
+                                         int head_dim, int num_pages, int page_size,
+                                         const int* block_table, int max_pages_per_seq,
+                                         const int* kv_lens, const int* cu_seqlens, void* hip_stream,
+                                         const float* k_scale, const float* v_scale, const void* q,
+                                         void* q_out, int heads_q, const float* cos, const float* sin,
+                                         int rope_len, int rotary_dim, int interleaved);
+
 /* Sliding-window attention: the twelve fa_decode_*, fa_prefill_* and
  * fa_prefill_varlen_* entry pairs above with `int window` inserted directly
  * after `causal` (`_win` follows the family name).  window = W is the largest
