@@ -118,6 +118,29 @@ struct ParamsWindowed<PrefillPacked<Base>> : ParamsWindowed<Base> {};
 template <class Base>
 struct ParamsSinked<PrefillPacked<Base>> : ParamsSinked<Base> {};
 
+// The fifth K/V source (the fa_attn_varlen_* entries): no
+// cache at all, K and V token-major [T_k][Hkv][D] as Q is, the three of them
+// runtime strides apart (so they may be the slices of one fused QKV buffer).
+// Always packed: P = PrefillPacked<[Sinked<Windowed<]PrefillTokenKV[>>]>, and
+// the fields of PrefillParams are read as
+//   q_lens = cu_seqlens_q or nullptr, sq = T_q, nqb = B, cap = T_k;
+//   kv_lens, bhk unused
+// Sequence b's queries are the span of cu_seqlens_q (fa_varlen_map.hpp's rule,
+// clamped to [0, T_q]) and its keys the span (sk_b, nk_b) of cu_k clamped to
+// [0, T_k]; a nullptr stands for i * useq_q / i * useq_k (uniform lengths, the
+// [B][S][H][D] layout: no array is read).  len_b := nk_b in the header's
+// formulas, so the tile sequence of a block, and with it every bit of O and
+// LSE, is that of the packed contiguous-cache kernel on a cache whose rows
+// [0, nk_b) are the same keys.  The descriptor of tile tl starts at row
+// sk_b + 64 tl of head hkv and ends with the last live row's own ROW bytes
+// (as the packed Q descriptor does), the staging loads step by the runtime
+// stride, O stays dense.  All of it sits under `if constexpr (TOK)`.
+struct PrefillTokenKV : PrefillParams {
+  const int* cu_k;           // device int32[B + 1], or nullptr (uniform)
+  int useq_q, useq_k;        // the uniform lengths (read where the cu is nullptr)
+  int q_sb, k_sb, v_sb;      // bytes between consecutive tokens of Q, K and V
+};
+
 // WIN (P = [PrefillPacked<]Windowed<...>[>], the fa_prefill[_varlen]_win_*
 // entries; without causal the host admits W = 0 alone and the kernel applies
 // no lower bound): row t of the block also masks the keys below
@@ -144,6 +167,9 @@ __global__ __launch_bounds__(256, 2) void fa_prefill_kernel(P p) {
   constexpr bool VARLEN = PrefillIsPacked<P>::value;
   constexpr bool WIN = ParamsWindowed<P>::value;
   constexpr bool SINK = ParamsSinked<P>::value;
+  constexpr bool TOK = std::is_base_of<PrefillTokenKV, P>::value;
+  static_assert(!TOK || (VARLEN && !PAGED && std::is_same<KV, T>::value),
+                "token-major K/V: packed, 16-bit, no pages");
   __shared__ __attribute__((aligned(16))) char smem[kPrefillLdsBytes];
   constexpr bool KV8 = !std::is_same<KV, T>::value;
   static_assert(!KV8 || std::is_same<KV, unsigned char>::value, "the cache holds T or E4M3 bytes");
@@ -184,7 +210,11 @@ __global__ __launch_bounds__(256, 2) void fa_prefill_kernel(P p) {
     // blocks; the order BETWEEN sequences stays the packing order
     int id = (int)(rest / (unsigned)p.hkv);
     if (p.causal) id = p.sq / BM + p.nqb - 1 - id;
-    if (!varlen_block<BM>(p.q_lens, p.nqb, p.sq, id, b, s0, nq, qb)) return;
+    if constexpr (TOK) {
+      if (!varlen_block_u<BM>(p.q_lens, p.useq_q, p.nqb, p.sq, id, b, s0, nq, qb)) return;
+    } else {
+      if (!varlen_block<BM>(p.q_lens, p.nqb, p.sq, id, b, s0, nq, qb)) return;
+    }
     b = __builtin_amdgcn_readfirstlane(b);
     s0 = __builtin_amdgcn_readfirstlane(s0);
     nq = __builtin_amdgcn_readfirstlane(nq);
@@ -202,8 +232,18 @@ __global__ __launch_bounds__(256, 2) void fa_prefill_kernel(P p) {
   }
   const int q0 = qb * BM;
   if (q0 >= nq) return;  // nothing of this block is valid: nothing is written
-  int len = p.kv_lens ? p.kv_lens[b] : p.cap;
-  len = __builtin_amdgcn_readfirstlane(min(max(len, 0), p.cap));
+  int len;
+  [[maybe_unused]] int sk = 0;  // TOK: the sequence's first key row
+  if constexpr (TOK) {
+    // the keys' span: one more pair of scalar loads (uniform mode: none)
+    sk = varlen_start(p.cu_k, p.useq_k, p.cap, b);
+    len = max(varlen_start(p.cu_k, p.useq_k, p.cap, b + 1), sk) - sk;
+    sk = __builtin_amdgcn_readfirstlane(sk);
+    len = __builtin_amdgcn_readfirstlane(len);
+  } else {
+    len = p.kv_lens ? p.kv_lens[b] : p.cap;
+    len = __builtin_amdgcn_readfirstlane(min(max(len, 0), p.cap));
+  }
   const int off = len - nq;  // keys before the chunk (negative: the leading rows see nothing)
   const int kv_hi = p.causal ? max(0, min(len, off + q0 + BM)) : len;
   const int ntiles = (kv_hi + BN - 1) / BN;
@@ -239,8 +279,18 @@ __global__ __launch_bounds__(256, 2) void fa_prefill_kernel(P p) {
   }
   // the range ends with the last valid row's own bytes (VARLEN: <= 127 * Hq *
   // ROW + ROW, which the host checks fits)
-  const __amdgpu_buffer_rsrc_t rq = make_rsrc(static_cast<const char*>(p.q) + qrow0 * ROW,
-                                              VARLEN ? (qrows - 1) * qs + ROW : qrows * ROW);
+  // TOK: Q rows are the runtime stride apart (qsq; <= 127 * qsq + ROW fits, the
+  // host's check), O rows stay dense (qs)
+  [[maybe_unused]] int qsq = 0;
+  __amdgpu_buffer_rsrc_t rq;
+  if constexpr (TOK) {
+    qsq = p.q_sb;
+    rq = make_rsrc(static_cast<const char*>(p.q) + ((size_t)s0 + q0) * (size_t)qsq + (size_t)hq * ROW,
+                   (qrows - 1) * qsq + ROW);
+  } else {
+    rq = make_rsrc(static_cast<const char*>(p.q) + qrow0 * ROW,
+                   VARLEN ? (qrows - 1) * qs + ROW : qrows * ROW);
+  }
   const __amdgpu_buffer_rsrc_t ro = make_rsrc(static_cast<char*>(p.o) + qrow0 * ROW,
                                               VARLEN ? (qrows - 1) * qs + ROW : qrows * ROW);
 
@@ -265,7 +315,11 @@ __global__ __launch_bounds__(256, 2) void fa_prefill_kernel(P p) {
   // head without one (-inf, or sinks == nullptr) keeps the windowed kernel's
   // arithmetic and so its bits
   if constexpr (RTS) pol.scale_s_rt = sink2 != ninf();
-  pol.issue_q(rq, qwl, qs);  // scaled once tile 0's loads are in flight
+  // scaled once tile 0's loads are in flight
+  if constexpr (TOK)
+    pol.issue_q(rq, qwl, qsq);
+  else
+    pol.issue_q(rq, qwl, qs);
 
   // Staging.  16-bit: the policy's lanes (K natural row-major, V two rows of
   // opposite parity x 4 chunks per 8 lanes).  FP8: a lane holds a 16-byte
@@ -293,14 +347,29 @@ __global__ __launch_bounds__(256, 2) void fa_prefill_kernel(P p) {
     vr0 = pol.v_stage_row(wave), vc = pol.v_stage_ch();
   }
   static_assert(KV8 || RPP == Pol::RPW * WAVES, "the policy's staging covers RPW rows per wave");
-  const int kvo = kr0 * CROW + kc * 16, vvo = vr0 * CROW + vc * 16;
+  // TOK: the rows of a tile are ksb (K) and vsb (V) bytes apart
+  [[maybe_unused]] int ksb = 0, vsb = 0;
+  int kvo, vvo;
+  if constexpr (TOK) {
+    ksb = p.k_sb, vsb = p.v_sb;
+    kvo = kr0 * ksb + kc * 16, vvo = vr0 * vsb + vc * 16;
+  } else {
+    kvo = kr0 * CROW + kc * 16, vvo = vr0 * CROW + vc * 16;
+  }
 
   // The descriptors of the tile whose loads are issued next: its 64 rows start
   // at the base and the range ends at its last visible row (a tile past the
   // range: zero bytes, no memory traffic).
-  const size_t kvoff = PAGED ? 0 : (size_t)bhk * (size_t)p.cap * CROW;
-  const char* Kh = static_cast<const char*>(p.k) + kvoff;
-  const char* Vh = static_cast<const char*>(p.v) + kvoff;
+  const char *Kh, *Vh;
+  if constexpr (TOK) {
+    // head hk's part of the sequence's first key row
+    Kh = static_cast<const char*>(p.k) + (size_t)sk * (size_t)ksb + (size_t)hk * ROW;
+    Vh = static_cast<const char*>(p.v) + (size_t)sk * (size_t)vsb + (size_t)hk * ROW;
+  } else {
+    const size_t kvoff = PAGED ? 0 : (size_t)bhk * (size_t)p.cap * CROW;
+    Kh = static_cast<const char*>(p.k) + kvoff;
+    Vh = static_cast<const char*>(p.v) + kvoff;
+  }
   __amdgpu_buffer_rsrc_t rk, rv;
   // pg: the tile's pool page, r: its 64-row block within head hk's part of the page (paged only)
   auto tile_at = [&](int tl, [[maybe_unused]] int pg, [[maybe_unused]] int r) {
@@ -312,6 +381,13 @@ __global__ __launch_bounds__(256, 2) void fa_prefill_kernel(P p) {
                        (size_t)(BN * r) * CROW;
       rk = make_rsrc(Kh + o, ok ? live * CROW : 0);
       rv = make_rsrc(Vh + o, ok ? live * CROW : 0);
+    } else if constexpr (TOK) {
+      // the range ends with the last live row's own ROW bytes: a lane's 16
+      // bytes of row r lie inside it iff r < live, whatever the strides (>=
+      // Hkv * ROW, the host's check); <= 63 * stride + ROW fits (the same)
+      const size_t r0 = (size_t)min(BN * tl, kv_hi);
+      rk = make_rsrc(Kh + r0 * (size_t)ksb, live > 0 ? (live - 1) * ksb + ROW : 0);
+      rv = make_rsrc(Vh + r0 * (size_t)vsb, live > 0 ? (live - 1) * vsb + ROW : 0);
     } else {
       // a tile past the range keeps the base inside the cache (tl <= ntiles)
       const size_t o = (size_t)min(BN * tl, kv_hi) * CROW;
@@ -323,8 +399,13 @@ __global__ __launch_bounds__(256, 2) void fa_prefill_kernel(P p) {
   auto issue_loads = [&]() {
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
-      kst[i] = __builtin_amdgcn_raw_buffer_load_b128(rk, kvo + RPP * i * CROW, 0, 0);
-      vst[i] = __builtin_amdgcn_raw_buffer_load_b128(rv, vvo + RPP * i * CROW, 0, 0);
+      if constexpr (TOK) {
+        kst[i] = __builtin_amdgcn_raw_buffer_load_b128(rk, kvo + RPP * i * ksb, 0, 0);
+        vst[i] = __builtin_amdgcn_raw_buffer_load_b128(rv, vvo + RPP * i * vsb, 0, 0);
+      } else {
+        kst[i] = __builtin_amdgcn_raw_buffer_load_b128(rk, kvo + RPP * i * CROW, 0, 0);
+        vst[i] = __builtin_amdgcn_raw_buffer_load_b128(rv, vvo + RPP * i * CROW, 0, 0);
+      }
     }
   };
   // WIN, tile tlo (the prologue's): its rows below kv_lo are addressed past
@@ -335,10 +416,17 @@ __global__ __launch_bounds__(256, 2) void fa_prefill_kernel(P p) {
   [[maybe_unused]] auto issue_loads_first = [&]() {
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
-      kst[i] = __builtin_amdgcn_raw_buffer_load_b128(
-          rk, kr0 + RPP * i >= lo_in ? kvo + RPP * i * CROW : kBelowWindow, 0, 0);
-      vst[i] = __builtin_amdgcn_raw_buffer_load_b128(
-          rv, vr0 + RPP * i >= lo_in ? vvo + RPP * i * CROW : kBelowWindow, 0, 0);
+      if constexpr (TOK) {
+        kst[i] = __builtin_amdgcn_raw_buffer_load_b128(
+            rk, kr0 + RPP * i >= lo_in ? kvo + RPP * i * ksb : kBelowWindow, 0, 0);
+        vst[i] = __builtin_amdgcn_raw_buffer_load_b128(
+            rv, vr0 + RPP * i >= lo_in ? vvo + RPP * i * vsb : kBelowWindow, 0, 0);
+      } else {
+        kst[i] = __builtin_amdgcn_raw_buffer_load_b128(
+            rk, kr0 + RPP * i >= lo_in ? kvo + RPP * i * CROW : kBelowWindow, 0, 0);
+        vst[i] = __builtin_amdgcn_raw_buffer_load_b128(
+            rv, vr0 + RPP * i >= lo_in ? vvo + RPP * i * CROW : kBelowWindow, 0, 0);
+      }
     }
   };
   auto write_lds = [&](char* kb) {

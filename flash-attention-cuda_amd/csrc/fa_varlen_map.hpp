@@ -48,4 +48,31 @@ __device__ __forceinline__ bool varlen_block(const int* cu_, int nseq, int total
   return r < (n + BT - 1) / BT;
 }
 
+// The same map where cu may be absent (the uniform mode of the token-major
+// attention entries, fa_attn_varlen_*): entry i is then i * S, never a load,
+// and the host has checked nseq * S == total.  A twin of varlen_block(), not a
+// parameter of it: the packed entries' instantiations stay what they were.
+__device__ __forceinline__ int varlen_start(const int* cu_, int S, int total, int i) {
+  typedef const __attribute__((address_space(4))) int* cu_t;  // scalar loads
+  return cu_ ? min(max(((cu_t)cu_)[i], 0), total) : min(i * S, total);
+}
+template <int BT>
+__device__ __forceinline__ bool varlen_block_u(const int* cu_, int S, int nseq, int total, int id,
+                                               int& b, int& s, int& n, int& r) {
+  int lo = 0, hi = nseq + 1;
+  while (lo < hi) {
+    const int mid = (int)(((unsigned)lo + (unsigned)hi) >> 1);
+    if (varlen_start(cu_, S, total, mid) / BT + mid <= id)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  if (lo == 0 || lo > nseq) return false;
+  b = lo - 1;
+  s = varlen_start(cu_, S, total, b);
+  n = max(varlen_start(cu_, S, total, b + 1), s) - s;
+  r = id - (s / BT + b);
+  return r < (n + BT - 1) / BT;
+}
+
 }  // namespace fa

@@ -150,6 +150,12 @@ EXPORTED_SYMBOLS = (
     "fa_rope_append_varlen_kv8_bf16",
     "fa_rope_append_varlen_paged_kv8_f16",
     "fa_rope_append_varlen_paged_kv8_bf16",
+    "fa_attn_varlen_f16",
+    "fa_attn_varlen_bf16",
+    "fa_attn_varlen_win_f16",
+    "fa_attn_varlen_win_bf16",
+    "fa_attn_varlen_sink_f16",
+    "fa_attn_varlen_sink_bf16",
     "fa_select_config",
     "fa_num_configs",
     "fa_config_info",
@@ -316,6 +322,15 @@ def load_library() -> ctypes.CDLL:
                 fn = getattr(lib, fam + "_sink" + form + ty)
                 fn.argtypes = base[:at] + [i, vp] + base[at:]
                 fn.restype = i
+    # attention over token-major Q, K, V (no cache): three long long strides
+    # after head_dim; _win: `int window` after causal; _sink: `sinks` last
+    ll = ctypes.c_longlong
+    for ty in ("_f16", "_bf16"):
+        head = [vp, vp, vp, vp, vp, i, i, i, i, i, i, ll, ll, ll, vp, vp, i, i, i]
+        for variant, mid, last in (("", [], []), ("_win", [i], []), ("_sink", [i], [vp])):
+            fn = getattr(lib, "fa_attn_varlen" + variant + ty)
+            fn.argtypes = head + mid + [vp] + last
+            fn.restype = i
     lib.fa_decode_num_splits.argtypes = [i, i, i, i, i, i]
     lib.fa_decode_num_splits.restype = i
     lib.fa_decode_ws_bytes.argtypes = [i, i, i, i, i, i, i]
@@ -1363,6 +1378,186 @@ def flash_attention_prefill_varlen_paged(q, k_pages, v_pages, block_table, cu_se
         raise FlashAttentionError(FA_ERR_NULL_POINTER, "block_table is required")
     return _prefill_varlen(q, k_pages, v_pages, block_table, ("k_pages", "v_pages"), cu_seqlens_q,
                            kv_lens, causal, out, return_lse, stream, k_scale, v_scale, window, sinks)
+
+
+def _token_stride(t, name, rank):
+    """The token stride (elements; 0: dense) of a token-major view, [T,H,D] or
+    [B,S,H,D]: the last dimension contiguous, heads D apart, and (rank 4) the
+    batch stride S token strides, so that tokens are one stride apart
+    throughout.  Extents of 1 have no stride to check.  Nothing is copied:
+    anything else raises."""
+    h, d = t.shape[-2], t.shape[-1]
+    if (d > 1 and t.stride(-1) != 1) or (h > 1 and t.stride(-2) != d):
+        raise FlashAttentionError(
+            FA_ERR_BAD_SHAPE,
+            f"{name} must have stride(-1) == 1 and stride(-2) == head_dim (a token-major view; it is "
+            f"not copied), got strides {tuple(t.stride())}")
+    ntok = t.shape[-3]
+    if rank == 4 and t.shape[0] > 1:
+        if ntok > 1 and t.stride(0) != ntok * t.stride(1):
+            raise FlashAttentionError(
+                FA_ERR_BAD_SHAPE,
+                f"{name}: the batch stride {t.stride(0)} is not seqlen * the token stride "
+                f"{t.stride(1)} (it is not copied)")
+        st = t.stride(1) if ntok > 1 else t.stride(0)
+    else:
+        st = t.stride(-3) if ntok > 1 else 0
+    if st % 8 != 0 or (st and st < h * d):
+        raise FlashAttentionError(
+            FA_ERR_BAD_SHAPE,
+            f"{name}: the token stride {st} must be a multiple of 8 elements, at least heads * head_dim")
+    return st
+
+
+def _check_attn(q, k, v, out, rank, cu_q, cu_k, sinks):
+    """What flash_attention_varlen (rank 3, [T,H,D]) and flash_attention_bshd
+    (rank 4, [B,S,H,D]) check: dtypes, ranks and shapes, then where the tensors
+    live, never values.  Returns the three token strides."""
+    import torch
+
+    layout = " [T,H,D]" if rank == 3 else " [B,S,H,D]"
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"q must be float16 or bfloat16, got {q.dtype}")
+    for name, t in (("q", q), ("k", k), ("v", v), ("out", out)):
+        if t.dtype != q.dtype:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be {q.dtype}, got {t.dtype}")
+        if t.dim() != rank:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be {rank}-D{layout}")
+    if not out.is_contiguous():
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"out must be contiguous{layout}")
+    if out.shape != q.shape:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"out must be{layout} like q")
+    if k.shape != v.shape:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, "k and v must have one shape")
+    if k.shape[-1] != q.shape[-1] or (rank == 4 and k.shape[0] != q.shape[0]):
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE,
+                                  "q, k and v must agree in head_dim" + (" and batch" if rank == 4 else ""))
+    strides = tuple(_token_stride(t, name, rank) for name, t in (("q", q), ("k", k), ("v", v)))
+    hq, hkv = q.shape[-2], k.shape[-2]
+    if hkv == 0 or hq % hkv != 0:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"heads_q {hq} is not a multiple of heads_kv {hkv}")
+    if sinks is not None:
+        t = sinks
+        if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 1
+                or t.shape[0] != hq or not t.is_contiguous()):
+            got = f"{t.dtype} {list(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+            raise FlashAttentionError(
+                FA_ERR_BAD_SHAPE, f"sinks must be a contiguous float32 [Hq = {hq}] tensor, got {got}")
+    if rank == 3:
+        if cu_q is None:
+            _check_cu_seqlens(None, "cu_seqlens_q", 0, q, False)
+        if cu_q.dim() != 1 or cu_q.shape[0] < 1:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, "cu_seqlens_q must be a [B + 1] tensor")
+        nseq = cu_q.shape[0] - 1
+        _check_cu_seqlens(cu_q, "cu_seqlens_q", nseq, q, False)
+        if cu_k is not None:
+            _check_cu_seqlens(cu_k, "cu_seqlens_k", nseq, q, False)
+    for name, t in (("q", q), ("k", k), ("v", v), ("out", out)):
+        if not t.is_cuda:
+            raise FlashAttentionError(FA_ERR_NULL_POINTER, f"{name} must be a device tensor")
+        if t.device != q.device:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE,
+                                      f"{name} is on {t.device}, q on {q.device}: one device only")
+    if rank == 3:
+        _check_cu_seqlens(cu_q, "cu_seqlens_q", nseq, q, True)
+        if cu_k is not None:
+            _check_cu_seqlens(cu_k, "cu_seqlens_k", nseq, q, True)
+    if sinks is not None and (not sinks.is_cuda or sinks.device != q.device):
+        raise FlashAttentionError(FA_ERR_NULL_POINTER, f"sinks must be a tensor on {q.device}")
+    return strides
+
+
+def _attn_call(q, k, v, out, strides, batch, total_q, total_k, cu_q, cu_k, seqlen_q, seqlen_k, causal,
+               lse, stream, window, sinks):
+    """The call of the two functions below after their checks: the stream and
+    the fa_attn_varlen[_win|_sink]_* entry of q's dtype."""
+    import torch
+
+    variant, win = _entry_variant(window, sinks)  # window: checked by the public function
+    last = ()
+    if sinks is not None:
+        win, last = win[:1], win[1:]  # these entries take `sinks` after the stream
+    name = "fa_attn_varlen" + variant + ("_bf16" if q.dtype is torch.bfloat16 else "_f16")
+    dev = q.device.index
+    if stream is None:
+        st = torch._C._cuda_getCurrentRawStream(dev)
+    else:
+        st = stream if isinstance(stream, int) else stream.cuda_stream
+    lib = _lib or load_library()
+    with torch.cuda.device(dev):
+        rc = getattr(lib, name)(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
+                                lse.data_ptr() if lse is not None else None, batch, q.shape[-2],
+                                k.shape[-2], total_q, total_k, q.shape[-1], *strides,
+                                cu_q.data_ptr() if cu_q is not None else None,
+                                cu_k.data_ptr() if cu_k is not None else None, seqlen_q, seqlen_k,
+                                int(bool(causal)), *win, st, *last)
+    _check(rc)
+
+
+def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k=None, causal: bool = False, out=None,
+                           return_lse: bool = False, stream=None, window: int = 0, sinks=None):
+    """Attention over token-major Q, K and V with no cache (fa_attn_varlen_f16 /
+    _bf16; flash-attn's ``flash_attn_varlen_func``): a packed ragged batch as
+    the QKV projection leaves it -- an encoder, a vision tower (causal=False),
+    an embedding model, a first prefill whose keys are not cached yet.
+
+    q: [T_q, Hq, D]; k, v: [T_k, Hkv, D] with Hq % Hkv == 0 (GQA / MQA); fp16 or
+    bf16 device tensors of one dtype, D = 128 or 64.  Each may be a VIEW with
+    stride(-1) == 1 and stride(-2) == D whose token stride is a multiple of 8
+    elements -- the three slices of one fused QKV buffer are read in place;
+    anything else raises (nothing is ever copied).  cu_seqlens_q, cu_seqlens_k:
+    int32 [B + 1] on q's device, read and clamped there as
+    :func:`flash_attention_prefill_varlen` reads cu_seqlens_q: sequence b's
+    queries are rows [sq_b, sq_b + nq_b) of q and its keys rows [sk_b, sk_b +
+    nk_b) of k and v.  cu_seqlens_k=None: self-attention, the keys' spans are
+    the queries'.  causal: bottom-right aligned, row t of b sees keys < nk_b -
+    nq_b + t + 1 of b.  A row that sees no key gives zeros and LSE = -inf.
+    Rows that belong to no sequence are not written (unspecified with
+    out=None) and K/V rows that belong to none are never read.  The result
+    equals :func:`flash_attention_prefill_varlen` on a contiguous cache holding
+    the same keys (kv_lens = nk) BIT FOR BIT.  Any contents of the cu arrays
+    are memory-safe.  out: a contiguous [T_q, Hq, D] tensor that does not
+    overlap q.  Returns out, or (out, lse) with lse fp32 [Hq, T_q] (natural
+    log) when return_lse.  No sync, no workspace, graph-capturable.
+    window, sinks: as for :func:`flash_attention_prefill`
+    (fa_attn_varlen_win_* / fa_attn_varlen_sink_*), pos = nk_b - nq_b + t.
+    """
+    window = _check_window(window, causal)  # before the tensors: a bad window is named whatever they are
+    import torch
+
+    if out is None:
+        out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+    strides = _check_attn(q, k, v, out, 3, cu_seqlens_q, cu_seqlens_k, sinks)
+    total_q, hq = q.shape[0], q.shape[1]
+    lse = torch.empty((hq, total_q), dtype=torch.float32, device=q.device) if return_lse else None
+    _attn_call(q, k, v, out, strides, cu_seqlens_q.shape[0] - 1, total_q, k.shape[0], cu_seqlens_q,
+               cu_seqlens_k, 0, 0, causal, lse, stream, window, sinks)
+    return (out, lse) if return_lse else out
+
+
+def flash_attention_bshd(q, k, v, causal: bool = False, out=None, return_lse: bool = False, stream=None,
+                         window: int = 0, sinks=None):
+    """:func:`flash_attention_varlen` for uniform lengths (flash-attn's
+    ``flash_attn_func``): q [B, Sq, Hq, D], k and v [B, Sk, Hkv, D], taken as
+    they are -- the entries' uniform mode, with no cu_seqlens tensor and no
+    extra launch.  Views as for that function, with stride(0) == S * stride(1)
+    (a [B, S, (Hq + 2 Hkv) D] projection output sliced along its last
+    dimension qualifies).  causal: bottom-right aligned (row t sees keys < Sk -
+    Sq + t + 1).  Returns out [B, Sq, Hq, D] (contiguous), or (out, lse) with
+    lse a [B, Hq, Sq] VIEW of the fp32 [Hq, B * Sq] result when return_lse.
+    window, sinks: as for that function."""
+    window = _check_window(window, causal)  # before the tensors: a bad window is named whatever they are
+    import torch
+
+    if out is None:
+        out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+    strides = _check_attn(q, k, v, out, 4, None, None, sinks)
+    b, sq, hq, _ = q.shape
+    sk = k.shape[1]
+    lse = torch.empty((hq, b * sq), dtype=torch.float32, device=q.device) if return_lse else None
+    _attn_call(q, k, v, out, strides, b, b * sq, b * sk, None, None, sq, sk, causal, lse, stream, window,
+               sinks)
+    return (out, lse.view(hq, b, sq).permute(1, 0, 2)) if return_lse else out
 
 
 def _append_varlen(k_new, v_new, k, v, block_table, names, cu_seqlens, kv_lens, k_scale, v_scale, stream):

@@ -16,6 +16,8 @@ rank 3: the wrapper that puts the kernel beside PyTorch SDPA on one box).
     torch.ops.fa_mi355x.cache_append_varlen_paged(k_packed, v_packed, k_pages, v_pages, block_table, cu_seqlens, kv_lens)
     q_rot = torch.ops.fa_mi355x.rope_append(q, k_new, v_new, k_cache, v_cache, kv_lens, cos, sin)  # RoPE + append
     (and rope_append_paged, rope_append_varlen, rope_append_varlen_paged)
+    o = torch.ops.fa_mi355x.attn_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, causal=False)  # [T,H,D], no cache
+    o = torch.ops.fa_mi355x.attn_bshd(q, k, v, causal=True)  # [B,S,H,D], no cache
 
 ``q, k, v``: fp16 or bf16 ``[B, H, S, D]`` (D = 128 or 64) tensors on the GPU (BHSD, the
 reference layout, flash_attention.cu:119-122); returns a new tensor of the same shape and dtype.
@@ -37,11 +39,13 @@ import torch
 
 from . import (flash_attention_cache_append, flash_attention_cache_append_paged,
                flash_attention_cache_append_varlen, flash_attention_cache_append_varlen_paged,
-               flash_attention_decode, flash_attention_decode_paged, flash_attention_fwd,
+               flash_attention_bshd, flash_attention_decode, flash_attention_decode_paged,
+               flash_attention_fwd,
                flash_attention_prefill, flash_attention_prefill_paged,
                flash_attention_prefill_varlen, flash_attention_prefill_varlen_paged,
                flash_attention_rope_append, flash_attention_rope_append_paged,
-               flash_attention_rope_append_varlen, flash_attention_rope_append_varlen_paged)
+               flash_attention_rope_append_varlen, flash_attention_rope_append_varlen_paged,
+               flash_attention_varlen)
 
 OP_NAME = "fa_mi355x::fwd"
 
@@ -620,3 +624,65 @@ rope_append = torch.ops.fa_mi355x.rope_append
 rope_append_paged = torch.ops.fa_mi355x.rope_append_paged
 rope_append_varlen = torch.ops.fa_mi355x.rope_append_varlen
 rope_append_varlen_paged = torch.ops.fa_mi355x.rope_append_varlen_paged
+
+# Attention over token-major Q, K and V with no cache: attn_varlen(q [T_q,Hq,D],
+# k / v [T_k,Hkv,D], cu_seqlens_q int32 [B + 1], cu_seqlens_k or None = self-
+# attention) and attn_bshd(q [B,Sq,Hq,D], k / v [B,Sk,Hkv,D]):
+# fa_mi355x.flash_attention_varlen / flash_attention_bshd behind the prefill
+# kind of registration, each with a `.window` overload (then `int window`) and
+# a `.sinks` overload (then `Tensor? sinks`), registered in that order so that
+# every call an earlier overload accepts still resolves there.  q, k and v are
+# taken as they are -- a token-major view (the slices of a fused QKV buffer) is
+# read in place and any other layout raises, nothing is copied; rows of the
+# returned tensor that belong to no sequence are unspecified.
+
+
+def _attn_op(name, fn, head, rank):
+    """Registers fa_mi355x::<name> and its .window / .sinks overloads.  head: the
+    schema's arguments before `causal`, which are `fn`'s first positionals."""
+    names = [a.split()[-1].split("=")[0] for a in head]
+    layout = "[T, H, 64|128]" if rank == 3 else "[B, S, H, 64|128]"
+
+    def fake(*args, **kw):
+        vals = dict(zip(names + ["causal", "window", "sinks"], args))
+        vals.update(kw)
+        q, k, v = vals["q"], vals["k"], vals["v"]
+        _no_grad_needed(q, k, v)
+        torch._check(q.dim() == rank and q.shape[-1] in (64, 128), lambda: "expected q " + layout)
+        torch._check(k.dim() == rank and v.dim() == rank, lambda: "expected k, v " + layout)
+        torch._check(q.dtype in (torch.float16, torch.bfloat16), lambda: "expected fp16 or bf16")
+        if rank == 3:
+            torch._check(vals["cu_seqlens_q"].dim() == 1, lambda: "expected a [B + 1] cu_seqlens_q")
+        torch._check(vals.get("window", 0) >= 0, lambda: "expected window >= 0")
+        sinks = vals.get("sinks")
+        torch._check(sinks is None or sinks.dim() == 1, lambda: "expected a [Hq] sinks")
+        return torch.empty(q.shape, dtype=q.dtype, device=q.device)
+
+    def gpu(*args, **kw):
+        vals = dict(zip(names + ["causal", "window", "sinks"], args))
+        vals.update(kw)
+        _no_grad_needed(vals["q"], vals["k"], vals["v"])
+        for n in ("cu_seqlens_q", "cu_seqlens_k", "sinks"):
+            if isinstance(vals.get(n), torch.Tensor):
+                vals[n] = vals[n].contiguous()
+        return fn(**vals)
+
+    def cpu(*args, **kw):
+        raise ValueError("fa_mi355x::%s needs GPU tensors (no CPU path)" % name)
+
+    for overload, tail in (("", []), (".window", ["int window=0"]),
+                           (".sinks", ["int window=0", "Tensor? sinks=None"])):
+        full = name + overload
+        _LIB.define("%s(%s) -> Tensor" % (full, ", ".join(head + ["bool causal=False"] + tail)))
+        _LIB.impl(full, gpu, "CUDA")
+        _LIB.impl(full, torch.library.fallthrough_kernel, "Autograd")
+        _LIB.impl(full, cpu, "CPU")
+        torch.library.register_fake("fa_mi355x::" + full, fake, lib=_LIB)
+
+
+_attn_op("attn_varlen", flash_attention_varlen,
+         ["Tensor q", "Tensor k", "Tensor v", "Tensor cu_seqlens_q", "Tensor? cu_seqlens_k=None"], 3)
+_attn_op("attn_bshd", flash_attention_bshd, ["Tensor q", "Tensor k", "Tensor v"], 4)
+
+attn_varlen = torch.ops.fa_mi355x.attn_varlen
+attn_bshd = torch.ops.fa_mi355x.attn_bshd

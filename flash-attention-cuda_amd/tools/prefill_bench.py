@@ -52,6 +52,23 @@ the windowed kernel at W = capacity), base / sinks / base: sink_over_base beside
 base_aa.
 
     timeout 300 python3 tools/prefill_bench.py --shape s32k --window 4096 --sinks [--out profiles/prefill_sinks_bench.jsonl]
+
+--selfattn NAME (instead of --shape): flash_attention_varlen, attention over
+token-major Q, K and V with no cache, at D = 128, Hq = 32, Hkv = 8 on `uniform`
+(8 prompts of 4096 tokens, causal), `ragged` (the --varlen batch, causal) or
+`vit` (a non-causal packed batch of ViT-like lengths), alternated the same way:
+
+  new       the entry on dense [T, H, D] tensors;
+  (a) append_prefill   what a caller did before it: cache_append_varlen into a
+            scratch contiguous cache (from torch's caching allocator inside the
+            arm), then prefill_varlen on it;
+  (b) prefill   prefill_varlen alone on a cache filled beforehand: the same K/V
+            bytes through contiguous rows;
+  fused     the entry on Q, K and V as the head slices of one [T, Hq + 2 Hkv, D]
+            buffer, read in place (the rows a runtime stride apart);
+  new2      `new` again: new_aa is the spread of the box.
+
+    timeout 300 python3 tools/prefill_bench.py --selfattn ragged [--out profiles/prefill_selfattn_bench.jsonl]
 """
 import argparse
 import json
@@ -417,10 +434,75 @@ def run_varlen(name, dt, form, rounds, iters):
     return rec
 
 
+SELFATTN = ("uniform", "ragged", "vit")
+
+
+def selfattn_lengths(name):
+    """(n_b, causal) of the --selfattn batches."""
+    if name == "vit":
+        # images of 14-pixel patches at mixed resolutions, each with a class token
+        sides = [(16, 16), (24, 24), (32, 32), (27, 36), (37, 37), (18, 52), (64, 48), (32, 24)] * 4
+        return [h * w + 1 for h, w in sides], False
+    return varlen_lengths(name)[0], True
+
+
+def run_selfattn(name, dt, rounds, iters):
+    n, causal = selfattn_lengths(name)
+    b, hq, hkv, d = len(n), 32, 8, 128
+    total, cap = sum(n), -(-max(n) // 64) * 64
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    fused = ((torch.rand((total, hq + 2 * hkv, d), generator=gen, device="cuda", dtype=torch.float32) * 2 - 1)
+             .to(dt))
+    fq, fk, fv = fused[:, :hq], fused[:, hq:hq + hkv], fused[:, hq + hkv:]
+    q, k, v = fq.contiguous(), fk.contiguous(), fv.contiguous()
+    cu = torch.tensor([0] + [sum(n[:i + 1]) for i in range(b)], dtype=torch.int32, device="cuda")
+    kv_lens = torch.tensor(n, dtype=torch.int32, device="cuda")
+    kc = torch.zeros((b, hkv, cap, d), dtype=dt, device="cuda")
+    vc = torch.zeros_like(kc)
+    fa_mi355x.flash_attention_cache_append_varlen(k, v, kc, vc, cu, kv_lens)
+    outs = [torch.empty_like(q) for _ in range(4)]
+
+    def new():
+        return fa_mi355x.flash_attention_varlen(q, k, v, cu, causal=causal, out=outs[0])
+
+    def append_prefill():
+        k2 = torch.empty((b, hkv, cap, d), dtype=dt, device="cuda")
+        v2 = torch.empty_like(k2)
+        fa_mi355x.flash_attention_cache_append_varlen(k, v, k2, v2, cu, kv_lens)
+        return fa_mi355x.flash_attention_prefill_varlen(q, k2, v2, cu, kv_lens, causal=causal, out=outs[1])
+
+    def prefill():
+        return fa_mi355x.flash_attention_prefill_varlen(q, kc, vc, cu, kv_lens, causal=causal, out=outs[2])
+
+    def fused_views():
+        return fa_mi355x.flash_attention_varlen(fq, fk, fv, cu, causal=causal, out=outs[3])
+
+    same = bool(torch.equal(new(), append_prefill()) and torch.equal(outs[0], prefill())
+                and torch.equal(outs[0], fused_views()))
+    names = ("new", "append_prefill", "prefill", "fused", "new2")
+    ts = time_arms([new, append_prefill, prefill, fused_views, new], iters, rounds)
+    fl = 4.0 * hq * d * sum(x * (x + 1) // 2 if causal else x * x for x in n)
+    rec = dict(selfattn=name, dtype=str(dt).split(".")[-1], causal=causal, batch=b, heads_q=hq, heads_kv=hkv,
+               head_dim=d, total=total, max_n=max(n), scratch_cache_bytes=2 * b * hkv * cap * d * 2,
+               rounds=rounds, iters=iters, bit_identical=same)
+    for arm, (med, lo, hi) in zip(names, ts):
+        rec[arm + "_ms"] = round(med, 4)
+        rec[arm + "_min_ms"] = round(lo, 4)
+        rec[arm + "_max_ms"] = round(hi, 4)
+    rec["new_tflops"] = round(fl / (ts[0][0] * 1e-3) / 1e12, 1)
+    rec["new_over_append_prefill"] = round(ts[0][0] / ts[1][0], 4)
+    rec["new_over_prefill"] = round(ts[0][0] / ts[2][0], 4)
+    rec["fused_over_prefill"] = round(ts[3][0] / ts[2][0], 4)
+    rec["new_aa"] = round(ts[4][0] / ts[0][0], 4)
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shape", choices=sorted(SHAPES))
     ap.add_argument("--varlen", choices=VARLEN, help="a packed ragged batch instead of --shape")
+    ap.add_argument("--selfattn", choices=SELFATTN,
+                    help="attention over token-major Q, K, V with no cache instead of --shape")
     ap.add_argument("--dtype", choices=("fp16", "bf16"), default="fp16")
     ap.add_argument("--forms", default=",".join(FORMS))
     ap.add_argument("--window", type=int, default=0,
@@ -434,17 +516,24 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("prefill_bench.py needs a GPU")
-    if (args.shape is None) == (args.varlen is None):
-        ap.error("one of --shape and --varlen is required")
+    if (args.shape is not None) + (args.varlen is not None) + (args.selfattn is not None) != 1:
+        ap.error("one of --shape, --varlen and --selfattn is required")
     if args.out is None:
         args.out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "profiles",
                                 "prefill_varlen_bench.jsonl" if args.varlen else
+                                "prefill_selfattn_bench.jsonl" if args.selfattn else
                                 "prefill_sinks_bench.jsonl" if args.sinks else
                                 "prefill_window_bench.jsonl" if args.window else "prefill_bench.jsonl")
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     dt = torch.bfloat16 if args.dtype == "bf16" else torch.float16
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     with open(args.out, "a") as f:
+        if args.selfattn:
+            rec = run_selfattn(args.selfattn, dt, args.rounds, args.iters)
+            rec["cus"] = cus
+            f.write(json.dumps(rec) + "\n")
+            print(json.dumps(rec), flush=True)
+            return
         for form in args.forms.split(","):
             assert form in FORMS, form
             if args.varlen:

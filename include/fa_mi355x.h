@@ -1069,6 +1069,94 @@ int fa_prefill_varlen_sink_paged_kv8_bf16(const void* q, const void* k_pages, co
                                           int window, const float* sinks, void* hip_stream,
                                           const float* k_scale, const float* v_scale);
 
+/* Attention over token-major Q, K and V with NO cache (flash-attn's
+ * flash_attn_varlen_func / flash_attn_func): what a QKV projection leaves,
+ * taken as it is -- an encoder, a vision tower, an embedding model, a first
+ * prefill whose keys are not cached yet.  The prefill kernels over a fifth K/V
+ * source.
+ *
+ *   q      [total_q][heads_q][head_dim]   16-bit, token-major
+ *   k, v   [total_k][heads_kv][head_dim]  the same type, heads_q % heads_kv == 0
+ *   o      [total_q][heads_q][head_dim]   dense
+ *   lse    optional fp32 [heads_q][total_q], natural log; may be NULL
+ *   q_stride, k_stride, v_stride: ELEMENTS between consecutive tokens of q, k
+ *     and v; 0 = dense (heads * head_dim).  Heads are head_dim apart and the
+ *     last dimension is contiguous, so the three may be the slices of one
+ *     fused QKV buffer, read in place.  A stride must be a multiple of 8 (16-
+ *     byte loads), not shorter than heads * head_dim, and the byte range of one
+ *     block's rows (127 * stride * 2 + 2 head_dim for q, 63 * stride * 2 + 2
+ *     head_dim for k and v) must fit a 32-bit int.  o and q must not overlap.
+ *   cu_seqlens_q, cu_seqlens_k: device int32 [batch + 1], read and clamped on
+ *     the device by the rule of the fa_prefill_varlen_* entries:
+ *       (sq_b, nq_b) = the span of cu_seqlens_q clamped to [0, total_q]
+ *       (sk_b, nk_b) = the span of cu_seqlens_k clamped to [0, total_k]
+ *     cu_seqlens_k == NULL: self-attention, the keys' spans are the spans of
+ *     cu_seqlens_q (clamped to [0, total_k]).  Both NULL: uniform lengths,
+ *     sq_b = b * seqlen_q and sk_b = b * seqlen_k with total_q = batch *
+ *     seqlen_q and total_k = batch * seqlen_k -- the [B][S][H][D] layout; no
+ *     array is read.  seqlen_q and seqlen_k are looked at in that mode only.
+ *
+ * Row t of sequence b (o row sq_b + t) sees keys [lo, vis) of b, with off_b =
+ * nk_b - nq_b: vis = causal ? clamp(off_b + t + 1, 0, nk_b) : nk_b (bottom-
+ * right aligned), lo = 0 -- fa_prefill_varlen_*'s formulas with len_b = nk_b,
+ * and its bits: o and lse equal fa_prefill_varlen_* on a contiguous cache
+ * whose rows [0, nk_b) of element b are the same keys, bit for bit.  A row
+ * that sees no key gives zeros and lse = -inf.  Rows of o and lse that belong
+ * to no sequence are not written; rows of k and v that belong to no sequence,
+ * or lie past a row block's range, are never read.  Any contents of the two
+ * arrays are memory-safe (if they do not increase the result is unspecified).
+ * No sync, no workspace, graph-capturable; a captured graph follows the arrays.
+ * Tensors may exceed 4 GiB; total_k <= INT_MAX - 64.
+ *
+ * Statuses, all before any launch and in this order: negative batch, heads,
+ * total_k, head_dim (or window) FA_ERR_BAD_SHAPE; head_dim not 64 / 128
+ * FA_ERR_UNSUPPORTED_HEAD_DIM; negative total_q, window > 0 without causal, a
+ * stride that is negative, no multiple of 8 or past the byte range,
+ * cu_seqlens_k without cu_seqlens_q, uniform mode with a negative seqlen or
+ * total != batch * seqlen FA_ERR_BAD_SHAPE; batch, heads_q or total_q == 0
+ * FA_OK; heads_q % heads_kv != 0, a stride shorter than its heads * head_dim,
+ * heads_q * total_q > INT_MAX, total_k > INT_MAX - 64 FA_ERR_BAD_SHAPE;
+ * total_k == 0: o = 0 and lse = -inf (or the sink) for ALL total_q rows (o
+ * NULL: FA_ERR_NULL_POINTER); NULL q, k, v or o FA_ERR_NULL_POINTER.
+ *
+ * _win: `int window` after `causal`, the sliding window of the _win entries
+ * above (W = 0: none, the plain entry's bits; W > 0 needs causal): lo =
+ * max(0, off_b + t - W + 1).  _sink: `const float* sinks` last, the attention
+ * sinks of the _sink entries above (float32 [heads_q]; NULL or -inf: the _win
+ * entry's bits; a row with no key gives lse = sinks[h]). */
+int fa_attn_varlen_f16(const void* q, const void* k, const void* v, void* o, float* lse,
+                       int batch, int heads_q, int heads_kv, int total_q, int total_k, int head_dim,
+                       long long q_stride, long long k_stride, long long v_stride,
+                       const int* cu_seqlens_q, const int* cu_seqlens_k, int seqlen_q, int seqlen_k,
+                       int causal, void* hip_stream);
+int fa_attn_varlen_bf16(const void* q, const void* k, const void* v, void* o, float* lse,
+                        int batch, int heads_q, int heads_kv, int total_q, int total_k, int head_dim,
+                        long long q_stride, long long k_stride, long long v_stride,
+                        const int* cu_seqlens_q, const int* cu_seqlens_k, int seqlen_q, int seqlen_k,
+                        int causal, void* hip_stream);
+int fa_attn_varlen_win_f16(const void* q, const void* k, const void* v, void* o, float* lse,
+                           int batch, int heads_q, int heads_kv, int total_q, int total_k,
+                           int head_dim, long long q_stride, long long k_stride, long long v_stride,
+                           const int* cu_seqlens_q, const int* cu_seqlens_k, int seqlen_q,
+                           int seqlen_k, int causal, int window, void* hip_stream);
+int fa_attn_varlen_win_bf16(const void* q, const void* k, const void* v, void* o, float* lse,
+                            int batch, int heads_q, int heads_kv, int total_q, int total_k,
+                            int head_dim, long long q_stride, long long k_stride, long long v_stride,
+                            const int* cu_seqlens_q, const int* cu_seqlens_k, int seqlen_q,
+                            int seqlen_k, int causal, int window, void* hip_stream);
+int fa_attn_varlen_sink_f16(const void* q, const void* k, const void* v, void* o, float* lse,
+                            int batch, int heads_q, int heads_kv, int total_q, int total_k,
+                            int head_dim, long long q_stride, long long k_stride, long long v_stride,
+                            const int* cu_seqlens_q, const int* cu_seqlens_k, int seqlen_q,
+                            int seqlen_k, int causal, int window, void* hip_stream,
+                            const float* sinks);
+int fa_attn_varlen_sink_bf16(const void* q, const void* k, const void* v, void* o, float* lse,
+                             int batch, int heads_q, int heads_kv, int total_q, int total_k,
+                             int head_dim, long long q_stride, long long k_stride, long long v_stride,
+                             const int* cu_seqlens_q, const int* cu_seqlens_k, int seqlen_q,
+                             int seqlen_k, int causal, int window, void* hip_stream,
+                             const float* sinks);
+
 /* The dispatcher's decision (ref tier table :620-661): config id used by
  * fa_fwd_f16 for this shape.  The _ws entries may run the causal split tier
  * instead: check fa_fwd_split_pieces() first (> 0: the split tier runs with
