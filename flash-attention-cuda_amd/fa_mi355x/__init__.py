@@ -156,6 +156,8 @@ EXPORTED_SYMBOLS = (
     "fa_attn_varlen_win_bf16",
     "fa_attn_varlen_sink_f16",
     "fa_attn_varlen_sink_bf16",
+    "fa_attn_varlen_bwd_f16",
+    "fa_attn_varlen_bwd_bf16",
     "fa_select_config",
     "fa_num_configs",
     "fa_config_info",
@@ -331,6 +333,10 @@ def load_library() -> ctypes.CDLL:
             fn = getattr(lib, "fa_attn_varlen" + variant + ty)
             fn.argtypes = head + mid + [vp] + last
             fn.restype = i
+        # the backward: dout, q, k, v, out, lse, dq, dk, dv, delta, then four strides
+        fn = getattr(lib, "fa_attn_varlen_bwd" + ty)
+        fn.argtypes = [vp] * 10 + [i, i, i, i, i, i, ll, ll, ll, ll, vp, vp, i, i, i, vp]
+        fn.restype = i
     lib.fa_decode_num_splits.argtypes = [i, i, i, i, i, i]
     lib.fa_decode_num_splits.restype = i
     lib.fa_decode_ws_bytes.argtypes = [i, i, i, i, i, i, i]
@@ -1558,6 +1564,136 @@ def flash_attention_bshd(q, k, v, causal: bool = False, out=None, return_lse: bo
     _attn_call(q, k, v, out, strides, b, b * sq, b * sk, None, None, sq, sk, causal, lse, stream, window,
                sinks)
     return (out, lse.view(hq, b, sq).permute(1, 0, 2)) if return_lse else out
+
+
+def _check_attn_bwd(dout, q, k, v, out, lse, rank, cu_q, cu_k, dq, dk, dv):
+    """What the two backward functions check on top of _check_attn (which sees
+    q, k, v and the forward's out): dout under q's stride rule, the LSE's
+    layout, and the three gradients (allocated when None).  Returns the four
+    token strides (dout's first) and dq, dk, dv."""
+    import torch
+
+    # dout, lse and the gradients before _check_attn, whose last checks are where
+    # the tensors live: shapes and layouts are refused whatever the device (a
+    # malformed q is _check_attn's to name)
+    grads, do_stride = [], 0
+    if q.dim() == rank and q.dtype in (torch.float16, torch.bfloat16):
+        layout = "[T,H,D]" if rank == 3 else "[B,S,H,D]"
+        if dout.dtype != q.dtype or dout.dim() != rank or dout.shape != q.shape:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"dout must be a {q.dtype} {layout} tensor like q")
+        do_stride = _token_stride(dout, "dout", rank)
+        hq = q.shape[-2]
+        if not isinstance(lse, torch.Tensor) or lse.dtype != torch.float32:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, "lse must be the forward's float32 lse")
+        if rank == 3:
+            want, want_st = (hq, q.shape[0]), (q.shape[0], 1)
+        else:
+            b, sq = q.shape[0], q.shape[1]
+            want, want_st = (b, hq, sq), (sq, b * sq, 1)
+        if tuple(lse.shape) != want or (lse.numel() > 0 and any(
+                n > 1 and st != w for n, st, w in zip(want, lse.stride(), want_st))):
+            raise FlashAttentionError(
+                FA_ERR_BAD_SHAPE,
+                "lse must be the forward's lse: " + ("a contiguous [Hq, T_q] tensor" if rank == 3 else
+                                                     "the [B, Hq, Sq] view of a [Hq, B * Sq] buffer")
+                + f", got {list(lse.shape)} with strides {tuple(lse.stride())}")
+        grads = []
+        for name, t, like in (("dq", dq, q), ("dk", dk, k), ("dv", dv, v)):
+            if t is None:
+                t = torch.empty(like.shape, dtype=q.dtype, device=q.device)
+            elif t.dtype != q.dtype or t.shape != like.shape or not t.is_contiguous():
+                raise FlashAttentionError(FA_ERR_BAD_SHAPE,
+                                          f"{name} must be a contiguous {q.dtype} tensor shaped like {name[1]}")
+            grads.append(t)
+    strides = _check_attn(q, k, v, out, rank, cu_q, cu_k, None)
+    for name, t in (("dout", dout), ("lse", lse), ("dq", grads[0]), ("dk", grads[1]), ("dv", grads[2])):
+        if not t.is_cuda:
+            raise FlashAttentionError(FA_ERR_NULL_POINTER, f"{name} must be a device tensor")
+        if t.device != q.device:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE,
+                                      f"{name} is on {t.device}, q on {q.device}: one device only")
+    return (do_stride,) + strides, grads
+
+
+def _attn_bwd_call(dout, q, k, v, out, lse, grads, strides, batch, total_q, total_k, cu_q, cu_k, seqlen_q,
+                   seqlen_k, causal, stream):
+    """The call of the two functions below after their checks: delta (the only
+    workspace), the stream and the fa_attn_varlen_bwd_* entry of q's dtype."""
+    import torch
+
+    name = "fa_attn_varlen_bwd" + ("_bf16" if q.dtype is torch.bfloat16 else "_f16")
+    dev = q.device.index
+    delta = torch.empty((q.shape[-2], total_q), dtype=torch.float32, device=q.device)
+    if stream is None:
+        st = torch._C._cuda_getCurrentRawStream(dev)
+    else:
+        st = stream if isinstance(stream, int) else stream.cuda_stream
+    lib = _lib or load_library()
+    dq, dk, dv = grads
+    with torch.cuda.device(dev):
+        rc = getattr(lib, name)(dout.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
+                                lse.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
+                                delta.data_ptr(), batch, q.shape[-2], k.shape[-2], total_q, total_k,
+                                q.shape[-1], *strides,
+                                cu_q.data_ptr() if cu_q is not None else None,
+                                cu_k.data_ptr() if cu_k is not None else None, seqlen_q, seqlen_k,
+                                int(bool(causal)), st)
+    _check(rc)
+
+
+def flash_attention_varlen_backward(dout, q, k, v, out, lse, cu_seqlens_q, cu_seqlens_k=None,
+                                    causal: bool = False, dq=None, dk=None, dv=None, stream=None):
+    """Backward pass of :func:`flash_attention_varlen` (fa_attn_varlen_bwd_f16 /
+    _bf16): the gradients of q, k and v from ``dout`` [T_q, Hq, D], the
+    forward's inputs as it took them (views included), its ``out`` and its
+    ``lse`` (return_lse=True: fp32 [Hq, T_q]).  dout follows q's stride rule and
+    is never copied; anything that would need a copy raises.  GQA: dk and dv
+    of a K/V head sum over its query heads, in fp32.  A row that saw no key
+    gets dq = 0; a key no row sees gets dk = dv = 0; rows that belong to no
+    sequence are neither read nor written (unspecified when the gradients are
+    allocated here).  dq, dk, dv: contiguous tensors shaped like q, k, v, or
+    None to allocate.  Returns (dq, dk, dv).  Three launches, no sync, one fp32
+    [Hq, T_q] workspace allocated here, graph-capturable, and bit-reproducible:
+    no atomics, no sum across workgroups.  window / sinks have no backward."""
+    strides, grads = _check_attn_bwd(dout, q, k, v, out, lse, 3, cu_seqlens_q, cu_seqlens_k, dq, dk, dv)
+    _attn_bwd_call(dout, q, k, v, out, lse, grads, strides, cu_seqlens_q.shape[0] - 1, q.shape[0],
+                   k.shape[0], cu_seqlens_q, cu_seqlens_k, 0, 0, causal, stream)
+    return tuple(grads)
+
+
+def flash_attention_bshd_backward(dout, q, k, v, out, lse, causal: bool = False, dq=None, dk=None, dv=None,
+                                  stream=None):
+    """:func:`flash_attention_varlen_backward` for uniform lengths, the backward
+    of :func:`flash_attention_bshd`: dout and q [B, Sq, Hq, D], k and v [B, Sk,
+    Hkv, D], ``lse`` the [B, Hq, Sq] view that function returned (that view of
+    a [Hq, B * Sq] buffer and no other layout).  Equals the packed function on
+    cu_seqlens = arange(B + 1) * S bit for bit.  Returns (dq, dk, dv)."""
+    strides, grads = _check_attn_bwd(dout, q, k, v, out, lse, 4, None, None, dq, dk, dv)
+    b, sq = q.shape[0], q.shape[1]
+    sk = k.shape[1]
+    _attn_bwd_call(dout, q, k, v, out, lse, grads, strides, b, b * sq, b * sk, None, None, sq, sk, causal,
+                   stream)
+    return tuple(grads)
+
+
+def flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k=None, causal: bool = False):
+    """DIFFERENTIABLE attention over packed token-major q [T_q, Hq, D], k and v
+    [T_k, Hkv, D], named as in flash-attn: :func:`flash_attention_varlen`
+    forward, :func:`flash_attention_varlen_backward` under torch.autograd
+    (fa_mi355x.torch_op, imported on first use).  Views as for the forward; a
+    dout that fails the stride rule is made contiguous in backward (the one
+    copy).  No window, no sinks, no dropout."""
+    from . import torch_op
+
+    return torch_op.flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, causal)
+
+
+def flash_attn_func(q, k, v, causal: bool = False):
+    """:func:`flash_attn_varlen_func` for uniform lengths: q [B, Sq, Hq, D], k and
+    v [B, Sk, Hkv, D] (:func:`flash_attention_bshd` and its backward)."""
+    from . import torch_op
+
+    return torch_op.flash_attn_func(q, k, v, causal)
 
 
 def _append_varlen(k_new, v_new, k, v, block_table, names, cu_seqlens, kv_lens, k_scale, v_scale, stream):

@@ -18,6 +18,8 @@ rank 3: the wrapper that puts the kernel beside PyTorch SDPA on one box).
     (and rope_append_paged, rope_append_varlen, rope_append_varlen_paged)
     o = torch.ops.fa_mi355x.attn_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, causal=False)  # [T,H,D], no cache
     o = torch.ops.fa_mi355x.attn_bshd(q, k, v, causal=True)  # [B,S,H,D], no cache
+    dq, dk, dv = torch.ops.fa_mi355x.attn_varlen_bwd(dout, q, k, v, out, lse, cu_seqlens_q, cu_seqlens_k)
+    o = fa_mi355x.flash_attn_varlen_func(q, k, v, cu_seqlens_q)  # differentiable (torch.autograd)
 
 ``q, k, v``: fp16 or bf16 ``[B, H, S, D]`` (D = 128 or 64) tensors on the GPU (BHSD, the
 reference layout, flash_attention.cu:119-122); returns a new tensor of the same shape and dtype.
@@ -31,7 +33,10 @@ same C ABI as every other entry point; there is no CPU or eager fallback (a
 CPU tensor raises ValueError).  Forward only: the Autograd key falls through
 (no Python frame on the call path) and the GPU and fake kernels raise when a
 gradient would be needed (q, k or v requiring grad with grad mode on)
-instead of returning an output that backward would silently ignore.
+instead of returning an output that backward would silently ignore.  The
+exception is the attention with no cache: flash_attn_varlen_func and
+flash_attn_func at the end of this module are torch.autograd.Functions over
+the attn_varlen_fwd / attn_varlen_bwd (attn_bshd_fwd / attn_bshd_bwd) ops.
 """
 from __future__ import annotations
 
@@ -39,13 +44,14 @@ import torch
 
 from . import (flash_attention_cache_append, flash_attention_cache_append_paged,
                flash_attention_cache_append_varlen, flash_attention_cache_append_varlen_paged,
-               flash_attention_bshd, flash_attention_decode, flash_attention_decode_paged,
+               flash_attention_bshd, flash_attention_bshd_backward, flash_attention_decode, flash_attention_decode_paged,
                flash_attention_fwd,
                flash_attention_prefill, flash_attention_prefill_paged,
                flash_attention_prefill_varlen, flash_attention_prefill_varlen_paged,
                flash_attention_rope_append, flash_attention_rope_append_paged,
                flash_attention_rope_append_varlen, flash_attention_rope_append_varlen_paged,
-               flash_attention_varlen)
+               flash_attention_varlen, flash_attention_varlen_backward)
+from . import FlashAttentionError, _token_stride
 
 OP_NAME = "fa_mi355x::fwd"
 
@@ -686,3 +692,143 @@ _attn_op("attn_bshd", flash_attention_bshd, ["Tensor q", "Tensor k", "Tensor v"]
 
 attn_varlen = torch.ops.fa_mi355x.attn_varlen
 attn_bshd = torch.ops.fa_mi355x.attn_bshd
+
+# The backward pass of those two and the differentiable functions over it.
+# attn_varlen_fwd / attn_bshd_fwd return (out, lse) -- the forward with
+# return_lse=True as an op, so that it has a fake implementation; attn_varlen_bwd
+# / attn_bshd_bwd(dout, q, k, v, out, lse, ...) return (dq, dk, dv):
+# fa_mi355x.flash_attention_varlen_backward / flash_attention_bshd_backward.
+# Everything is taken as it is (views under the stride rule, nothing copied).
+# attn_varlen / attn_bshd above stay forward-only and keep raising on inputs
+# that require grad; the differentiable entry points are flash_attn_varlen_func
+# and flash_attn_func below.
+
+
+def _attn_grad_ops(name, fwd_fn, bwd_fn, mid, rank):
+    """Registers fa_mi355x::<name>_fwd and <name>_bwd.  mid: the schema's
+    arguments between v (forward) / lse (backward) and `causal`."""
+    mid_names = [a.split()[-1].split("=")[0] for a in mid]
+    layout = "[T, H, 64|128]" if rank == 3 else "[B, S, H, 64|128]"
+    fwd_names = ["q", "k", "v"] + mid_names + ["causal"]
+    bwd_names = ["dout", "q", "k", "v", "out", "lse"] + mid_names + ["causal"]
+
+    def check(q, k, v, vals):
+        torch._check(q.dim() == rank and q.shape[-1] in (64, 128), lambda: "expected q " + layout)
+        torch._check(k.dim() == rank and v.dim() == rank and k.shape == v.shape,
+                     lambda: "expected k, v " + layout)
+        torch._check(q.dtype in (torch.float16, torch.bfloat16), lambda: "expected fp16 or bf16")
+        if rank == 3:
+            torch._check(vals["cu_seqlens_q"].dim() == 1, lambda: "expected a [B + 1] cu_seqlens_q")
+
+    def bind(names, args, kw):
+        vals = dict(zip(names, args))
+        vals.update(kw)
+        for n in mid_names:
+            if isinstance(vals.get(n), torch.Tensor):
+                vals[n] = vals[n].contiguous()
+        return vals
+
+    def new_lse(q):
+        if rank == 3:
+            return torch.empty((q.shape[1], q.shape[0]), dtype=torch.float32, device=q.device)
+        b, sq, hq = q.shape[0], q.shape[1], q.shape[2]
+        return torch.empty((hq, b * sq), dtype=torch.float32, device=q.device).view(hq, b, sq).permute(1, 0, 2)
+
+    def fwd_gpu(*args, **kw):
+        out, lse = fwd_fn(**bind(fwd_names, args, kw), return_lse=True)
+        return out, lse
+
+    def fwd_fake(*args, **kw):
+        vals = bind(fwd_names, args, kw)
+        q = vals["q"]
+        check(q, vals["k"], vals["v"], vals)
+        return torch.empty(q.shape, dtype=q.dtype, device=q.device), new_lse(q)
+
+    def bwd_gpu(*args, **kw):
+        return bwd_fn(**bind(bwd_names, args, kw))
+
+    def bwd_fake(*args, **kw):
+        vals = bind(bwd_names, args, kw)
+        q, k, v = vals["q"], vals["k"], vals["v"]
+        check(q, k, v, vals)
+        torch._check(vals["dout"].shape == q.shape and vals["out"].shape == q.shape,
+                     lambda: "expected dout and out shaped like q")
+        torch._check(vals["lse"].dtype == torch.float32 and vals["lse"].shape == new_lse(q).shape,
+                     lambda: "expected the forward's float32 lse")
+        return tuple(torch.empty(t.shape, dtype=q.dtype, device=q.device) for t in (q, k, v))
+
+    def cpu_of(full):
+        def cpu(*args, **kw):
+            raise ValueError("fa_mi355x::%s needs GPU tensors (no CPU path)" % full)
+        return cpu
+
+    tail = ", ".join(mid + ["bool causal=False"])
+    for full, schema, gpu, fake in (
+            (name + "_fwd", "Tensor q, Tensor k, Tensor v, %s) -> (Tensor, Tensor)" % tail, fwd_gpu, fwd_fake),
+            (name + "_bwd", "Tensor dout, Tensor q, Tensor k, Tensor v, Tensor out, Tensor lse, %s) -> "
+                            "(Tensor, Tensor, Tensor)" % tail, bwd_gpu, bwd_fake)):
+        _LIB.define(full + "(" + schema)
+        _LIB.impl(full, gpu, "CUDA")
+        _LIB.impl(full, cpu_of(full), "CPU")
+        torch.library.register_fake("fa_mi355x::" + full, fake, lib=_LIB)
+
+
+_attn_grad_ops("attn_varlen", flash_attention_varlen, flash_attention_varlen_backward,
+               ["Tensor cu_seqlens_q", "Tensor? cu_seqlens_k=None"], 3)
+_attn_grad_ops("attn_bshd", flash_attention_bshd, flash_attention_bshd_backward, [], 4)
+
+attn_varlen_fwd = torch.ops.fa_mi355x.attn_varlen_fwd
+attn_varlen_bwd = torch.ops.fa_mi355x.attn_varlen_bwd
+attn_bshd_fwd = torch.ops.fa_mi355x.attn_bshd_fwd
+attn_bshd_bwd = torch.ops.fa_mi355x.attn_bshd_bwd
+
+
+def _dout_as_given_or_dense(dout, rank):
+    """dout under the stride rule as it is; otherwise contiguous -- the one
+    documented copy of the backward, made here and nowhere below."""
+    try:
+        _token_stride(dout, "dout", rank)
+    except FlashAttentionError:
+        return dout.contiguous()
+    return dout
+
+
+class _FlashAttnVarlen(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, cu_seqlens_q, cu_seqlens_k, causal):
+        out, lse = attn_varlen_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, causal)
+        ctx.save_for_backward(q, k, v, out, lse, cu_seqlens_q, cu_seqlens_k)
+        ctx.causal = causal
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, out, lse, cu_q, cu_k = ctx.saved_tensors
+        dq, dk, dv = attn_varlen_bwd(_dout_as_given_or_dense(dout, 3), q, k, v, out, lse, cu_q, cu_k,
+                                     ctx.causal)
+        return dq, dk, dv, None, None, None
+
+
+class _FlashAttn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, causal):
+        out, lse = attn_bshd_fwd(q, k, v, causal)
+        ctx.save_for_backward(q, k, v, out, lse)
+        ctx.causal = causal
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, out, lse = ctx.saved_tensors
+        dq, dk, dv = attn_bshd_bwd(_dout_as_given_or_dense(dout, 4), q, k, v, out, lse, ctx.causal)
+        return dq, dk, dv, None
+
+
+def flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k=None, causal: bool = False):
+    """Differentiable fa_mi355x.flash_attention_varlen (see fa_mi355x.flash_attn_varlen_func)."""
+    return _FlashAttnVarlen.apply(q, k, v, cu_seqlens_q, cu_seqlens_k, bool(causal))
+
+
+def flash_attn_func(q, k, v, causal: bool = False):
+    """Differentiable fa_mi355x.flash_attention_bshd (see fa_mi355x.flash_attn_func)."""
+    return _FlashAttn.apply(q, k, v, bool(causal))

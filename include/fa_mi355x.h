@@ -1157,6 +1157,55 @@ int fa_attn_varlen_sink_bf16(const void* q, const void* k, const void* v, void* 
                              int seqlen_k, int causal, int window, void* hip_stream,
                              const float* sinks);
 
+/* Backward pass of fa_attn_varlen_f16 / _bf16: dq, dk and dv from dout, the
+ * forward's inputs and its out and lse (csrc/fa_attn_bwd_kernel.hpp, DESIGN.md
+ * §3.0q).  With c = 1 / sqrt(head_dim), s_ij = c q_i . k_j, P_ij = exp(s_ij -
+ * lse_i) on the keys row i sees by the forward's rule (0 elsewhere) and
+ * delta_i = sum_d dout_id out_id:
+ *   dv_j = sum_i P_ij dout_i           dS_ij = P_ij (dout_i . v_j - delta_i)
+ *   dq_i = c sum_j dS_ij k_j           dk_j = c sum_i dS_ij q_i
+ * dk and dv of a K/V head sum over its heads_q / heads_kv query heads.  All
+ * sums are fp32; P and dS are rounded to the 16-bit type once, as matrix
+ * operands, and every output element once.
+ *
+ *   dout: [total_q][heads_q][head_dim], under the stride rule of q (do_stride)
+ *   q, k, v, the strides, cu_seqlens_q / cu_seqlens_k, seqlen_q / seqlen_k,
+ *     causal: as the forward took them (the byte range of a block's rows is
+ *     127 * stride * 2 + 2 head_dim for all four strided tensors here)
+ *   out: the forward's o, dense;  lse: the forward's lse, fp32 [heads_q][total_q]
+ *   dq: [total_q][heads_q][head_dim], dk, dv: [total_k][heads_kv][head_dim],
+ *     dense, of the inputs' type
+ *   delta: fp32 [heads_q][total_q], the only workspace (written, then read)
+ *
+ * A row that sees no key (lse = -inf) gets dq = 0 and adds nothing to dk and
+ * dv; a key of a sequence that no row sees gets dk = dv = 0, written.  Rows of
+ * dq, dk, dv that belong to no sequence are not written, and such rows of
+ * dout, q, k, v, out, lse are never read.  Any contents of the cu arrays are
+ * memory-safe.  Three launches on the stream (delta, dK/dV, dQ), no sync,
+ * nothing read back, graph-capturable, no atomics: two calls on the same
+ * inputs give the same bits.
+ *
+ * Statuses in the forward's order: negative counts, head_dim, the strides
+ * (do_stride with them), the modes as there; heads_q == 0 FA_OK; batch == 0 or
+ * total_q == 0: dk = dv = 0 for all total_k rows (NULL dk or dv with rows to
+ * fill: FA_ERR_NULL_POINTER), FA_OK; then heads_q % heads_kv, a short stride,
+ * heads_q * total_q > INT_MAX, total_k > INT_MAX - 64 FA_ERR_BAD_SHAPE;
+ * total_k == 0: dq = 0 for ALL total_q rows (NULL dq: FA_ERR_NULL_POINTER),
+ * FA_OK; any pointer but the cu arrays NULL (lse and delta included):
+ * FA_ERR_NULL_POINTER. */
+int fa_attn_varlen_bwd_f16(const void* dout, const void* q, const void* k, const void* v,
+                           const void* out, const float* lse, void* dq, void* dk, void* dv, float* delta,
+                           int batch, int heads_q, int heads_kv, int total_q, int total_k, int head_dim,
+                           long long do_stride, long long q_stride, long long k_stride, long long v_stride,
+                           const int* cu_seqlens_q, const int* cu_seqlens_k, int seqlen_q, int seqlen_k,
+                           int causal, void* hip_stream);
+int fa_attn_varlen_bwd_bf16(const void* dout, const void* q, const void* k, const void* v,
+                            const void* out, const float* lse, void* dq, void* dk, void* dv, float* delta,
+                            int batch, int heads_q, int heads_kv, int total_q, int total_k, int head_dim,
+                            long long do_stride, long long q_stride, long long k_stride, long long v_stride,
+                            const int* cu_seqlens_q, const int* cu_seqlens_k, int seqlen_q, int seqlen_k,
+                            int causal, void* hip_stream);
+
 /* The dispatcher's decision (ref tier table :620-661): config id used by
  * fa_fwd_f16 for this shape.  The _ws entries may run the causal split tier
  * instead: check fa_fwd_split_pieces() first (> 0: the split tier runs with
