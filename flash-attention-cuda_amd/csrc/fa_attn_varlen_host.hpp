@@ -1,6 +1,7 @@
 // Host side of the fa_attn_varlen_* entries of include/fa_mi355x.h: attention
 // over token-major Q, K and V with no cache, the sibling of
-// fa_prefill_host.hpp.  One entry body (attn_varlen_entry) over the
+// fa_prefill_host.hpp.  One entry body (attn_varlen_entry, stamped into C
+// entries by FA_ATTN_VARLEN_ENTRIES below) over the
 // PrefillPacked<[Sinked<Windowed<]PrefillTokenKV[>>]> instantiations of
 // fa_prefill_kernel.hpp; prefill_entry's checks in prefill_entry's order, with
 // the strides and the two modes (cu_seqlens / uniform) where the page geometry
@@ -26,12 +27,12 @@ inline bool attn_stride_ok(long long stride, long long dense, int rows, int head
 }
 
 // WIN / SINK: as for prefill_entry (the fa_attn_varlen_win_* / _sink_* entries).
-template <bool WIN = false, bool SINK = false>
+template <bool WIN, bool SINK>
 static int attn_varlen_entry(int dtype, const void* q, const void* k, const void* v, void* o, float* lse,
                              int batch, int heads_q, int heads_kv, int total_q, int total_k,
                              int head_dim, long long q_stride, long long k_stride, long long v_stride,
                              const int* cu_q, const int* cu_k, int seqlen_q, int seqlen_k, int causal,
-                             int window, void* hip_stream, [[maybe_unused]] const float* sinks = nullptr) {
+                             int window, const float* sinks, void* hip_stream) {
   static_assert(WIN || !SINK, "the sink kernels are instantiated over the windowed ones");
   using P = std::conditional_t<SINK, Sinked<Windowed<PrefillTokenKV>>,
                                std::conditional_t<WIN, Windowed<PrefillTokenKV>, PrefillTokenKV>>;
@@ -70,16 +71,9 @@ static int attn_varlen_entry(int dtype, const void* q, const void* k, const void
   const long long nwg = heads_q * nqb;
   if (nqb > 0x7fffffffLL || nwg > 0x7fffffffLL) return FA_ERR_BAD_SHAPE;
   hipStream_t stream = (hipStream_t)hip_stream;
-  if (total_k == 0) {
-    // rows but no keys: O = 0, LSE = -inf (or the sink) for every row
-    if (!o) return FA_ERR_NULL_POINTER;
-    const size_t nrow = (size_t)heads_q * total_q;
-    if constexpr (SINK)
-      return decode_fill_empty_sink<true>(o, lse, sinks, nrow, heads_q, total_q, head_dim, stream)
-                 ? FA_OK
-                 : FA_ERR_HIP;
-    return decode_fill_empty(o, lse, nrow, head_dim, stream) ? FA_OK : FA_ERR_HIP;
-  }
+  if (total_k == 0)
+    return decode_empty_cache<SINK, true>(o, lse, sinks, (size_t)heads_q * total_q, heads_q, total_q,
+                                          head_dim, stream);
   if (!q || !k || !v || !o) return FA_ERR_NULL_POINTER;
   P p = {};
   p.q = q;
@@ -102,14 +96,30 @@ static int attn_varlen_entry(int dtype, const void* q, const void* k, const void
   p.nqb = batch;  // the kernel takes the sequence count here
   p.causal = causal ? 1 : 0;
   p.c = 1.4426950408889634f / sqrtf((float)head_dim);
-  if constexpr (WIN) p.window = window > 0 ? std::min(window, total_k) : total_k;
-  if constexpr (SINK) p.sinks = sinks;
+  decode_set_variant<false, WIN, SINK>(p, total_k, window, sinks, nullptr, nullptr);
   const unsigned grid = (unsigned)nwg;
-  if (dtype == FA_DTYPE_BF16)
-    return head_dim == 128 ? prefill_launch_inst<__bf16, 128, false, false, true>(p, grid, stream)
-                           : prefill_launch_inst<__bf16, 64, false, false, true>(p, grid, stream);
-  return head_dim == 128 ? prefill_launch_inst<f16, 128, false, false, true>(p, grid, stream)
-                         : prefill_launch_inst<f16, 64, false, false, true>(p, grid, stream);
+  return dispatch_elem_dim(dtype, head_dim, [&](auto e) {
+    using E = decltype(e);
+    return prefill_launch_inst<typename E::type, E::hdim, false, false, true>(p, grid, stream);
+  });
 }
 
 }  // namespace fa
+
+// PREFIX_f16 and PREFIX_bf16 of include/fa_mi355x.h, the variant's groups from
+// fa_decode_host.hpp (`sinks` comes last here):
+// FA_ATTN_VARLEN_ENTRIES(fa_attn_varlen_sink, SINK).
+#define FA_ATTN_VARLEN_ENTRY(NAME, DTYPE, VARIANT)                                                  \
+  extern "C" int NAME(const void* q, const void* k, const void* v, void* o, float* lse, int batch,  \
+                      int heads_q, int heads_kv, int total_q, int total_k, int head_dim,            \
+                      long long q_stride, long long k_stride, long long v_stride,                   \
+                      const int* cu_seqlens_q, const int* cu_seqlens_k, int seqlen_q, int seqlen_k, \
+                      int causal FA_##VARIANT##_WINDOW, void* hip_stream FA_##VARIANT##_SINKS) {    \
+    return fa::attn_varlen_entry<FA_##VARIANT##_FLAGS>(                                             \
+        DTYPE, q, k, v, o, lse, batch, heads_q, heads_kv, total_q, total_k, head_dim, q_stride,     \
+        k_stride, v_stride, cu_seqlens_q, cu_seqlens_k, seqlen_q, seqlen_k, causal,                 \
+        FA_##VARIANT##_ARGS, hip_stream);                                                           \
+  }
+#define FA_ATTN_VARLEN_ENTRIES(PREFIX, VARIANT)                 \
+  FA_ATTN_VARLEN_ENTRY(PREFIX##_f16, FA_DTYPE_F16, VARIANT)     \
+  FA_ATTN_VARLEN_ENTRY(PREFIX##_bf16, FA_DTYPE_BF16, VARIANT)

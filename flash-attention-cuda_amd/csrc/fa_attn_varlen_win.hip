@@ -1,24 +1,8 @@
-// fa_attn_varlen_win.hip -- the sliding-window twins of fa_attn_varlen.hip's
-// entries (fa_attn_varlen_win_f16 / _bf16 of include/fa_mi355x.h): the same
-// argument list with `int window` after `causal`, the same entry body
-// (csrc/fa_attn_varlen_host.hpp) with WIN = true, launching the
-// PrefillPacked<Windowed<PrefillTokenKV>> instantiations of
-// csrc/fa_prefill_kernel.hpp.  A unit of its own so that the
-// build stays parallel.
+// fa_attn_varlen_win.hip -- attention over token-major Q, K and V with no
+// cache with a sliding window: fa_attn_varlen_win_f16 / _bf16 of
+// include/fa_mi355x.h, stamped by FA_ATTN_VARLEN_ENTRIES next to the host body
+// in csrc/fa_attn_varlen_host.hpp; the kernel is csrc/fa_prefill_kernel.hpp
+// (DESIGN.md §3.0p).  A unit of its own so that the build stays parallel.
 #include "fa_attn_varlen_host.hpp"
 
-using namespace fa;
-
-#define FA_ATTN_VARLEN_WIN(SUFFIX, DTYPE)                                                             \
-  extern "C" int fa_attn_varlen_win_##SUFFIX(                                                         \
-      const void* q, const void* k, const void* v, void* o, float* lse, int batch, int heads_q,       \
-      int heads_kv, int total_q, int total_k, int head_dim, long long q_stride, long long k_stride,   \
-      long long v_stride, const int* cu_seqlens_q, const int* cu_seqlens_k, int seqlen_q,             \
-      int seqlen_k, int causal, int window, void* hip_stream) {                                       \
-    return attn_varlen_entry<true>(DTYPE, q, k, v, o, lse, batch, heads_q, heads_kv, total_q,         \
-        total_k, head_dim, q_stride, k_stride, v_stride, cu_seqlens_q, cu_seqlens_k, seqlen_q,        \
-        seqlen_k, causal, window, hip_stream);                                                        \
-  }
-FA_ATTN_VARLEN_WIN(f16, FA_DTYPE_F16)
-FA_ATTN_VARLEN_WIN(bf16, FA_DTYPE_BF16)
-#undef FA_ATTN_VARLEN_WIN
+FA_ATTN_VARLEN_ENTRIES(fa_attn_varlen_win, WIN)

@@ -43,11 +43,7 @@ static int append_entry(int dtype, const void* k_new, const void* v_new, void* k
   // token indices (up to the end of a wave's last row) are 32-bit ints in the kernel
   if (seqlen_new < (VARLEN ? 0 : 1) || seqlen_new > 0x7fffffff - 64) return FA_ERR_BAD_SHAPE;
   if constexpr (PAGED) {
-    if (pg.page_size <= 0 || pg.page_size % 64 != 0) return FA_ERR_BAD_SHAPE;
-    if (pg.num_pages <= 0 || pg.max_pages_per_seq < 0) return FA_ERR_BAD_SHAPE;
-    if ((long long)pg.page_size * 2 * head_dim > 0x7fffffffLL) return FA_ERR_BAD_SHAPE;
-    if ((long long)pg.max_pages_per_seq * pg.page_size > 0x7fffffffLL - 64) return FA_ERR_BAD_SHAPE;
-    kv_capacity = pg.max_pages_per_seq * pg.page_size;
+    if (const int st = decode_check_pages(pg, head_dim, &kv_capacity)) return st;
   }
   if (batch == 0 || heads_kv == 0 || (VARLEN && seqlen_new == 0)) return FA_OK;
   if constexpr (!PAGED) {

@@ -1,30 +1,14 @@
-// fa_decode.hip -- the decode-attention entries of include/fa_mi355x.h over a
-// contiguous 16-bit K/V cache (fa_decode_f16 / fa_decode_bf16), plus the split
-// plan and the workspace size that all decode entries share.  The entry body,
-// the launcher, geometry, plan and workspace layout are csrc/fa_decode_host.hpp;
-// the kernel is csrc/fa_decode_kernel.hpp.  It is not a tile config:
-// fa_config_info() does not list it.
+// fa_decode.hip -- decode attention over a contiguous 16-bit K/V cache, plus
+// the split plan and the workspace size that all decode entries share:
+// fa_decode_f16 / _bf16 of include/fa_mi355x.h, stamped by FA_DECODE_ENTRIES
+// next to the host body in csrc/fa_decode_host.hpp; the kernel is
+// csrc/fa_decode_kernel.hpp.  A unit of its own so that the
+// build stays parallel.
 #include "fa_decode_host.hpp"
 
 using namespace fa;
 
-extern "C" int fa_decode_f16(const void* q, const void* k, const void* v, void* o, float* lse,
-                             int batch, int heads_q, int heads_kv, int seqlen_q, int kv_capacity,
-                             int head_dim, const int* kv_lens, int causal, int num_splits,
-                             void* workspace, unsigned long long ws_bytes, void* hip_stream) {
-  return decode_entry<false, false>(FA_DTYPE_F16, q, k, v, o, lse, batch, heads_q, heads_kv, seqlen_q,
-                                    kv_capacity, head_dim, {}, kv_lens, causal, 0, num_splits, workspace,
-                                    ws_bytes, hip_stream, nullptr, nullptr);
-}
-
-extern "C" int fa_decode_bf16(const void* q, const void* k, const void* v, void* o, float* lse,
-                              int batch, int heads_q, int heads_kv, int seqlen_q, int kv_capacity,
-                              int head_dim, const int* kv_lens, int causal, int num_splits,
-                              void* workspace, unsigned long long ws_bytes, void* hip_stream) {
-  return decode_entry<false, false>(FA_DTYPE_BF16, q, k, v, o, lse, batch, heads_q, heads_kv, seqlen_q,
-                                    kv_capacity, head_dim, {}, kv_lens, causal, 0, num_splits, workspace,
-                                    ws_bytes, hip_stream, nullptr, nullptr);
-}
+FA_DECODE_ENTRIES(fa_decode, CONTIG, PLAIN, KV16)
 
 extern "C" int fa_decode_num_splits(int batch, int heads_q, int heads_kv, int seqlen_q,
                                     int kv_capacity, int head_dim) {

@@ -3,7 +3,9 @@
 // block table, fa_decode_kv8.hip and fa_decode_paged_kv8.hip: the same two over
 // FP8 bytes): geometry, split plan and workspace layout, so that all cut a
 // problem the same way and one per-stream workspace serves any of them, then
-// the one entry body (decode_entry) and the one launcher under it.
+// the one entry body (decode_entry) and the one launcher under it, the pieces
+// the other families' entry bodies share with it, and the macro that stamps a
+// unit's C entries from named argument groups (FA_DECODE_ENTRIES).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -161,27 +163,100 @@ struct DecodePages {
   int max_pages_per_seq;
 };
 
-// The body of all eight entries.  PAGED: `k` / `v` are the page pools, `pg`
+// The page-geometry checks of every paged entry (decode, prefill, append and
+// RoPE append alike); on FA_OK *kv_capacity is the logical capacity.
+inline int decode_check_pages(const DecodePages& pg, int head_dim, int* kv_capacity) {
+  // a 64-key tile must not straddle two pages
+  if (pg.page_size <= 0 || pg.page_size % 64 != 0) return FA_ERR_BAD_SHAPE;
+  if (pg.num_pages <= 0 || pg.max_pages_per_seq < 0) return FA_ERR_BAD_SHAPE;
+  // a head's rows of one page are addressed through one buffer resource whose
+  // byte range (page_size * 2 * head_dim) is a 32-bit int.  The FP8 entries
+  // keep the 16-bit bound (their range is half that): both accept the same
+  // page sizes
+  if ((long long)pg.page_size * 2 * head_dim > 0x7fffffffLL) return FA_ERR_BAD_SHAPE;
+  // key indices (up to the end of the last tile) are 32-bit ints in the kernel
+  if ((long long)pg.max_pages_per_seq * pg.page_size > 0x7fffffffLL - 64) return FA_ERR_BAD_SHAPE;
+  *kv_capacity = pg.max_pages_per_seq * pg.page_size;
+  return FA_OK;
+}
+
+// the paged fields the decode and prefill kernels share (decode adds its own)
+template <bool KV8, class Params>
+inline void decode_set_pages(Params& p, const DecodePages& pg, int heads_kv, int head_dim) {
+  p.table = pg.block_table;
+  p.max_pages = pg.max_pages_per_seq;
+  p.num_pages = pg.num_pages;
+  p.tpp = pg.page_size / 64;
+  using CacheElem = std::conditional_t<KV8, unsigned char, f16>;  // f16 and bf16: one size
+  p.head_bytes = (unsigned long long)pg.page_size * sizeof(CacheElem) * head_dim;
+  p.page_bytes = p.head_bytes * heads_kv;
+}
+
+// the fields a variant adds: the window (W = 0, no window, runs as W =
+// capacity, which masks nothing), the sinks and the FP8 scales
+template <bool KV8, bool WIN, bool SINK, class Params>
+inline void decode_set_variant(Params& p, [[maybe_unused]] int kv_capacity, [[maybe_unused]] int window,
+                               [[maybe_unused]] const float* sinks,
+                               [[maybe_unused]] const float* k_scale,
+                               [[maybe_unused]] const float* v_scale) {
+  if constexpr (WIN) p.window = window > 0 ? std::min(window, kv_capacity) : kv_capacity;
+  if constexpr (SINK) p.sinks = sinks;
+  if constexpr (KV8) {
+    p.k_scale = k_scale;
+    p.v_scale = v_scale;
+  }
+}
+
+// rows but no keys, as a status: O = 0, LSE = -inf (SINK: the row's head's
+// sink); nothing else runs.  PACKED: as for decode_fill_empty_sink.
+template <bool SINK, bool PACKED>
+static int decode_empty_cache(void* o, float* lse, [[maybe_unused]] const float* sinks, size_t nrow,
+                              [[maybe_unused]] int heads_q, [[maybe_unused]] int seqlen_q, int head_dim,
+                              hipStream_t stream) {
+  if (!o) return FA_ERR_NULL_POINTER;
+  bool ok;
+  if constexpr (SINK)
+    ok = decode_fill_empty_sink<PACKED>(o, lse, sinks, nrow, heads_q, seqlen_q, head_dim, stream);
+  else
+    ok = decode_fill_empty(o, lse, nrow, head_dim, stream);
+  return ok ? FA_OK : FA_ERR_HIP;
+}
+
+// The element type and head_dim of a launch as a type: launch(ElemDim<T, HDIM>{})
+// for the one of the four that (dtype, head_dim) names (head_dim is 128 or 64).
+template <class T, int HDIM>
+struct ElemDim {
+  using type = T;
+  static constexpr int hdim = HDIM;
+};
+template <class Launch>
+inline int dispatch_elem_dim(int dtype, int head_dim, Launch&& launch) {
+  if (dtype == FA_DTYPE_BF16)
+    return head_dim == 128 ? launch(ElemDim<__bf16, 128>{}) : launch(ElemDim<__bf16, 64>{});
+  return head_dim == 128 ? launch(ElemDim<f16, 128>{}) : launch(ElemDim<f16, 64>{});
+}
+
+// The body of every decode entry.  PAGED: `k` / `v` are the page pools, `pg`
 // describes them and kv_capacity (passed as 0) becomes max_pages_per_seq *
 // page_size; otherwise `pg` is unused.  KV8: the cache holds E4M3 bytes and
 // k_scale / v_scale go to the kernel; otherwise they are unused.  The twelve
 // kernels a <PAGED, KV8> pair can launch are instantiated from here.
-// WIN (the fa_decode_win_* entries, fa_decode_win*.hip): `window` is the
+// WIN (the fa_decode_win_* and fa_decode_sink_* entries): `window` is the
 // sliding window W and the kernels are the Windowed<> instantiations; a
 // negative W is refused with the negative shapes, W > 0 without causal right
 // after the seqlen_q check, W = 0 (no window) runs as W = capacity, which
 // masks nothing, and num_splits = 0 plans from decode_window_capacity().
 // Without WIN `window` is not looked at (the entries pass 0).
-// SINK (the fa_decode_sink_* entries, fa_decode_sink*.hip; with WIN): `sinks`
+// SINK (the fa_decode_sink_* entries; with WIN): `sinks`
 // goes to the Sinked<Windowed<>> instantiations (nullptr: no sinks); the
 // statuses, the plan and the workspace are the windowed twin's.
-template <bool PAGED, bool KV8, bool WIN = false, bool SINK = false>
+template <bool PAGED, bool KV8, bool WIN, bool SINK>
 static int decode_entry(int dtype, const void* q, const void* k, const void* v, void* o, float* lse,
                         int batch, int heads_q, int heads_kv, int seqlen_q, int kv_capacity,
                         int head_dim, const DecodePages& pg, const int* kv_lens, int causal,
-                        int window, int num_splits, void* ws, unsigned long long ws_bytes,
-                        void* hip_stream, const float* k_scale, const float* v_scale,
-                        [[maybe_unused]] const float* sinks = nullptr) {
+                        int window, const float* sinks, int num_splits, void* ws,
+                        unsigned long long ws_bytes, void* hip_stream, const float* k_scale,
+                        const float* v_scale) {
   static_assert(WIN || !SINK, "the sink kernels are instantiated over the windowed ones");
   using P0 = std::conditional_t<PAGED, std::conditional_t<KV8, DecodePagedKv8Params, DecodePagedParams>,
                                 std::conditional_t<KV8, DecodeKv8Params, DecodeParams>>;
@@ -193,17 +268,7 @@ static int decode_entry(int dtype, const void* q, const void* k, const void* v, 
   if (seqlen_q < 1 || seqlen_q > 16) return FA_ERR_BAD_SHAPE;
   if (WIN && window > 0 && !causal) return FA_ERR_BAD_SHAPE;
   if constexpr (PAGED) {
-    // a 64-key tile must not straddle two pages
-    if (pg.page_size <= 0 || pg.page_size % 64 != 0) return FA_ERR_BAD_SHAPE;
-    if (pg.num_pages <= 0 || pg.max_pages_per_seq < 0) return FA_ERR_BAD_SHAPE;
-    // a head's rows of one page are addressed through one buffer resource whose
-    // byte range (page_size * 2 * head_dim) is a 32-bit int.  The FP8 entries
-    // keep the 16-bit bound (their range is half that): both accept the same
-    // page sizes
-    if ((long long)pg.page_size * 2 * head_dim > 0x7fffffffLL) return FA_ERR_BAD_SHAPE;
-    // key indices (up to the end of the last tile) are 32-bit ints in the kernel
-    if ((long long)pg.max_pages_per_seq * pg.page_size > 0x7fffffffLL - 64) return FA_ERR_BAD_SHAPE;
-    kv_capacity = pg.max_pages_per_seq * pg.page_size;
+    if (const int st = decode_check_pages(pg, head_dim, &kv_capacity)) return st;
   }
   if (batch == 0 || heads_q == 0) return FA_OK;
   if (heads_kv == 0 || heads_q % heads_kv != 0) return FA_ERR_BAD_SHAPE;
@@ -217,15 +282,8 @@ static int decode_entry(int dtype, const void* q, const void* k, const void* v, 
   }
   hipStream_t stream = (hipStream_t)hip_stream;
   const size_t nrow = (size_t)batch * heads_q * seqlen_q;
-  if (kv_capacity == 0) {
-    // rows but no keys: O = 0, LSE = -inf; nothing else runs
-    if (!o) return FA_ERR_NULL_POINTER;
-    if constexpr (SINK)
-      return decode_fill_empty_sink<false>(o, lse, sinks, nrow, heads_q, seqlen_q, head_dim, stream)
-                 ? FA_OK
-                 : FA_ERR_HIP;
-    return decode_fill_empty(o, lse, nrow, head_dim, stream) ? FA_OK : FA_ERR_HIP;
-  }
+  if (kv_capacity == 0)
+    return decode_empty_cache<SINK, false>(o, lse, sinks, nrow, heads_q, seqlen_q, head_dim, stream);
   if (!q || !k || !v || !o || (PAGED && !pg.block_table)) return FA_ERR_NULL_POINTER;
   const DecodeGeom ge = decode_geom(batch, heads_q, heads_kv, seqlen_q);
   if (num_splits > kDecodeMaxSplits) return FA_ERR_BAD_CONFIG;
@@ -260,29 +318,70 @@ static int decode_entry(int dtype, const void* q, const void* k, const void* v, 
   p.causal = causal ? 1 : 0;
   p.c = 1.4426950408889634f / sqrtf((float)head_dim);
   if (ns > 1) decode_set_workspace(p, ge, ns, ws);
-  if constexpr (WIN) p.window = window > 0 ? std::min(window, kv_capacity) : kv_capacity;
-  if constexpr (SINK) p.sinks = sinks;
+  decode_set_variant<KV8, WIN, SINK>(p, kv_capacity, window, sinks, k_scale, v_scale);
   if constexpr (PAGED) {
-    p.table = pg.block_table;
-    p.max_pages = pg.max_pages_per_seq;
-    p.num_pages = pg.num_pages;
-    p.tpp = pg.page_size / 64;
+    decode_set_pages<KV8>(p, pg, heads_kv, head_dim);
     p.adv_pages = 4 / p.tpp;
     p.adv_tiles = 4 % p.tpp;
-    using CacheElem = std::conditional_t<KV8, unsigned char, f16>;  // f16 and bf16: one size
-    p.head_bytes = (unsigned long long)pg.page_size * sizeof(CacheElem) * head_dim;
-    p.page_bytes = p.head_bytes * heads_kv;
-  }
-  if constexpr (KV8) {
-    p.k_scale = k_scale;
-    p.v_scale = v_scale;
   }
   const unsigned grid = (unsigned)(ge.units * ns);
-  if (dtype == FA_DTYPE_BF16)
-    return head_dim == 128 ? decode_launch_nb<__bf16, 128, PAGED, KV8>(ge.nb, p, grid, stream)
-                           : decode_launch_nb<__bf16, 64, PAGED, KV8>(ge.nb, p, grid, stream);
-  return head_dim == 128 ? decode_launch_nb<f16, 128, PAGED, KV8>(ge.nb, p, grid, stream)
-                         : decode_launch_nb<f16, 64, PAGED, KV8>(ge.nb, p, grid, stream);
+  return dispatch_elem_dim(dtype, head_dim, [&](auto e) {
+    using E = decltype(e);
+    return decode_launch_nb<typename E::type, E::hdim, PAGED, KV8>(ge.nb, p, grid, stream);
+  });
 }
 
 }  // namespace fa
+
+// The argument groups an entry's C list is composed of, each once as
+// parameters and once as what the entry bodies take for it (FLAG / FLAGS: the
+// bodies' template arguments).  An entry macro picks one of each kind by tag:
+//   cache:   CONTIG | PAGED       in kv_capacity's place
+//   variant: PLAIN | WIN | SINK   `window` (and `sinks`) after `causal`
+//   scales:  KV16 | KV8           the FP8 scales, last
+#define FA_CONTIG_PARAMS int kv_capacity, int head_dim
+#define FA_CONTIG_ARGS kv_capacity, head_dim, {}
+#define FA_CONTIG_FLAG false
+#define FA_PAGED_PARAMS \
+  int head_dim, int num_pages, int page_size, const int* block_table, int max_pages_per_seq
+#define FA_PAGED_ARGS 0, head_dim, {num_pages, page_size, block_table, max_pages_per_seq}
+#define FA_PAGED_FLAG true
+
+// (the token-major attention entries take `sinks` last, hence two groups)
+#define FA_PLAIN_WINDOW
+#define FA_PLAIN_SINKS
+#define FA_PLAIN_ARGS 0, nullptr
+#define FA_PLAIN_FLAGS false, false
+#define FA_WIN_WINDOW , int window
+#define FA_WIN_SINKS
+#define FA_WIN_ARGS window, nullptr
+#define FA_WIN_FLAGS true, false
+#define FA_SINK_WINDOW , int window
+#define FA_SINK_SINKS , const float* sinks
+#define FA_SINK_ARGS window, sinks
+#define FA_SINK_FLAGS true, true
+
+#define FA_KV16_PARAMS
+#define FA_KV16_ARGS nullptr, nullptr
+#define FA_KV16_FLAG false
+#define FA_KV8_PARAMS , const float* k_scale, const float* v_scale
+#define FA_KV8_ARGS k_scale, v_scale
+#define FA_KV8_FLAG true
+
+// PREFIX_f16 and PREFIX_bf16 of include/fa_mi355x.h, e.g.
+// FA_DECODE_ENTRIES(fa_decode_win_paged_kv8, PAGED, WIN, KV8); the paged lists
+// name `k` / `v` k_pages / v_pages there.
+#define FA_DECODE_ENTRY(NAME, DTYPE, CACHE, VARIANT, SCALES)                                        \
+  extern "C" int NAME(const void* q, const void* k, const void* v, void* o, float* lse, int batch,  \
+                      int heads_q, int heads_kv, int seqlen_q, FA_##CACHE##_PARAMS,                 \
+                      const int* kv_lens, int causal FA_##VARIANT##_WINDOW FA_##VARIANT##_SINKS,    \
+                      int num_splits, void* workspace, unsigned long long ws_bytes,                 \
+                      void* hip_stream FA_##SCALES##_PARAMS) {                                      \
+    return fa::decode_entry<FA_##CACHE##_FLAG, FA_##SCALES##_FLAG, FA_##VARIANT##_FLAGS>(           \
+        DTYPE, q, k, v, o, lse, batch, heads_q, heads_kv, seqlen_q, FA_##CACHE##_ARGS, kv_lens,     \
+        causal, FA_##VARIANT##_ARGS, num_splits, workspace, ws_bytes, hip_stream,                   \
+        FA_##SCALES##_ARGS);                                                                        \
+  }
+#define FA_DECODE_ENTRIES(PREFIX, CACHE, VARIANT, SCALES)                 \
+  FA_DECODE_ENTRY(PREFIX##_f16, FA_DTYPE_F16, CACHE, VARIANT, SCALES)     \
+  FA_DECODE_ENTRY(PREFIX##_bf16, FA_DTYPE_BF16, CACHE, VARIANT, SCALES)

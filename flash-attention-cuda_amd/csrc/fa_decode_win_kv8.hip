@@ -1,31 +1,8 @@
-// fa_decode_win_kv8.hip -- the sliding-window twins of fa_decode_kv8.hip's
-// entries (fa_decode_win_kv8_f16 / _bf16 of include/fa_mi355x.h): the same
-// argument list with `int window` after `causal`, the same entry body
-// (csrc/fa_decode_host.hpp) with WIN = true, launching the Windowed<>
-// instantiations of csrc/fa_decode_kernel.hpp.  A unit of its
-// own so that the build stays parallel.
+// fa_decode_win_kv8.hip -- decode attention over a contiguous FP8 (E4M3) K/V
+// cache with a sliding window: fa_decode_win_kv8_f16 / _bf16 of
+// include/fa_mi355x.h, stamped by FA_DECODE_ENTRIES next to the host body in
+// csrc/fa_decode_host.hpp; the kernel is csrc/fa_decode_kernel.hpp (DESIGN.md
+// §3.0m).  A unit of its own so that the build stays parallel.
 #include "fa_decode_host.hpp"
 
-using namespace fa;
-
-extern "C" int fa_decode_win_kv8_f16(const void* q, const void* k, const void* v, void* o, float* lse,
-                                     int batch, int heads_q, int heads_kv, int seqlen_q,
-                                     int kv_capacity, int head_dim, const int* kv_lens, int causal,
-                                     int window, int num_splits, void* workspace,
-                                     unsigned long long ws_bytes, void* hip_stream,
-                                     const float* k_scale, const float* v_scale) {
-  return decode_entry<false, true, true>(FA_DTYPE_F16, q, k, v, o, lse, batch, heads_q, heads_kv,
-                                         seqlen_q, kv_capacity, head_dim, {}, kv_lens, causal, window,
-                                         num_splits, workspace, ws_bytes, hip_stream, k_scale, v_scale);
-}
-
-extern "C" int fa_decode_win_kv8_bf16(const void* q, const void* k, const void* v, void* o, float* lse,
-                                      int batch, int heads_q, int heads_kv, int seqlen_q,
-                                      int kv_capacity, int head_dim, const int* kv_lens, int causal,
-                                      int window, int num_splits, void* workspace,
-                                      unsigned long long ws_bytes, void* hip_stream,
-                                      const float* k_scale, const float* v_scale) {
-  return decode_entry<false, true, true>(FA_DTYPE_BF16, q, k, v, o, lse, batch, heads_q, heads_kv,
-                                         seqlen_q, kv_capacity, head_dim, {}, kv_lens, causal, window,
-                                         num_splits, workspace, ws_bytes, hip_stream, k_scale, v_scale);
-}
+FA_DECODE_ENTRIES(fa_decode_win_kv8, CONTIG, WIN, KV8)

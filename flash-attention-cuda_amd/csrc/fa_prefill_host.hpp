@@ -1,8 +1,9 @@
 // Host side of the prefill entries of include/fa_mi355x.h, shared by the four
 // cache families (fa_prefill.hip: contiguous, fa_prefill_paged.hip: page pool +
 // block table, fa_prefill_kv8.hip and fa_prefill_paged_kv8.hip: the same two
-// over FP8 bytes): the one entry body (prefill_entry) and the one launcher
-// under it, the twin of fa_decode_host.hpp.  No workspace and no plan: a
+// over FP8 bytes): the one entry body (prefill_entry), the one launcher under
+// it and the macro that stamps a unit's C entries (FA_PREFILL_ENTRIES), the
+// twin of fa_decode_host.hpp.  No workspace and no plan: a
 // workgroup is (batch element, query head, 128-row query block).
 #pragma once
 
@@ -25,30 +26,30 @@ static int prefill_launch_inst(const P& p, unsigned grid, hipStream_t stream) {
   return hipGetLastError() == hipSuccess ? FA_OK : FA_ERR_LAUNCH;
 }
 
-// The body of all eight entries.  PAGED: `k` / `v` are the page pools, `pg`
+// The body of every prefill entry.  PAGED: `k` / `v` are the page pools, `pg`
 // describes them and kv_capacity (passed as 0) becomes max_pages_per_seq *
 // page_size; otherwise `pg` is unused.  KV8: the cache holds E4M3 bytes and
 // k_scale / v_scale go to the kernel; otherwise they are unused.  The checks
 // come in decode_entry's order; everything is returned before any launch.
-// VARLEN (the fa_prefill_varlen_* entries, fa_prefill_varlen*.hip): q and o are
-// packed token-major [total_q][heads_q][head_dim], lse [heads_q][total_q];
+// VARLEN (the fa_prefill_varlen_* entries): q and o are packed token-major
+// [total_q][heads_q][head_dim], lse [heads_q][total_q];
 // `seqlen_q` is total_q, `q_lens` is cu_seqlens (int32[batch + 1], required)
 // and `batch` the number of sequences.  The grid is sized from shapes alone:
 // heads_q * (total_q / 128 + batch) workgroups (fa_varlen_map.hpp).
-// WIN (the fa_prefill[_varlen]_win_* entries, fa_prefill*_win*.hip): `window`
-// is the sliding window W and the kernels are the Windowed<> instantiations,
+// WIN (the fa_prefill[_varlen]_win_* and _sink_* entries): `window` is the
+// sliding window W and the kernels are the Windowed<> instantiations,
 // with decode_entry's rules: a negative W is refused with the negative shapes,
 // W > 0 without causal right after the seqlen_q check, and W = 0 (no window)
 // runs as W = capacity.  Without WIN `window` is not looked at.
-// SINK (the fa_prefill[_varlen]_sink_* entries, fa_prefill*_sink*.hip; with
-// WIN): `sinks` goes to the Sinked<Windowed<>> instantiations (nullptr: no
-// sinks); every status is the windowed twin's.
-template <bool PAGED, bool KV8, bool VARLEN = false, bool WIN = false, bool SINK = false>
+// SINK (the fa_prefill[_varlen]_sink_* entries; with WIN): `sinks` goes to the
+// Sinked<Windowed<>> instantiations (nullptr: no sinks); every status is the
+// windowed twin's.
+template <bool PAGED, bool KV8, bool VARLEN, bool WIN, bool SINK>
 static int prefill_entry(int dtype, const void* q, const void* k, const void* v, void* o, float* lse,
                          int batch, int heads_q, int heads_kv, int seqlen_q, int kv_capacity,
                          int head_dim, const DecodePages& pg, const int* kv_lens, const int* q_lens,
-                         int causal, int window, void* hip_stream, const float* k_scale,
-                         const float* v_scale, [[maybe_unused]] const float* sinks = nullptr) {
+                         int causal, int window, const float* sinks, void* hip_stream,
+                         const float* k_scale, const float* v_scale) {
   static_assert(WIN || !SINK, "the sink kernels are instantiated over the windowed ones");
   using P0 = std::conditional_t<PAGED, std::conditional_t<KV8, PrefillPagedKv8Params, PrefillPagedParams>,
                                 std::conditional_t<KV8, PrefillKv8Params, PrefillParams>>;
@@ -60,15 +61,7 @@ static int prefill_entry(int dtype, const void* q, const void* k, const void* v,
   if (VARLEN ? seqlen_q < 0 : seqlen_q < 1) return FA_ERR_BAD_SHAPE;
   if (WIN && window > 0 && !causal) return FA_ERR_BAD_SHAPE;
   if constexpr (PAGED) {
-    // a 64-key tile must not straddle two pages
-    if (pg.page_size <= 0 || pg.page_size % 64 != 0) return FA_ERR_BAD_SHAPE;
-    if (pg.num_pages <= 0 || pg.max_pages_per_seq < 0) return FA_ERR_BAD_SHAPE;
-    // a head's rows of one page lie in a 32-bit byte range (the FP8 entries
-    // keep the 16-bit bound: both accept the same page sizes)
-    if ((long long)pg.page_size * 2 * head_dim > 0x7fffffffLL) return FA_ERR_BAD_SHAPE;
-    // key indices (up to the end of the last tile) are 32-bit ints in the kernel
-    if ((long long)pg.max_pages_per_seq * pg.page_size > 0x7fffffffLL - 64) return FA_ERR_BAD_SHAPE;
-    kv_capacity = pg.max_pages_per_seq * pg.page_size;
+    if (const int st = decode_check_pages(pg, head_dim, &kv_capacity)) return st;
   }
   if (batch == 0 || heads_q == 0 || (VARLEN && seqlen_q == 0)) return FA_OK;
   if (heads_kv == 0 || heads_q % heads_kv != 0) return FA_ERR_BAD_SHAPE;
@@ -93,14 +86,8 @@ static int prefill_entry(int dtype, const void* q, const void* k, const void* v,
   if (nqb > 0x7fffffffLL || nwg > 0x7fffffffLL) return FA_ERR_BAD_SHAPE;
   hipStream_t stream = (hipStream_t)hip_stream;
   if (kv_capacity == 0) {
-    // rows but no keys: O = 0, LSE = -inf for every row; nothing else runs
-    if (!o) return FA_ERR_NULL_POINTER;
     const size_t nrow = (VARLEN ? (size_t)1 : (size_t)batch) * heads_q * seqlen_q;
-    if constexpr (SINK)
-      return decode_fill_empty_sink<VARLEN>(o, lse, sinks, nrow, heads_q, seqlen_q, head_dim, stream)
-                 ? FA_OK
-                 : FA_ERR_HIP;
-    return decode_fill_empty(o, lse, nrow, head_dim, stream) ? FA_OK : FA_ERR_HIP;
+    return decode_empty_cache<SINK, VARLEN>(o, lse, sinks, nrow, heads_q, seqlen_q, head_dim, stream);
   }
   if (!q || !k || !v || !o || (PAGED && !pg.block_table) || (VARLEN && !q_lens))
     return FA_ERR_NULL_POINTER;
@@ -121,27 +108,32 @@ static int prefill_entry(int dtype, const void* q, const void* k, const void* v,
   p.bhk = (unsigned)batch * (unsigned)heads_kv;
   p.causal = causal ? 1 : 0;
   p.c = 1.4426950408889634f / sqrtf((float)head_dim);
-  if constexpr (WIN) p.window = window > 0 ? std::min(window, kv_capacity) : kv_capacity;
-  if constexpr (SINK) p.sinks = sinks;
-  if constexpr (PAGED) {
-    p.table = pg.block_table;
-    p.max_pages = pg.max_pages_per_seq;
-    p.num_pages = pg.num_pages;
-    p.tpp = pg.page_size / 64;
-    using CacheElem = std::conditional_t<KV8, unsigned char, f16>;  // f16 and bf16: one size
-    p.head_bytes = (unsigned long long)pg.page_size * sizeof(CacheElem) * head_dim;
-    p.page_bytes = p.head_bytes * heads_kv;
-  }
-  if constexpr (KV8) {
-    p.k_scale = k_scale;
-    p.v_scale = v_scale;
-  }
+  decode_set_variant<KV8, WIN, SINK>(p, kv_capacity, window, sinks, k_scale, v_scale);
+  if constexpr (PAGED) decode_set_pages<KV8>(p, pg, heads_kv, head_dim);
   const unsigned grid = (unsigned)nwg;
-  if (dtype == FA_DTYPE_BF16)
-    return head_dim == 128 ? prefill_launch_inst<__bf16, 128, PAGED, KV8, VARLEN>(p, grid, stream)
-                           : prefill_launch_inst<__bf16, 64, PAGED, KV8, VARLEN>(p, grid, stream);
-  return head_dim == 128 ? prefill_launch_inst<f16, 128, PAGED, KV8, VARLEN>(p, grid, stream)
-                         : prefill_launch_inst<f16, 64, PAGED, KV8, VARLEN>(p, grid, stream);
+  return dispatch_elem_dim(dtype, head_dim, [&](auto e) {
+    using E = decltype(e);
+    return prefill_launch_inst<typename E::type, E::hdim, PAGED, KV8, VARLEN>(p, grid, stream);
+  });
 }
 
 }  // namespace fa
+
+// PREFIX_f16 and PREFIX_bf16 of include/fa_mi355x.h from the argument groups of
+// fa_decode_host.hpp, e.g. FA_PREFILL_ENTRIES(fa_prefill_varlen_sink_paged,
+// true, PAGED, SINK, KV16).  VARLEN: the fa_prefill_varlen_* entries, which
+// name `seqlen_q` / `q_lens` total_q / cu_seqlens_q there (the C names differ,
+// the lists do not).
+#define FA_PREFILL_ENTRY(NAME, DTYPE, VARLEN, CACHE, VARIANT, SCALES)                               \
+  extern "C" int NAME(const void* q, const void* k, const void* v, void* o, float* lse, int batch,  \
+                      int heads_q, int heads_kv, int seqlen_q, FA_##CACHE##_PARAMS,                 \
+                      const int* kv_lens, const int* q_lens,                                        \
+                      int causal FA_##VARIANT##_WINDOW FA_##VARIANT##_SINKS,                        \
+                      void* hip_stream FA_##SCALES##_PARAMS) {                                      \
+    return fa::prefill_entry<FA_##CACHE##_FLAG, FA_##SCALES##_FLAG, VARLEN, FA_##VARIANT##_FLAGS>(  \
+        DTYPE, q, k, v, o, lse, batch, heads_q, heads_kv, seqlen_q, FA_##CACHE##_ARGS, kv_lens,     \
+        q_lens, causal, FA_##VARIANT##_ARGS, hip_stream, FA_##SCALES##_ARGS);                       \
+  }
+#define FA_PREFILL_ENTRIES(PREFIX, VARLEN, CACHE, VARIANT, SCALES)                  \
+  FA_PREFILL_ENTRY(PREFIX##_f16, FA_DTYPE_F16, VARLEN, CACHE, VARIANT, SCALES)      \
+  FA_PREFILL_ENTRY(PREFIX##_bf16, FA_DTYPE_BF16, VARLEN, CACHE, VARIANT, SCALES)

@@ -1,27 +1,8 @@
-// fa_prefill_kv8.hip -- the prefill-attention entries of include/fa_mi355x.h
-// over a contiguous FP8 (OCP E4M3) K/V cache (fa_prefill_kv8_f16 /
-// fa_prefill_kv8_bf16): the entry body of csrc/fa_prefill_host.hpp with one
-// byte per cache element and one fp32 scale per K/V head for K and for V,
-// launching csrc/fa_prefill_kernel.hpp with PAGED = false and KV = unsigned
-// char.
+// fa_prefill_kv8.hip -- prefill attention over a contiguous FP8 (E4M3) K/V
+// cache: fa_prefill_kv8_f16 / _bf16 of include/fa_mi355x.h, stamped by
+// FA_PREFILL_ENTRIES next to the host body in csrc/fa_prefill_host.hpp; the
+// kernel is csrc/fa_prefill_kernel.hpp.  A unit of its own
+// so that the build stays parallel.
 #include "fa_prefill_host.hpp"
 
-using namespace fa;
-
-extern "C" int fa_prefill_kv8_f16(const void* q, const void* k, const void* v, void* o, float* lse,
-                                  int batch, int heads_q, int heads_kv, int seqlen_q, int kv_capacity,
-                                  int head_dim, const int* kv_lens, const int* q_lens, int causal,
-                                  void* hip_stream, const float* k_scale, const float* v_scale) {
-  return prefill_entry<false, true>(FA_DTYPE_F16, q, k, v, o, lse, batch, heads_q, heads_kv, seqlen_q,
-                                    kv_capacity, head_dim, {}, kv_lens, q_lens, causal, 0, hip_stream,
-                                    k_scale, v_scale);
-}
-
-extern "C" int fa_prefill_kv8_bf16(const void* q, const void* k, const void* v, void* o, float* lse,
-                                   int batch, int heads_q, int heads_kv, int seqlen_q, int kv_capacity,
-                                   int head_dim, const int* kv_lens, const int* q_lens, int causal,
-                                   void* hip_stream, const float* k_scale, const float* v_scale) {
-  return prefill_entry<false, true>(FA_DTYPE_BF16, q, k, v, o, lse, batch, heads_q, heads_kv, seqlen_q,
-                                    kv_capacity, head_dim, {}, kv_lens, q_lens, causal, 0, hip_stream,
-                                    k_scale, v_scale);
-}
+FA_PREFILL_ENTRIES(fa_prefill_kv8, false, CONTIG, PLAIN, KV8)

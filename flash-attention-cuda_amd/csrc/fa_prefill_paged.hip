@@ -1,29 +1,8 @@
-// fa_prefill_paged.hip -- the prefill-attention entries of include/fa_mi355x.h
-// over a paged 16-bit K/V cache (fa_prefill_paged_f16 / fa_prefill_paged_bf16):
-// the entry body of csrc/fa_prefill_host.hpp launching
-// csrc/fa_prefill_kernel.hpp with PAGED = true and KV = T.
+// fa_prefill_paged.hip -- prefill attention over a paged 16-bit K/V cache
+// (page pool + block table): fa_prefill_paged_f16 / _bf16 of
+// include/fa_mi355x.h, stamped by FA_PREFILL_ENTRIES next to the host body in
+// csrc/fa_prefill_host.hpp; the kernel is csrc/fa_prefill_kernel.hpp
+// (DESIGN.md §3.0k).  A unit of its own so that the build stays parallel.
 #include "fa_prefill_host.hpp"
 
-using namespace fa;
-
-extern "C" int fa_prefill_paged_f16(const void* q, const void* k_pages, const void* v_pages, void* o,
-                                    float* lse, int batch, int heads_q, int heads_kv, int seqlen_q,
-                                    int head_dim, int num_pages, int page_size, const int* block_table,
-                                    int max_pages_per_seq, const int* kv_lens, const int* q_lens,
-                                    int causal, void* hip_stream) {
-  return prefill_entry<true, false>(FA_DTYPE_F16, q, k_pages, v_pages, o, lse, batch, heads_q, heads_kv,
-                                    seqlen_q, 0, head_dim,
-                                    {num_pages, page_size, block_table, max_pages_per_seq}, kv_lens,
-                                    q_lens, causal, 0, hip_stream, nullptr, nullptr);
-}
-
-extern "C" int fa_prefill_paged_bf16(const void* q, const void* k_pages, const void* v_pages, void* o,
-                                     float* lse, int batch, int heads_q, int heads_kv, int seqlen_q,
-                                     int head_dim, int num_pages, int page_size, const int* block_table,
-                                     int max_pages_per_seq, const int* kv_lens, const int* q_lens,
-                                     int causal, void* hip_stream) {
-  return prefill_entry<true, false>(FA_DTYPE_BF16, q, k_pages, v_pages, o, lse, batch, heads_q, heads_kv,
-                                    seqlen_q, 0, head_dim,
-                                    {num_pages, page_size, block_table, max_pages_per_seq}, kv_lens,
-                                    q_lens, causal, 0, hip_stream, nullptr, nullptr);
-}
+FA_PREFILL_ENTRIES(fa_prefill_paged, false, PAGED, PLAIN, KV16)

@@ -1,32 +1,9 @@
-// fa_prefill_sink_paged_kv8.hip -- the attention-sink twins of
-// fa_prefill_win_paged_kv8.hip's entries (fa_prefill_sink_paged_kv8_f16 / _bf16
-// of include/fa_mi355x.h): the same argument list with `const float* sinks`
-// after `window`, the same entry body (csrc/fa_prefill_host.hpp) with WIN =
-// SINK = true, launching the Sinked<Windowed<>> instantiations of
-// csrc/fa_prefill_kernel.hpp.  A unit of its own so that the
-// build stays parallel.
+// fa_prefill_sink_paged_kv8.hip -- prefill attention over a paged FP8 (E4M3)
+// K/V cache with a sliding window and attention sinks:
+// fa_prefill_sink_paged_kv8_f16 / _bf16 of include/fa_mi355x.h, stamped by
+// FA_PREFILL_ENTRIES next to the host body in csrc/fa_prefill_host.hpp; the
+// kernel is csrc/fa_prefill_kernel.hpp.  A unit of its own
+// so that the build stays parallel.
 #include "fa_prefill_host.hpp"
 
-using namespace fa;
-
-extern "C" int fa_prefill_sink_paged_kv8_f16(const void* q, const void* k_pages,
-    const void* v_pages, void* o, float* lse, int batch, int heads_q, int heads_kv, int seqlen_q,
-    int head_dim, int num_pages, int page_size, const int* block_table, int max_pages_per_seq,
-    const int* kv_lens, const int* q_lens, int causal, int window, const float* sinks,
-    void* hip_stream, const float* k_scale, const float* v_scale) {
-  return prefill_entry<true, true, false, true, true>(FA_DTYPE_F16, q, k_pages, v_pages, o, lse,
-      batch, heads_q, heads_kv, seqlen_q, 0, head_dim,
-      {num_pages, page_size, block_table, max_pages_per_seq}, kv_lens, q_lens, causal, window,
-      hip_stream, k_scale, v_scale, sinks);
-}
-
-extern "C" int fa_prefill_sink_paged_kv8_bf16(const void* q, const void* k_pages,
-    const void* v_pages, void* o, float* lse, int batch, int heads_q, int heads_kv, int seqlen_q,
-    int head_dim, int num_pages, int page_size, const int* block_table, int max_pages_per_seq,
-    const int* kv_lens, const int* q_lens, int causal, int window, const float* sinks,
-    void* hip_stream, const float* k_scale, const float* v_scale) {
-  return prefill_entry<true, true, false, true, true>(FA_DTYPE_BF16, q, k_pages, v_pages, o, lse,
-      batch, heads_q, heads_kv, seqlen_q, 0, head_dim,
-      {num_pages, page_size, block_table, max_pages_per_seq}, kv_lens, q_lens, causal, window,
-      hip_stream, k_scale, v_scale, sinks);
-}
+FA_PREFILL_ENTRIES(fa_prefill_sink_paged_kv8, false, PAGED, SINK, KV8)

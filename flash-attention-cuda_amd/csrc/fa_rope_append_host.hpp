@@ -56,11 +56,7 @@ static int rope_append_entry(int dtype, const RopeArgs& ra, const void* k_new, c
   if (ra.rotary_dim < 16 || ra.rotary_dim > head_dim || ra.rotary_dim % 16 != 0) return FA_ERR_BAD_SHAPE;
   if (ra.rope_len < 1) return FA_ERR_BAD_SHAPE;
   if constexpr (PAGED) {
-    if (pg.page_size <= 0 || pg.page_size % 64 != 0) return FA_ERR_BAD_SHAPE;
-    if (pg.num_pages <= 0 || pg.max_pages_per_seq < 0) return FA_ERR_BAD_SHAPE;
-    if ((long long)pg.page_size * 2 * head_dim > 0x7fffffffLL) return FA_ERR_BAD_SHAPE;
-    if ((long long)pg.max_pages_per_seq * pg.page_size > 0x7fffffffLL - 64) return FA_ERR_BAD_SHAPE;
-    kv_capacity = pg.max_pages_per_seq * pg.page_size;
+    if (const int st = decode_check_pages(pg, head_dim, &kv_capacity)) return st;
   }
   if (batch == 0 || (heads_kv == 0 && ra.heads_q == 0) || (VARLEN && seqlen_new == 0)) return FA_OK;
   if constexpr (!PAGED) {

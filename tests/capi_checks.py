@@ -178,3 +178,65 @@ def decode_paged_argument_checks(fa, lib):
         # ... but the page geometry is still checked
         assert _call(fn, None, None, None, None, 0, 8, 2, 1, 128, 100, 96, None, 32) == \
             fa.FA_ERR_BAD_SHAPE
+
+
+# The attention entries the three host bodies serve: family x variant x cache
+# form x element type (the fa_attn_varlen_* entries read no cache: one form).
+FORMS = ("", "_paged", "_kv8", "_paged_kv8")
+VARIANTS = ("", "_win", "_sink")
+ATTENTION_ENTRIES = [(fam, var, form, ty)
+                     for fam in ("fa_decode", "fa_prefill", "fa_prefill_varlen", "fa_attn_varlen")
+                     for var in VARIANTS for form in (FORMS if fam != "fa_attn_varlen" else ("",))
+                     for ty in ("_f16", "_bf16")]
+
+
+def entry_symbol(entry):
+    fam, var, form, ty = entry
+    return fam + var + form + ty
+
+
+def _entry_call(lib, entry, q=None, k=None, v=None, o=None, table=None, qlens=None, b=1, hq=2, hkv=1,
+                sq=1, cap=128, d=64, psz=64, causal=1, window=0):
+    """One attention entry on the shared arguments, each argument group where
+    its list has it: the paged forms take `cap` as two pages of `psz` keys from
+    a pool of two, the token-major entries as uniform lengths (totals = b * sq
+    and b * cap, no cu_seqlens)."""
+    fam, var, form, _ = entry
+    fn = getattr(lib, entry_symbol(entry))
+    win = {"": [], "_win": [window], "_sink": [window, None]}[var]
+    scales = [None, None] if "kv8" in form else []
+    if fam == "fa_attn_varlen":
+        return fn(q, k, v, o, None, b, hq, hkv, b * sq, b * cap, d, 0, 0, 0, None, None, sq, cap, causal,
+                  *win[:1], None, *win[1:])
+    cache = [d, 2, psz, table, 2] if "paged" in form else [cap, d]
+    if fam == "fa_decode":
+        return fn(q, k, v, o, None, b, hq, hkv, sq, *cache, None, causal, *win, 0, None, 0, None, *scales)
+    return fn(q, k, v, o, None, b, hq, hkv, sq, *cache, None, qlens, causal, *win, None, *scales)
+
+
+def entry_status_checks(fa, lib, entry):
+    """The argument statuses every attention entry answers alike, whichever
+    argument groups its list carries; all are returned before any HIP call
+    (fake pointers).  B=1, Hq=2, Hkv=1, cap=128, D=64; Sq=1 for decode, else 130."""
+    fam, var, form, _ = entry
+    p = ctypes.c_void_p(0x1000)
+    sq = 1 if fam == "fa_decode" else 130
+    ptrs = dict(q=p, k=p, v=p, o=p, table=p, qlens=p)
+
+    def call(**kw):
+        return _entry_call(lib, entry, **{"sq": sq, **ptrs, **kw})
+
+    # negative extents
+    assert call(b=-1) == fa.FA_ERR_BAD_SHAPE
+    assert call(hq=-2) == fa.FA_ERR_BAD_SHAPE
+    assert call(hkv=-1) == fa.FA_ERR_BAD_SHAPE
+    assert call(d=96) == fa.FA_ERR_UNSUPPORTED_HEAD_DIM
+    # an empty batch: nothing to do, no pointer looked at
+    assert _entry_call(lib, entry, b=0, sq=sq) == fa.FA_OK
+    if var:
+        assert call(window=-1) == fa.FA_ERR_BAD_SHAPE
+        assert call(window=4, causal=0) == fa.FA_ERR_BAD_SHAPE
+    if "paged" in form:
+        assert call(psz=32) == fa.FA_ERR_BAD_SHAPE
+    # a valid shape: q is looked at after every shape check
+    assert call(q=None) == fa.FA_ERR_NULL_POINTER

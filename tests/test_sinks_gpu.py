@@ -328,6 +328,24 @@ def test_prefill_random_inputs_against_the_references(dtype, d, window, causal):
     assert _same_rows(packed, base8, RQ_LENS), what + " fp8 paged packed"
 
 
+@pytest.mark.parametrize("dtype", dr.DTYPES)
+def test_packed_prefill_over_a_contiguous_fp8_cache_against_the_references(dtype):
+    """fa_prefill_varlen_sink_kv8_*, the one pair of sink entries nothing above
+    calls (packed Q over a contiguous FP8 cache), at a small shape with real
+    arguments: two sequences of 130 and 40 rows, the second behind a 30-key
+    prefix, W = 80, non-unit scales; the gates on the dequantised cache."""
+    b, hq, hkv, sq, cap, d, window = 2, 4, 2, 130, 192, 64, 80
+    kv_lens, q_lens = (192, 70), (130, 40)
+    _, (q, _, _), (k8, v8, ksc, vsc) = _inputs(b, hq, hkv, sq, cap, d, dtype, True)
+    sinks, refs = _refs(b, hq, hkv, sq, cap, d, dtype, True, kv_lens, q_lens, window, True, 11)
+    cu = vr.cu_of(q_lens)
+    qp = vr.pack(q, q_lens, total=cu[-1] + 7, fill=dr.NAN_BITS)
+    po, pl = prefill_varlen(qp, _pad(k8, kv_lens), _pad(v8, kv_lens), _lens(cu), _lens(kv_lens), return_lse=True,
+                            window=window, sinks=_dev32(sinks), k_scale=ksc, v_scale=vsc)
+    packed = (vr.unpack(po, cu, sq), vr.unpack(pl, cu, sq, fill=NINF))
+    sr.check(*packed, refs, q_lens, dtype, f"packed fp8 contiguous {dr.name(dtype)} W={window}")
+
+
 @pytest.mark.parametrize("window,causal", [(0, True), (100, True), (0, False)])
 @pytest.mark.parametrize("sq", [1, 4, 16])
 @pytest.mark.parametrize("dtype", dr.DTYPES)
