@@ -1,10 +1,14 @@
-// Host side of the fa_attn_varlen_bwd_* entries of include/fa_mi355x.h: the
-// backward pass of the attention over token-major Q, K and V (DESIGN.md
-// §3.0q).  attn_varlen_entry's checks in attn_varlen_entry's order, then three
-// launches on the caller's stream (delta, dK/dV, dQ: fa_attn_bwd_kernel.hpp).
-// No sync, nothing read from the device, no workspace but the caller's delta:
-// the grids are total_q / 128 + batch, heads_kv * (total_k / 128 + batch) and
-// heads_q * (total_q / 128 + batch) workgroups, from shapes alone.
+// Host side of the fa_attn_varlen_bwd_* entries of include/fa_mi355x.h and of
+// their sliding-window and attention-sink twins, fa_attn_bwd_win_* and
+// fa_attn_bwd_sink_*: the backward pass of the attention over token-major Q, K
+// and V.  One entry body (attn_varlen_bwd_entry,
+// stamped into C entries by FA_ATTN_BWD_ENTRY below); attn_varlen_entry's
+// checks in attn_varlen_entry's order, then three launches on the caller's
+// stream (delta, dK/dV, dQ: fa_attn_bwd_kernel.hpp) and, with sinks, a fourth
+// (dsinks).  No sync, nothing read from the device, no workspace but the
+// caller's delta: the grids are total_q / 128 + batch, heads_kv * (total_k /
+// 128 + batch), heads_q * (total_q / 128 + batch) and heads_q workgroups, from
+// shapes alone.
 #pragma once
 
 #include "fa_attn_bwd_kernel.hpp"
@@ -12,28 +16,43 @@
 
 namespace fa {
 
-template <class T, int HDIM>
-static int attn_bwd_launch(const AttnBwdParams& p, unsigned g_delta, unsigned g_dkdv, unsigned g_dq,
+// P: AttnBwdParams, or Windowed<AttnBwdParams> for the _win kernels
+template <class T, int HDIM, class P>
+static int attn_bwd_launch(const P& p, unsigned g_delta, unsigned g_dkdv, unsigned g_dq,
                            hipStream_t stream) {
   hipLaunchKernelGGL((fa_attn_bwd_delta_kernel<T, HDIM>), dim3(g_delta), dim3(256), 0, stream, p);
   if (hipGetLastError() != hipSuccess) return FA_ERR_LAUNCH;
-  hipLaunchKernelGGL((fa_attn_bwd_dkdv_kernel<T, HDIM>), dim3(g_dkdv), dim3(256), 0, stream, p);
+  hipLaunchKernelGGL((fa_attn_bwd_dkdv_kernel<T, HDIM, P>), dim3(g_dkdv), dim3(256), 0, stream, p);
   if (hipGetLastError() != hipSuccess) return FA_ERR_LAUNCH;
-  hipLaunchKernelGGL((fa_attn_bwd_dq_kernel<T, HDIM>), dim3(g_dq), dim3(256), 0, stream, p);
+  hipLaunchKernelGGL((fa_attn_bwd_dq_kernel<T, HDIM, P>), dim3(g_dq), dim3(256), 0, stream, p);
   return hipGetLastError() == hipSuccess ? FA_OK : FA_ERR_LAUNCH;
 }
 
-// T: the element type (one translation unit per type, so the two compile in parallel)
-template <class T>
+// dsinks, where the caller gave it, of a problem without a row or without a key: zeros
+static inline bool attn_bwd_zero_dsinks(float* dsinks, int heads_q, hipStream_t stream) {
+  return !dsinks || hipMemsetAsync(dsinks, 0, (size_t)heads_q * sizeof(float), stream) == hipSuccess;
+}
+
+// T: the element type (one translation unit per type, so the two compile in
+// parallel).  WIN / SINK: as for attn_varlen_entry (the fa_attn_bwd_win_* /
+// _sink_* entries).  SINK: `sinks` NULL is the _win entry, and `dsinks` is then
+// zero-filled if it is given; with `sinks`, `dsinks` is required and written.
+template <class T, bool WIN, bool SINK>
 static int attn_varlen_bwd_entry(const void* dout, const void* q, const void* k, const void* v,
                                  const void* out, const float* lse, void* dq, void* dk, void* dv,
                                  float* delta, int batch, int heads_q, int heads_kv, int total_q,
                                  int total_k, int head_dim, long long do_stride, long long q_stride,
                                  long long k_stride, long long v_stride, const int* cu_q, const int* cu_k,
-                                 int seqlen_q, int seqlen_k, int causal, void* hip_stream) {
+                                 int seqlen_q, int seqlen_k, int causal, [[maybe_unused]] int window,
+                                 [[maybe_unused]] const float* sinks, [[maybe_unused]] float* dsinks,
+                                 void* hip_stream) {
+  static_assert(WIN || !SINK, "the sink entries run the windowed kernels");
+  using P = std::conditional_t<WIN, Windowed<AttnBwdParams>, AttnBwdParams>;
   if (batch < 0 || heads_q < 0 || heads_kv < 0 || total_k < 0 || head_dim < 0) return FA_ERR_BAD_SHAPE;
+  if (WIN && window < 0) return FA_ERR_BAD_SHAPE;
   if (head_dim != 128 && head_dim != 64) return FA_ERR_UNSUPPORTED_HEAD_DIM;
   if (total_q < 0) return FA_ERR_BAD_SHAPE;
+  if (WIN && window > 0 && !causal) return FA_ERR_BAD_SHAPE;
   // the strides: 16-byte loads, and one block's rows (128 of each tensor here:
   // a workgroup addresses its 128 keys from the block's first as it does its
   // 128 query rows) in a 32-bit byte range
@@ -54,6 +73,8 @@ static int attn_varlen_bwd_entry(const void* dout, const void* q, const void* k,
   if (batch == 0 || total_q == 0) {
     // no query row: every key's gradient is zero
     const size_t bytes = (size_t)total_k * (size_t)heads_kv * head_dim * 2;
+    if constexpr (SINK)
+      if (!attn_bwd_zero_dsinks(dsinks, heads_q, stream)) return FA_ERR_HIP;
     if (bytes == 0) return FA_OK;
     if (!dk || !dv) return FA_ERR_NULL_POINTER;
     if (hipMemsetAsync(dk, 0, bytes, stream) != hipSuccess) return FA_ERR_HIP;
@@ -70,20 +91,26 @@ static int attn_varlen_bwd_entry(const void* dout, const void* q, const void* k,
   if ((long long)kBwdBM * heads_q * 2 * head_dim > 0x7fffffffLL) return FA_ERR_BAD_SHAPE;
   if ((long long)kBwdBN * heads_kv * 2 * head_dim > 0x7fffffffLL) return FA_ERR_BAD_SHAPE;
   if (total_k > 0x7fffffff - 64) return FA_ERR_BAD_SHAPE;
+  // the windowed kernels form off + row - W and key + W from ints
+  if (WIN && (long long)total_q + total_k > 0x7fffffffLL) return FA_ERR_BAD_SHAPE;
   const long long nqb = (long long)total_q / kBwdBM + batch;
   const long long nkb = (long long)total_k / kBwdBN + batch;
   if (nqb > 0x7fffffffLL || heads_q * nqb > 0x7fffffffLL || heads_kv * nkb > 0x7fffffffLL)
     return FA_ERR_BAD_SHAPE;
   if (total_k == 0) {
-    // rows but no keys: dQ = 0 for every row
+    // rows but no keys: dQ = 0 for every row (and out = 0, so delta = 0: dsinks = 0)
     if (!dq) return FA_ERR_NULL_POINTER;
+    if constexpr (SINK)
+      if (!attn_bwd_zero_dsinks(dsinks, heads_q, stream)) return FA_ERR_HIP;
     return hipMemsetAsync(dq, 0, (size_t)total_q * (size_t)heads_q * head_dim * 2, stream) == hipSuccess
                ? FA_OK
                : FA_ERR_HIP;
   }
   if (!dout || !q || !k || !v || !out || !dq || !dk || !dv) return FA_ERR_NULL_POINTER;
   if (!lse || !delta) return FA_ERR_NULL_POINTER;
-  AttnBwdParams p = {};
+  if constexpr (SINK)
+    if (sinks && !dsinks) return FA_ERR_NULL_POINTER;
+  P p = {};
   p.dout = dout, p.q = q, p.k = k, p.v = v, p.out = out, p.lse = lse;
   p.dq = dq, p.dk = dk, p.dv = dv, p.delta = delta;
   p.cu_q = cu_q;
@@ -94,9 +121,45 @@ static int attn_varlen_bwd_entry(const void* dout, const void* q, const void* k,
   p.tq = total_q, p.tk = total_k, p.nseq = batch;
   p.causal = causal ? 1 : 0;
   p.c = 1.0f / sqrtf((float)head_dim);
+  // no window (and so every non-causal call): W = total_k, which excludes no key
+  if constexpr (WIN) p.window = window > 0 ? std::min(window, total_k) : total_k;
   const unsigned gd = (unsigned)nqb, gk = (unsigned)(heads_kv * nkb), gq = (unsigned)(heads_q * nqb);
-  return head_dim == 128 ? attn_bwd_launch<T, 128>(p, gd, gk, gq, stream)
-                         : attn_bwd_launch<T, 64>(p, gd, gk, gq, stream);
+  const int rc = head_dim == 128 ? attn_bwd_launch<T, 128>(p, gd, gk, gq, stream)
+                                 : attn_bwd_launch<T, 64>(p, gd, gk, gq, stream);
+  if constexpr (SINK) {
+    if (rc != FA_OK) return rc;
+    if (!sinks) return attn_bwd_zero_dsinks(dsinks, heads_q, stream) ? FA_OK : FA_ERR_HIP;
+    AttnBwdSinkParams sp = {};
+    sp.lse = lse, sp.delta = delta, sp.sinks = sinks, sp.dsinks = dsinks;
+    sp.cu_q = cu_q, sp.useq_q = seqlen_q, sp.nseq = batch, sp.tq = total_q;
+    hipLaunchKernelGGL((fa_attn_bwd_dsinks_kernel<kBwdSinkThreads>), dim3((unsigned)heads_q),
+                       dim3(kBwdSinkThreads), 0, stream, sp);
+    return hipGetLastError() == hipSuccess ? FA_OK : FA_ERR_LAUNCH;
+  }
+  return rc;
 }
 
 }  // namespace fa
+
+// NAME of include/fa_mi355x.h over element type T, the variant's window group
+// and flags from fa_decode_host.hpp; the sink entries take `sinks` and `dsinks`
+// after the stream: FA_ATTN_BWD_ENTRY(fa_attn_bwd_sink_f16, fa::f16, SINK).
+#define FA_BWD_PLAIN_SINKS
+#define FA_BWD_PLAIN_ARGS 0, nullptr, nullptr
+#define FA_BWD_WIN_SINKS
+#define FA_BWD_WIN_ARGS window, nullptr, nullptr
+#define FA_BWD_SINK_SINKS , const float* sinks, float* dsinks
+#define FA_BWD_SINK_ARGS window, sinks, dsinks
+#define FA_ATTN_BWD_ENTRY(NAME, T, VARIANT)                                                           \
+  extern "C" int NAME(const void* dout, const void* q, const void* k, const void* v, const void* out, \
+                      const float* lse, void* dq, void* dk, void* dv, float* delta, int batch,        \
+                      int heads_q, int heads_kv, int total_q, int total_k, int head_dim,              \
+                      long long do_stride, long long q_stride, long long k_stride,                    \
+                      long long v_stride, const int* cu_seqlens_q, const int* cu_seqlens_k,           \
+                      int seqlen_q, int seqlen_k, int causal FA_##VARIANT##_WINDOW,                   \
+                      void* hip_stream FA_BWD_##VARIANT##_SINKS) {                                    \
+    return fa::attn_varlen_bwd_entry<T, FA_##VARIANT##_FLAGS>(                                        \
+        dout, q, k, v, out, lse, dq, dk, dv, delta, batch, heads_q, heads_kv, total_q, total_k,       \
+        head_dim, do_stride, q_stride, k_stride, v_stride, cu_seqlens_q, cu_seqlens_k, seqlen_q,      \
+        seqlen_k, causal, FA_BWD_##VARIANT##_ARGS, hip_stream);                                       \
+  }

@@ -34,6 +34,21 @@
 // descriptors end the same way).  A masked element is selected to 0, never
 // multiplied; a row whose LSE is -inf takes -inf as its exponent offset, so
 // exp(-inf - (-inf)) is never formed.
+//
+// The sliding window and the sinks (fa_attn_bwd_win_* / fa_attn_bwd_sink_*,
+// DESIGN.md §3.0r).  The dK/dV and dQ kernels take WIN from their parameter
+// type, Windowed<AttnBwdParams>, as the forward's kernels do, and every line
+// of it stands under `if constexpr (WIN)`: the instantiations of the entries
+// without a window keep their device code, instruction for instruction.
+// Row t of a sequence then sees the keys lo <= j with lo = off + t - W + 1 (off
+// = nk - nq); the host gives W = total_k where there is no window, which
+// excludes no key, and has checked that total_q + total_k fits an int.  WIN
+// adds one comparison to the mask and bounds the sweeps: the dK/dV sweep ends
+// at the tile of the last row whose window reaches the block, the dQ sweep
+// starts at the tile of the first key its block's first row sees, and a wave
+// skips a 32-row (32-key) sub-block that lies wholly outside.  The sinks need
+// nothing there: the forward's LSE holds them.  Their own gradient is
+// fa_attn_bwd_dsinks_kernel, a fourth launch.
 #pragma once
 
 #include "fa_prefill_kernel.hpp"
@@ -156,8 +171,21 @@ __global__ __launch_bounds__(256) void fa_attn_bwd_delta_kernel(AttnBwdParams p)
   }
 }
 
-template <class T, int HDIM>
-__global__ __launch_bounds__(256) void fa_attn_bwd_dkdv_kernel(AttnBwdParams p) {
+// WIN: the last row whose window still holds a key, from the first row that
+// sees it under the causal mask (key - off; either may lie outside the
+// sequence); otherwise unused
+template <bool WIN, class P>
+__device__ __forceinline__ int bwd_last_row([[maybe_unused]] const P& p, [[maybe_unused]] int first) {
+  if constexpr (WIN)
+    return first + p.window - 1;
+  else
+    return 0;
+}
+
+// P: AttnBwdParams, or Windowed<AttnBwdParams> (WIN)
+template <class T, int HDIM, class P = AttnBwdParams>
+__global__ __launch_bounds__(256) void fa_attn_bwd_dkdv_kernel(P p) {
+  constexpr bool WIN = ParamsWindowed<P>::value;
   constexpr int BN = kBwdBN, BT = kBwdTile, ROW = 2 * HDIM, NS = HDIM / 32, NE = HDIM / 16;
   constexpr int KB = BN / 64;  // 16-key blocks per wave
   typedef typename Elem<T>::x8 tx8;
@@ -187,7 +215,11 @@ __global__ __launch_bounds__(256) void fa_attn_bwd_dkdv_kernel(AttnBwdParams p) 
   const int off = nk - nq;
   // causal: the first query tile with a row that reaches the block's first key
   const int j0 = p.causal ? max(0, k0 - off) / BT : 0;
-  const int nt = max(0, (nq + BT - 1) / BT - j0);
+  // WIN: ... and the sweep ends with the last row whose window reaches the
+  // block (lo <= its last key); no such row: no tile
+  const int last = bwd_last_row<WIN>(p, k0 + live - 1 - off);
+  const int nt = WIN ? (last < 0 ? 0 : max(0, min((nq + BT - 1) / BT, last / BT + 1) - j0))
+                     : max(0, (nq + BT - 1) / BT - j0);
   const int total = nt * p.group;
   const int kw = 32 * wave;  // this wave's first key within the block
   const float c2 = p.c * 1.4426950408889634f;
@@ -253,6 +285,9 @@ __global__ __launch_bounds__(256) void fa_attn_bwd_dkdv_kernel(AttnBwdParams p) 
       // wave-uniform: no row of these 32 in the sequence, or none reaches this wave's keys
       if (i0 + ib >= nq) continue;
       if (p.causal && off + i0 + ib + 31 < k0 + kw) continue;
+      // ... or the window of the first of them (and so of all) starts past this wave's keys
+      if constexpr (WIN)
+        if (off + i0 + ib - p.window + 1 > k0 + kw + 31) continue;
       f32x4 s[2][KB], dp[2][KB];
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
@@ -288,7 +323,8 @@ __global__ __launch_bounds__(256) void fa_attn_bwd_dkdv_kernel(AttnBwdParams p) 
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
               const int row = i0 + ib + 16 * t + 4 * h + i;
-              const bool ok = row < nq && key < nk && (!p.causal || key <= off + row);
+              bool ok = row < nq && key < nk && (!p.causal || key <= off + row);
+              if constexpr (WIN) ok = ok && key > off + row - p.window;
               const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(s[t][kb][i], c2, nl[t][i]));
               pv[t][i] = ok ? e : 0.f;
               ds[t][i] = ok ? e * (dp[t][kb][i] - de[t][i]) : 0.f;
@@ -345,8 +381,10 @@ __global__ __launch_bounds__(256) void fa_attn_bwd_dkdv_kernel(AttnBwdParams p) 
     }
 }
 
-template <class T, int HDIM>
-__global__ __launch_bounds__(256) void fa_attn_bwd_dq_kernel(AttnBwdParams p) {
+// P: as for the dK/dV kernel
+template <class T, int HDIM, class P = AttnBwdParams>
+__global__ __launch_bounds__(256) void fa_attn_bwd_dq_kernel(P p) {
+  constexpr bool WIN = ParamsWindowed<P>::value;
   constexpr int BM = kBwdBM, BT = kBwdTile, ROW = 2 * HDIM, NS = HDIM / 32, NE = HDIM / 16;
   constexpr int IB = BM / 64;  // 16-row blocks per wave
   typedef typename Elem<T>::x8 tx8;
@@ -377,6 +415,9 @@ __global__ __launch_bounds__(256) void fa_attn_bwd_dq_kernel(AttnBwdParams p) {
   const int off = nk - nq;
   const int kv_hi = p.causal ? max(0, min(nk, off + q0 + BM)) : nk;
   const int ntiles = (kv_hi + BT - 1) / BT;
+  // WIN: the tile of the first key the block's first row sees; the tiles below it are never loaded
+  int jt0 = 0;
+  if constexpr (WIN) jt0 = max(0, off + q0 - p.window + 1) / BT;
   const int qw = 32 * wave;  // this wave's first row within the block
   const float c2 = p.c * 1.4426950408889634f;
 
@@ -429,6 +470,9 @@ __global__ __launch_bounds__(256) void fa_attn_bwd_dq_kernel(AttnBwdParams p) {
       // wave-uniform: no key of these 32 is seen by a row of this wave
       if (key0 >= kv_hi) continue;
       if (p.causal && key0 > off + q0 + qw + 31) continue;
+      // ... or all 32 lie below the window of the wave's first row (and so of all its rows)
+      if constexpr (WIN)
+        if (key0 + 31 < off + q0 + qw - p.window + 1) continue;
       f32x4 s[2][IB], dp[2][IB];
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
@@ -457,7 +501,8 @@ __global__ __launch_bounds__(256) void fa_attn_bwd_dq_kernel(AttnBwdParams p) {
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
             const int key = key0 + 16 * t + 4 * h + i;
-            const bool ok = row < nq && key < nk && (!p.causal || key <= off + row);
+            bool ok = row < nq && key < nk && (!p.causal || key <= off + row);
+            if constexpr (WIN) ok = ok && key > off + row - p.window;
             const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(s[t][ib][i], c2, nl[ib]));
             ds[t][i] = ok ? e * (dp[t][ib][i] - de[ib]) : 0.f;
           }
@@ -475,12 +520,12 @@ __global__ __launch_bounds__(256) void fa_attn_bwd_dq_kernel(AttnBwdParams p) {
     }
   };
 
-  if (ntiles > 0) {
-    issue(0);
+  if (ntiles > jt0) {
+    issue(jt0);
     st.write(ki, vi, tid);
   }
   __syncthreads();
-  for (int j = 0; j < ntiles; ++j) {
+  for (int j = jt0; j < ntiles; ++j) {
     const bool more = j + 1 < ntiles;  // workgroup-uniform
     if (more) issue(j + 1);
     compute(j);
@@ -498,6 +543,66 @@ __global__ __launch_bounds__(256) void fa_attn_bwd_dq_kernel(AttnBwdParams p) {
 #pragma unroll
     for (int e = 0; e < NE; ++e)
       bwd_store4<T>(ro, (qw + 16 * ib + l16) * os + (16 * e + 4 * h) * 2, dq[ib][e], p.c);
+}
+
+// dsinks[h] = -sum_i exp(sinks[h] - LSE[h][i]) delta[h][i] over the rows of a
+// sequence (the sink is one more softmax column whose value is zero, so its dS
+// is P_sink (0 - delta)).  Workgroup = one query head.  It walks the sequences
+// in order (their spans as the packed map clamps them: the rows whose delta the
+// delta kernel wrote, in bounds whatever cu holds), thread t taking the rows t,
+// t + NT, .. of each into one fp32 sum; then the butterfly over the lanes and
+// the waves' sums in wave order: one fixed order, no atomics.  It is bound by
+// the latency of its loads, not their bytes: 1024 threads with both loads of
+// eight rows in flight take 8 - 19 us at T_q = 32k where four waves walking
+// the 128-row block ids, a bisection each, took 120 us, a tenth of a windowed
+// gpt-oss backward.  A row whose LSE is -inf and a head whose
+// sink is -inf add nothing, so exp(-inf - (-inf)) is never formed.  NT: the
+// workgroup's size (a template so that the units share the kernel).
+constexpr int kBwdSinkThreads = 1024;  // the workgroup of fa_attn_bwd_dsinks_kernel
+
+struct AttnBwdSinkParams {
+  const float* lse;    // [Hq][T_q]
+  const float* delta;  // [Hq][T_q]
+  const float* sinks;  // [Hq]
+  float* dsinks;       // [Hq]
+  const int* cu_q;
+  int useq_q, nseq, tq;
+};
+
+template <int NT>
+__global__ __launch_bounds__(NT) void fa_attn_bwd_dsinks_kernel(AttnBwdSinkParams p) {
+  constexpr int NW = NT / 64;
+  __shared__ float part[NW];
+  const int head = (int)blockIdx.x, lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+  const float sink = p.sinks[head];
+  float acc = 0.f;
+  if (sink != ninf()) {
+    const float* const L = p.lse + (size_t)head * (size_t)p.tq;
+    const float* const D = p.delta + (size_t)head * (size_t)p.tq;
+    for (int b = 0; b < p.nseq; ++b) {
+      const int s0 = varlen_start(p.cu_q, p.useq_q, p.tq, b);
+      const int n = max(varlen_start(p.cu_q, p.useq_q, p.tq, b + 1), s0) - s0;
+      // both loads whatever the row, so that the unrolled rows' loads are all in flight together
+#pragma unroll 8
+      for (int r = (int)threadIdx.x; r < n; r += NT) {
+        const size_t t = (size_t)s0 + r;
+        const float l = L[t], d = D[t];
+        const float e = __builtin_amdgcn_exp2f((sink - (l == ninf() ? sink : l)) * 1.4426950408889634f);
+        acc = l == ninf() ? acc : __builtin_fmaf(e, d, acc);
+      }
+    }
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m);
+  if (lane == 0) part[wave] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float tot = 0.f;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) tot += part[w];
+    p.dsinks[head] = 0.f - tot;
+  }
 }
 
 }  // namespace fa

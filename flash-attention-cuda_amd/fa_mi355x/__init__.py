@@ -158,6 +158,10 @@ EXPORTED_SYMBOLS = (
     "fa_attn_varlen_sink_bf16",
     "fa_attn_varlen_bwd_f16",
     "fa_attn_varlen_bwd_bf16",
+    "fa_attn_bwd_win_f16",
+    "fa_attn_bwd_win_bf16",
+    "fa_attn_bwd_sink_f16",
+    "fa_attn_bwd_sink_bf16",
     "fa_select_config",
     "fa_num_configs",
     "fa_config_info",
@@ -337,6 +341,11 @@ def load_library() -> ctypes.CDLL:
         fn = getattr(lib, "fa_attn_varlen_bwd" + ty)
         fn.argtypes = [vp] * 10 + [i, i, i, i, i, i, ll, ll, ll, ll, vp, vp, i, i, i, vp]
         fn.restype = i
+        # its twins: _win: `int window` after causal; _sink: then `sinks, dsinks` last
+        for variant, last in (("_win", []), ("_sink", [vp, vp])):
+            tw = getattr(lib, "fa_attn_bwd" + variant + ty)
+            tw.argtypes = fn.argtypes[:-1] + [i, vp] + last
+            tw.restype = i
     lib.fa_decode_num_splits.argtypes = [i, i, i, i, i, i]
     lib.fa_decode_num_splits.restype = i
     lib.fa_decode_ws_bytes.argtypes = [i, i, i, i, i, i, i]
@@ -1566,11 +1575,12 @@ def flash_attention_bshd(q, k, v, causal: bool = False, out=None, return_lse: bo
     return (out, lse.view(hq, b, sq).permute(1, 0, 2)) if return_lse else out
 
 
-def _check_attn_bwd(dout, q, k, v, out, lse, rank, cu_q, cu_k, dq, dk, dv):
+def _check_attn_bwd(dout, q, k, v, out, lse, rank, cu_q, cu_k, dq, dk, dv, sinks=None, dsinks=None):
     """What the two backward functions check on top of _check_attn (which sees
-    q, k, v and the forward's out): dout under q's stride rule, the LSE's
-    layout, and the three gradients (allocated when None).  Returns the four
-    token strides (dout's first) and dq, dk, dv."""
+    q, k, v, the forward's out and its sinks): dout under q's stride rule, the
+    LSE's layout, and the gradients (allocated when None; dsinks only with
+    sinks).  Returns the four token strides (dout's first), [dq, dk, dv] and
+    dsinks (None without sinks)."""
     import torch
 
     # dout, lse and the gradients before _check_attn, whose last checks are where
@@ -1605,23 +1615,38 @@ def _check_attn_bwd(dout, q, k, v, out, lse, rank, cu_q, cu_k, dq, dk, dv):
                 raise FlashAttentionError(FA_ERR_BAD_SHAPE,
                                           f"{name} must be a contiguous {q.dtype} tensor shaped like {name[1]}")
             grads.append(t)
-    strides = _check_attn(q, k, v, out, rank, cu_q, cu_k, None)
-    for name, t in (("dout", dout), ("lse", lse), ("dq", grads[0]), ("dk", grads[1]), ("dv", grads[2])):
+        if sinks is None and dsinks is not None:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, "dsinks is the gradient of sinks: it needs sinks")
+        if sinks is not None and dsinks is not None and (
+                not isinstance(dsinks, torch.Tensor) or dsinks.dtype != torch.float32 or dsinks.dim() != 1
+                or dsinks.shape[0] != hq or not dsinks.is_contiguous()):
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"dsinks must be a contiguous float32 [Hq = {hq}] tensor")
+    strides = _check_attn(q, k, v, out, rank, cu_q, cu_k, sinks)
+    if sinks is not None and dsinks is None:
+        dsinks = torch.empty(sinks.shape, dtype=torch.float32, device=q.device)
+    named = [("dout", dout), ("lse", lse), ("dq", grads[0]), ("dk", grads[1]), ("dv", grads[2])]
+    for name, t in named + ([("dsinks", dsinks)] if dsinks is not None else []):
         if not t.is_cuda:
             raise FlashAttentionError(FA_ERR_NULL_POINTER, f"{name} must be a device tensor")
         if t.device != q.device:
             raise FlashAttentionError(FA_ERR_BAD_SHAPE,
                                       f"{name} is on {t.device}, q on {q.device}: one device only")
-    return (do_stride,) + strides, grads
+    return (do_stride,) + strides, grads, dsinks
 
 
 def _attn_bwd_call(dout, q, k, v, out, lse, grads, strides, batch, total_q, total_k, cu_q, cu_k, seqlen_q,
-                   seqlen_k, causal, stream):
+                   seqlen_k, causal, stream, window=0, sinks=None, dsinks=None):
     """The call of the two functions below after their checks: delta (the only
-    workspace), the stream and the fa_attn_varlen_bwd_* entry of q's dtype."""
+    workspace), the stream and the entry of q's dtype: fa_attn_varlen_bwd_*, or
+    with a window fa_attn_bwd_win_*, or with sinks fa_attn_bwd_sink_*."""
     import torch
 
-    name = "fa_attn_varlen_bwd" + ("_bf16" if q.dtype is torch.bfloat16 else "_f16")
+    variant, win = _entry_variant(window, sinks)  # window: checked by the public function
+    last = ()
+    if sinks is not None:
+        win, last = win[:1], win[1:] + (dsinks.data_ptr(),)  # `sinks, dsinks` after the stream
+    name = ("fa_attn_bwd" + variant if variant else "fa_attn_varlen_bwd") + (
+        "_bf16" if q.dtype is torch.bfloat16 else "_f16")
     dev = q.device.index
     delta = torch.empty((q.shape[-2], total_q), dtype=torch.float32, device=q.device)
     if stream is None:
@@ -1637,12 +1662,13 @@ def _attn_bwd_call(dout, q, k, v, out, lse, grads, strides, batch, total_q, tota
                                 q.shape[-1], *strides,
                                 cu_q.data_ptr() if cu_q is not None else None,
                                 cu_k.data_ptr() if cu_k is not None else None, seqlen_q, seqlen_k,
-                                int(bool(causal)), st)
+                                int(bool(causal)), *win, st, *last)
     _check(rc)
 
 
 def flash_attention_varlen_backward(dout, q, k, v, out, lse, cu_seqlens_q, cu_seqlens_k=None,
-                                    causal: bool = False, dq=None, dk=None, dv=None, stream=None):
+                                    causal: bool = False, dq=None, dk=None, dv=None, stream=None,
+                                    window: int = 0, sinks=None, dsinks=None):
     """Backward pass of :func:`flash_attention_varlen` (fa_attn_varlen_bwd_f16 /
     _bf16): the gradients of q, k and v from ``dout`` [T_q, Hq, D], the
     forward's inputs as it took them (views included), its ``out`` and its
@@ -1654,46 +1680,59 @@ def flash_attention_varlen_backward(dout, q, k, v, out, lse, cu_seqlens_q, cu_se
     allocated here).  dq, dk, dv: contiguous tensors shaped like q, k, v, or
     None to allocate.  Returns (dq, dk, dv).  Three launches, no sync, one fp32
     [Hq, T_q] workspace allocated here, graph-capturable, and bit-reproducible:
-    no atomics, no sum across workgroups.  window / sinks have no backward."""
-    strides, grads = _check_attn_bwd(dout, q, k, v, out, lse, 3, cu_seqlens_q, cu_seqlens_k, dq, dk, dv)
+    no atomics, no sum across workgroups.
+    window, sinks: the forward's, whose out and lse these are
+    (fa_attn_bwd_win_* / fa_attn_bwd_sink_*).  With a window the kernels walk
+    the band, and a key no row sees gets dk = dv = 0.  With sinks (float32
+    [Hq]) the return is (dq, dk, dv, dsinks): dsinks float32 [Hq], the
+    gradient of the sinks, from a fourth launch in one fixed order (dsinks: a
+    contiguous float32 [Hq] tensor to write, or None to allocate)."""
+    window = _check_window(window, causal)  # before the tensors, as in the forward
+    strides, grads, dsinks = _check_attn_bwd(dout, q, k, v, out, lse, 3, cu_seqlens_q, cu_seqlens_k, dq, dk,
+                                             dv, sinks, dsinks)
     _attn_bwd_call(dout, q, k, v, out, lse, grads, strides, cu_seqlens_q.shape[0] - 1, q.shape[0],
-                   k.shape[0], cu_seqlens_q, cu_seqlens_k, 0, 0, causal, stream)
-    return tuple(grads)
+                   k.shape[0], cu_seqlens_q, cu_seqlens_k, 0, 0, causal, stream, window, sinks, dsinks)
+    return tuple(grads) if sinks is None else (*grads, dsinks)
 
 
 def flash_attention_bshd_backward(dout, q, k, v, out, lse, causal: bool = False, dq=None, dk=None, dv=None,
-                                  stream=None):
+                                  stream=None, window: int = 0, sinks=None, dsinks=None):
     """:func:`flash_attention_varlen_backward` for uniform lengths, the backward
     of :func:`flash_attention_bshd`: dout and q [B, Sq, Hq, D], k and v [B, Sk,
     Hkv, D], ``lse`` the [B, Hq, Sq] view that function returned (that view of
     a [Hq, B * Sq] buffer and no other layout).  Equals the packed function on
-    cu_seqlens = arange(B + 1) * S bit for bit.  Returns (dq, dk, dv)."""
-    strides, grads = _check_attn_bwd(dout, q, k, v, out, lse, 4, None, None, dq, dk, dv)
+    cu_seqlens = arange(B + 1) * S bit for bit.  Returns (dq, dk, dv), or with
+    sinks (dq, dk, dv, dsinks); window, sinks, dsinks: as for that function."""
+    window = _check_window(window, causal)  # before the tensors, as in the forward
+    strides, grads, dsinks = _check_attn_bwd(dout, q, k, v, out, lse, 4, None, None, dq, dk, dv, sinks,
+                                             dsinks)
     b, sq = q.shape[0], q.shape[1]
     sk = k.shape[1]
     _attn_bwd_call(dout, q, k, v, out, lse, grads, strides, b, b * sq, b * sk, None, None, sq, sk, causal,
-                   stream)
-    return tuple(grads)
+                   stream, window, sinks, dsinks)
+    return tuple(grads) if sinks is None else (*grads, dsinks)
 
 
-def flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k=None, causal: bool = False):
+def flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k=None, causal: bool = False, window: int = 0,
+                           sinks=None):
     """DIFFERENTIABLE attention over packed token-major q [T_q, Hq, D], k and v
     [T_k, Hkv, D], named as in flash-attn: :func:`flash_attention_varlen`
     forward, :func:`flash_attention_varlen_backward` under torch.autograd
     (fa_mi355x.torch_op, imported on first use).  Views as for the forward; a
     dout that fails the stride rule is made contiguous in backward (the one
-    copy).  No window, no sinks, no dropout."""
+    copy).  window, sinks: as for the forward; sinks may be a float32 [Hq]
+    leaf that requires grad, whose .grad is the backward's dsinks.  No dropout."""
     from . import torch_op
 
-    return torch_op.flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, causal)
+    return torch_op.flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, causal, window, sinks)
 
 
-def flash_attn_func(q, k, v, causal: bool = False):
+def flash_attn_func(q, k, v, causal: bool = False, window: int = 0, sinks=None):
     """:func:`flash_attn_varlen_func` for uniform lengths: q [B, Sq, Hq, D], k and
     v [B, Sk, Hkv, D] (:func:`flash_attention_bshd` and its backward)."""
     from . import torch_op
 
-    return torch_op.flash_attn_func(q, k, v, causal)
+    return torch_op.flash_attn_func(q, k, v, causal, window, sinks)
 
 
 def _append_varlen(k_new, v_new, k, v, block_table, names, cu_seqlens, kv_lens, k_scale, v_scale, stream):

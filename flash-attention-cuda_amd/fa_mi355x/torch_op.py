@@ -19,7 +19,10 @@ rank 3: the wrapper that puts the kernel beside PyTorch SDPA on one box).
     o = torch.ops.fa_mi355x.attn_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, causal=False)  # [T,H,D], no cache
     o = torch.ops.fa_mi355x.attn_bshd(q, k, v, causal=True)  # [B,S,H,D], no cache
     dq, dk, dv = torch.ops.fa_mi355x.attn_varlen_bwd(dout, q, k, v, out, lse, cu_seqlens_q, cu_seqlens_k)
+    dq, dk, dv, dsinks = torch.ops.fa_mi355x.attn_varlen_bwd(dout, q, k, v, out, lse, cu_seqlens_q, cu_seqlens_k,
+                                                             True, window, sinks)  # the .sinks overload
     o = fa_mi355x.flash_attn_varlen_func(q, k, v, cu_seqlens_q)  # differentiable (torch.autograd)
+    o = fa_mi355x.flash_attn_varlen_func(q, k, v, cu_seqlens_q, causal=True, window=128, sinks=sinks)
 
 ``q, k, v``: fp16 or bf16 ``[B, H, S, D]`` (D = 128 or 64) tensors on the GPU (BHSD, the
 reference layout, flash_attention.cu:119-122); returns a new tensor of the same shape and dtype.
@@ -699,6 +702,10 @@ attn_bshd = torch.ops.fa_mi355x.attn_bshd
 # / attn_bshd_bwd(dout, q, k, v, out, lse, ...) return (dq, dk, dv):
 # fa_mi355x.flash_attention_varlen_backward / flash_attention_bshd_backward.
 # Everything is taken as it is (views under the stride rule, nothing copied).
+# Each of the four has a `.window` overload (then `int window=0`) and a `.sinks`
+# overload (then `Tensor? sinks=None`), registered after the base schema as for
+# attn_varlen above; the `.sinks` backward returns (dq, dk, dv, dsinks), dsinks
+# float32 [Hq] (zeros when sinks is None).
 # attn_varlen / attn_bshd above stay forward-only and keep raising on inputs
 # that require grad; the differentiable entry points are flash_attn_varlen_func
 # and flash_attn_func below.
@@ -709,8 +716,8 @@ def _attn_grad_ops(name, fwd_fn, bwd_fn, mid, rank):
     arguments between v (forward) / lse (backward) and `causal`."""
     mid_names = [a.split()[-1].split("=")[0] for a in mid]
     layout = "[T, H, 64|128]" if rank == 3 else "[B, S, H, 64|128]"
-    fwd_names = ["q", "k", "v"] + mid_names + ["causal"]
-    bwd_names = ["dout", "q", "k", "v", "out", "lse"] + mid_names + ["causal"]
+    fwd_names = ["q", "k", "v"] + mid_names + ["causal", "window", "sinks"]
+    bwd_names = ["dout", "q", "k", "v", "out", "lse"] + mid_names + ["causal", "window", "sinks"]
 
     def check(q, k, v, vals):
         torch._check(q.dim() == rank and q.shape[-1] in (64, 128), lambda: "expected q " + layout)
@@ -719,11 +726,15 @@ def _attn_grad_ops(name, fwd_fn, bwd_fn, mid, rank):
         torch._check(q.dtype in (torch.float16, torch.bfloat16), lambda: "expected fp16 or bf16")
         if rank == 3:
             torch._check(vals["cu_seqlens_q"].dim() == 1, lambda: "expected a [B + 1] cu_seqlens_q")
+        torch._check(vals.get("window", 0) >= 0, lambda: "expected window >= 0")
+        sinks = vals.get("sinks")
+        torch._check(sinks is None or (sinks.dim() == 1 and sinks.dtype == torch.float32),
+                     lambda: "expected a float32 [Hq] sinks")
 
     def bind(names, args, kw):
         vals = dict(zip(names, args))
         vals.update(kw)
-        for n in mid_names:
+        for n in mid_names + ["sinks"]:
             if isinstance(vals.get(n), torch.Tensor):
                 vals[n] = vals[n].contiguous()
         return vals
@@ -747,6 +758,18 @@ def _attn_grad_ops(name, fwd_fn, bwd_fn, mid, rank):
     def bwd_gpu(*args, **kw):
         return bwd_fn(**bind(bwd_names, args, kw))
 
+    def new_dsinks(q):
+        return torch.empty((q.shape[-2],), dtype=torch.float32, device=q.device)
+
+    def bwd_sinks_gpu(*args, **kw):
+        vals = bind(bwd_names, args, kw)
+        g = bwd_fn(**vals)
+        # four tensors whatever `sinks` is: without sinks their gradient is zeros
+        return g if len(g) == 4 else (*g, new_dsinks(vals["q"]).zero_())
+
+    def bwd_sinks_fake(*args, **kw):
+        return (*bwd_fake(*args, **kw), new_dsinks(bind(bwd_names, args, kw)["q"]))
+
     def bwd_fake(*args, **kw):
         vals = bind(bwd_names, args, kw)
         q, k, v = vals["q"], vals["k"], vals["v"]
@@ -762,15 +785,19 @@ def _attn_grad_ops(name, fwd_fn, bwd_fn, mid, rank):
             raise ValueError("fa_mi355x::%s needs GPU tensors (no CPU path)" % full)
         return cpu
 
-    tail = ", ".join(mid + ["bool causal=False"])
-    for full, schema, gpu, fake in (
-            (name + "_fwd", "Tensor q, Tensor k, Tensor v, %s) -> (Tensor, Tensor)" % tail, fwd_gpu, fwd_fake),
-            (name + "_bwd", "Tensor dout, Tensor q, Tensor k, Tensor v, Tensor out, Tensor lse, %s) -> "
-                            "(Tensor, Tensor, Tensor)" % tail, bwd_gpu, bwd_fake)):
-        _LIB.define(full + "(" + schema)
-        _LIB.impl(full, gpu, "CUDA")
-        _LIB.impl(full, cpu_of(full), "CPU")
-        torch.library.register_fake("fa_mi355x::" + full, fake, lib=_LIB)
+    for overload, more in (("", []), (".window", ["int window=0"]),
+                           (".sinks", ["int window=0", "Tensor? sinks=None"])):
+        tail = ", ".join(mid + ["bool causal=False"] + more)
+        four = overload == ".sinks"
+        for full, schema, gpu, fake in (
+                (name + "_fwd", "Tensor q, Tensor k, Tensor v, %s) -> (Tensor, Tensor)" % tail, fwd_gpu, fwd_fake),
+                (name + "_bwd", "Tensor dout, Tensor q, Tensor k, Tensor v, Tensor out, Tensor lse, %s) -> "
+                                "(Tensor, Tensor, Tensor%s)" % (tail, ", Tensor" if four else ""),
+                 bwd_sinks_gpu if four else bwd_gpu, bwd_sinks_fake if four else bwd_fake)):
+            _LIB.define(full + overload + "(" + schema)
+            _LIB.impl(full + overload, gpu, "CUDA")
+            _LIB.impl(full + overload, cpu_of(full), "CPU")
+            torch.library.register_fake("fa_mi355x::" + full + overload, fake, lib=_LIB)
 
 
 _attn_grad_ops("attn_varlen", flash_attention_varlen, flash_attention_varlen_backward,
@@ -824,11 +851,61 @@ class _FlashAttn(torch.autograd.Function):
         return dq, dk, dv, None
 
 
-def flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k=None, causal: bool = False):
+# With a window or sinks: the same two Functions over the `.window` / `.sinks`
+# overloads.  `sinks` is a differentiable input; its gradient is the backward's dsinks.
+
+
+def _masked_forward(ctx, op, args, causal, window, sinks):
+    """The `.window` / `.sinks` overload of a forward op; saves what its backward reads."""
+    last = () if sinks is None else (sinks,)
+    out, lse = (op.window if sinks is None else op.sinks)(*args, causal, window, *last)
+    ctx.save_for_backward(*args[:3], out, lse, *args[3:], *last)
+    ctx.causal, ctx.window, ctx.has_sinks = causal, window, sinks is not None
+    return out
+
+
+def _masked_backward(ctx, op, dout, rank):
+    """(dq, dk, dv, dsinks or None) of the `.window` / `.sinks` overload of a backward op."""
+    saved = ctx.saved_tensors
+    last = (saved[-1],) if ctx.has_sinks else ()
+    rest = saved[:len(saved) - len(last)]
+    g = (op.sinks if ctx.has_sinks else op.window)(_dout_as_given_or_dense(dout, rank), *rest, ctx.causal,
+                                                   ctx.window, *last)
+    return g if ctx.has_sinks else (*g, None)
+
+
+class _FlashAttnVarlenMasked(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, cu_seqlens_q, cu_seqlens_k, causal, window, sinks):
+        return _masked_forward(ctx, attn_varlen_fwd, (q, k, v, cu_seqlens_q, cu_seqlens_k), causal, window, sinks)
+
+    @staticmethod
+    def backward(ctx, dout):
+        dq, dk, dv, dsinks = _masked_backward(ctx, attn_varlen_bwd, dout, 3)
+        return dq, dk, dv, None, None, None, None, dsinks
+
+
+class _FlashAttnMasked(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, causal, window, sinks):
+        return _masked_forward(ctx, attn_bshd_fwd, (q, k, v), causal, window, sinks)
+
+    @staticmethod
+    def backward(ctx, dout):
+        dq, dk, dv, dsinks = _masked_backward(ctx, attn_bshd_bwd, dout, 4)
+        return dq, dk, dv, None, None, dsinks
+
+
+def flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k=None, causal: bool = False, window: int = 0,
+                           sinks=None):
     """Differentiable fa_mi355x.flash_attention_varlen (see fa_mi355x.flash_attn_varlen_func)."""
-    return _FlashAttnVarlen.apply(q, k, v, cu_seqlens_q, cu_seqlens_k, bool(causal))
+    if window == 0 and sinks is None:
+        return _FlashAttnVarlen.apply(q, k, v, cu_seqlens_q, cu_seqlens_k, bool(causal))
+    return _FlashAttnVarlenMasked.apply(q, k, v, cu_seqlens_q, cu_seqlens_k, bool(causal), window, sinks)
 
 
-def flash_attn_func(q, k, v, causal: bool = False):
+def flash_attn_func(q, k, v, causal: bool = False, window: int = 0, sinks=None):
     """Differentiable fa_mi355x.flash_attention_bshd (see fa_mi355x.flash_attn_func)."""
-    return _FlashAttn.apply(q, k, v, bool(causal))
+    if window == 0 and sinks is None:
+        return _FlashAttn.apply(q, k, v, bool(causal))
+    return _FlashAttnMasked.apply(q, k, v, bool(causal), window, sinks)

@@ -1206,6 +1206,64 @@ int fa_attn_varlen_bwd_bf16(const void* dout, const void* q, const void* k, cons
                             const int* cu_seqlens_q, const int* cu_seqlens_k, int seqlen_q, int seqlen_k,
                             int causal, void* hip_stream);
 
+/* Backward pass of fa_attn_varlen_win_* and fa_attn_varlen_sink_* (DESIGN.md
+ * §3.0r): fa_attn_varlen_bwd_*'s arguments with `int window` after `causal`,
+ * and for the sink entries `sinks` and `dsinks` after the stream.
+ *
+ *   window: the forward's.  0: none; W >= 1: row t of sequence b sees the keys
+ *     [max(0, nk_b - nq_b + t - W + 1), nk_b - nq_b + t], causal only.  P is 0
+ *     on every other key, the formulas above are unchanged, and the kernels walk
+ *     the band: a key block's sweep over the query tiles ends with the last row
+ *     whose window reaches it, a query block's sweep over the key tiles starts
+ *     at its first row's first key, and K/V tiles wholly below a block's window
+ *     are never loaded.  A key no row sees (nk_b > nq_b + W - 1) gets dk = dv =
+ *     0, written.
+ *   sinks: float32 [heads_q], the forward's (lse holds them; NULL: none).  The
+ *     sink is one more softmax column with a zero value, so dq, dk and dv are
+ *     the formulas above on that lse, and
+ *   dsinks: float32 [heads_q], written (never accumulated into):
+ *       dsinks[h] = - sum_i exp(sinks[h] - lse[h][i]) delta[h][i]
+ *     over the rows of head h that belong to a sequence, in fp32 and in one
+ *     fixed order (a fourth launch of heads_q workgroups, no atomics).  A row
+ *     whose lse is -inf adds nothing; sinks[h] = -inf gives dsinks[h] = 0.
+ *     Required with sinks.  sinks == NULL: dsinks may be NULL and is zero-filled
+ *     if it is given.
+ *
+ * Bit for bit: _win with window 0, or causal with a window no shorter than
+ * every sequence's keys, is fa_attn_varlen_bwd_*; _sink with sinks == NULL is
+ * _win; _sink with every sink -inf gives _win's dq, dk, dv and dsinks = 0.
+ *
+ * Statuses: fa_attn_varlen_bwd_*'s, in the forward's order with window < 0
+ * after the negative counts and window > 0 without causal after total_q
+ * (FA_ERR_BAD_SHAPE); the empty problems (batch == 0, total_q == 0, total_k ==
+ * 0) also zero-fill dsinks where it is given; total_q + total_k > INT_MAX
+ * FA_ERR_BAD_SHAPE with the other 32-bit ranges; sinks without dsinks
+ * FA_ERR_NULL_POINTER, last. */
+int fa_attn_bwd_win_f16(const void* dout, const void* q, const void* k, const void* v, const void* out,
+                        const float* lse, void* dq, void* dk, void* dv, float* delta, int batch,
+                        int heads_q, int heads_kv, int total_q, int total_k, int head_dim,
+                        long long do_stride, long long q_stride, long long k_stride, long long v_stride,
+                        const int* cu_seqlens_q, const int* cu_seqlens_k, int seqlen_q, int seqlen_k,
+                        int causal, int window, void* hip_stream);
+int fa_attn_bwd_win_bf16(const void* dout, const void* q, const void* k, const void* v, const void* out,
+                         const float* lse, void* dq, void* dk, void* dv, float* delta, int batch,
+                         int heads_q, int heads_kv, int total_q, int total_k, int head_dim,
+                         long long do_stride, long long q_stride, long long k_stride, long long v_stride,
+                         const int* cu_seqlens_q, const int* cu_seqlens_k, int seqlen_q, int seqlen_k,
+                         int causal, int window, void* hip_stream);
+int fa_attn_bwd_sink_f16(const void* dout, const void* q, const void* k, const void* v, const void* out,
+                         const float* lse, void* dq, void* dk, void* dv, float* delta, int batch,
+                         int heads_q, int heads_kv, int total_q, int total_k, int head_dim,
+                         long long do_stride, long long q_stride, long long k_stride, long long v_stride,
+                         const int* cu_seqlens_q, const int* cu_seqlens_k, int seqlen_q, int seqlen_k,
+                         int causal, int window, void* hip_stream, const float* sinks, float* dsinks);
+int fa_attn_bwd_sink_bf16(const void* dout, const void* q, const void* k, const void* v, const void* out,
+                          const float* lse, void* dq, void* dk, void* dv, float* delta, int batch,
+                          int heads_q, int heads_kv, int total_q, int total_k, int head_dim,
+                          long long do_stride, long long q_stride, long long k_stride, long long v_stride,
+                          const int* cu_seqlens_q, const int* cu_seqlens_k, int seqlen_q, int seqlen_k,
+                          int causal, int window, void* hip_stream, const float* sinks, float* dsinks);
+
 /* The dispatcher's decision (ref tier table :620-661): config id used by
  * fa_fwd_f16 for this shape.  The _ws entries may run the causal split tier
  * instead: check fa_fwd_split_pieces() first (> 0: the split tier runs with
