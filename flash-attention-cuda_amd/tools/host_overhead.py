@@ -1,7 +1,9 @@
 """Host-side cost per call of each entry path, on a shape whose kernel is far
 shorter than the call (B=1 H=1 S=128, D=128): what a short launch pays before
-the GPU sees it.  Prints one JSON line per path (microseconds per call, wall
-clock over N back-to-back calls, then one synchronize).
+the GPU sees it; for the op layer also a cache op (decode, one token of two
+heads over a cache of capacity 256) through its default overload and through
+its `.window` overload.  Prints one JSON line per path (microseconds per call,
+wall clock over N back-to-back calls, then one synchronize).
 
 usage: python tools/host_overhead.py [--calls 3000]"""
 import argparse
@@ -25,6 +27,10 @@ a = ap.parse_args()
 
 q, k, v = (torch.randn(1, 1, a.seq, 128, dtype=torch.float16, device="cuda") for _ in range(3))
 o = torch.empty_like(q)
+# decode: one token of two heads over a full cache of capacity 256
+qd = torch.randn(1, 2, 1, 128, dtype=torch.float16, device="cuda")
+kc, vc = (torch.randn(1, 2, 256, 128, dtype=torch.float16, device="cuda") for _ in range(2))
+kv_lens = torch.full((1,), 256, dtype=torch.int32, device="cuda")
 lib = fa.load_library()
 raw = (ctypes.c_void_p(q.data_ptr()), ctypes.c_void_p(k.data_ptr()), ctypes.c_void_p(v.data_ptr()),
        ctypes.c_void_p(o.data_ptr()), 1, 1, a.seq, 128, 1,
@@ -44,6 +50,9 @@ paths = {
     "torch.ops.fa_mi355x.fwd": lambda: torch.ops.fa_mi355x.fwd(q, k, v, True),
     "torch.ops.fa_mi355x_customop.fwd (custom_op twin)": lambda: torch.ops.fa_mi355x_customop.fwd(q, k, v, True),
     "sdpa": lambda: F.scaled_dot_product_attention(q, k, v, is_causal=True),
+    # a cache op through its default overload and through a later one (resolved by the packet)
+    "torch.ops.fa_mi355x.decode": lambda: torch.ops.fa_mi355x.decode(qd, kc, vc, kv_lens, True),
+    "torch.ops.fa_mi355x.decode.window": lambda: torch.ops.fa_mi355x.decode(qd, kc, vc, kv_lens, True, window=128),
 }
 for name, fn in paths.items():
     for _ in range(200):
