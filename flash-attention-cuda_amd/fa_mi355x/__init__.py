@@ -31,144 +31,8 @@ FA_ERR_BAD_CONFIG = 5
 FA_ERR_HIP = 6
 FA_ERR_WORKSPACE = 7
 
-# every symbol include/fa_mi355x.h declares (tests check the .so exports them)
 FA_DTYPE_F16 = 0
 FA_DTYPE_BF16 = 1
-
-EXPORTED_SYMBOLS = (
-    "fa_fwd_f16",
-    "fa_fwd_f16_config",
-    "fa_fwd_bf16",
-    "fa_fwd_bf16_config",
-    "fa_fwd_f16_splitkv",
-    "fa_splitkv_num_splits",
-    "fa_splitkv_o_bytes",
-    "fa_splitkv_ml_bytes",
-    "fa_fwd_f16_ws",
-    "fa_fwd_bf16_ws",
-    "fa_fwd_ws_bytes",
-    "fa_fwd_split_pieces",
-    "fa_decode_f16",
-    "fa_decode_bf16",
-    "fa_decode_num_splits",
-    "fa_decode_ws_bytes",
-    "fa_decode_paged_f16",
-    "fa_decode_paged_bf16",
-    "fa_decode_kv8_f16",
-    "fa_decode_kv8_bf16",
-    "fa_decode_paged_kv8_f16",
-    "fa_decode_paged_kv8_bf16",
-    "fa_cache_append_16",
-    "fa_cache_append_paged_16",
-    "fa_cache_append_kv8_f16",
-    "fa_cache_append_kv8_bf16",
-    "fa_cache_append_paged_kv8_f16",
-    "fa_cache_append_paged_kv8_bf16",
-    "fa_prefill_f16",
-    "fa_prefill_bf16",
-    "fa_prefill_paged_f16",
-    "fa_prefill_paged_bf16",
-    "fa_prefill_kv8_f16",
-    "fa_prefill_kv8_bf16",
-    "fa_prefill_paged_kv8_f16",
-    "fa_prefill_paged_kv8_bf16",
-    "fa_prefill_varlen_f16",
-    "fa_prefill_varlen_bf16",
-    "fa_prefill_varlen_paged_f16",
-    "fa_prefill_varlen_paged_bf16",
-    "fa_prefill_varlen_kv8_f16",
-    "fa_prefill_varlen_kv8_bf16",
-    "fa_prefill_varlen_paged_kv8_f16",
-    "fa_prefill_varlen_paged_kv8_bf16",
-    "fa_cache_append_varlen_16",
-    "fa_cache_append_varlen_paged_16",
-    "fa_cache_append_varlen_kv8_f16",
-    "fa_cache_append_varlen_kv8_bf16",
-    "fa_cache_append_varlen_paged_kv8_f16",
-    "fa_cache_append_varlen_paged_kv8_bf16",
-    "fa_decode_win_f16",
-    "fa_decode_win_bf16",
-    "fa_decode_win_paged_f16",
-    "fa_decode_win_paged_bf16",
-    "fa_decode_win_kv8_f16",
-    "fa_decode_win_kv8_bf16",
-    "fa_decode_win_paged_kv8_f16",
-    "fa_decode_win_paged_kv8_bf16",
-    "fa_prefill_win_f16",
-    "fa_prefill_win_bf16",
-    "fa_prefill_win_paged_f16",
-    "fa_prefill_win_paged_bf16",
-    "fa_prefill_win_kv8_f16",
-    "fa_prefill_win_kv8_bf16",
-    "fa_prefill_win_paged_kv8_f16",
-    "fa_prefill_win_paged_kv8_bf16",
-    "fa_prefill_varlen_win_f16",
-    "fa_prefill_varlen_win_bf16",
-    "fa_prefill_varlen_win_paged_f16",
-    "fa_prefill_varlen_win_paged_bf16",
-    "fa_prefill_varlen_win_kv8_f16",
-    "fa_prefill_varlen_win_kv8_bf16",
-    "fa_prefill_varlen_win_paged_kv8_f16",
-    "fa_prefill_varlen_win_paged_kv8_bf16",
-    "fa_decode_sink_f16",
-    "fa_decode_sink_bf16",
-    "fa_decode_sink_paged_f16",
-    "fa_decode_sink_paged_bf16",
-    "fa_decode_sink_kv8_f16",
-    "fa_decode_sink_kv8_bf16",
-    "fa_decode_sink_paged_kv8_f16",
-    "fa_decode_sink_paged_kv8_bf16",
-    "fa_prefill_sink_f16",
-    "fa_prefill_sink_bf16",
-    "fa_prefill_sink_paged_f16",
-    "fa_prefill_sink_paged_bf16",
-    "fa_prefill_sink_kv8_f16",
-    "fa_prefill_sink_kv8_bf16",
-    "fa_prefill_sink_paged_kv8_f16",
-    "fa_prefill_sink_paged_kv8_bf16",
-    "fa_prefill_varlen_sink_f16",
-    "fa_prefill_varlen_sink_bf16",
-    "fa_prefill_varlen_sink_paged_f16",
-    "fa_prefill_varlen_sink_paged_bf16",
-    "fa_prefill_varlen_sink_kv8_f16",
-    "fa_prefill_varlen_sink_kv8_bf16",
-    "fa_prefill_varlen_sink_paged_kv8_f16",
-    "fa_prefill_varlen_sink_paged_kv8_bf16",
-    "fa_rope_append_f16",
-    "fa_rope_append_bf16",
-    "fa_rope_append_paged_f16",
-    "fa_rope_append_paged_bf16",
-    "fa_rope_append_kv8_f16",
-    "fa_rope_append_kv8_bf16",
-    "fa_rope_append_paged_kv8_f16",
-    "fa_rope_append_paged_kv8_bf16",
-    "fa_rope_append_varlen_f16",
-    "fa_rope_append_varlen_bf16",
-    "fa_rope_append_varlen_paged_f16",
-    "fa_rope_append_varlen_paged_bf16",
-    "fa_rope_append_varlen_kv8_f16",
-    "fa_rope_append_varlen_kv8_bf16",
-    "fa_rope_append_varlen_paged_kv8_f16",
-    "fa_rope_append_varlen_paged_kv8_bf16",
-    "fa_attn_varlen_f16",
-    "fa_attn_varlen_bf16",
-    "fa_attn_varlen_win_f16",
-    "fa_attn_varlen_win_bf16",
-    "fa_attn_varlen_sink_f16",
-    "fa_attn_varlen_sink_bf16",
-    "fa_attn_varlen_bwd_f16",
-    "fa_attn_varlen_bwd_bf16",
-    "fa_attn_bwd_win_f16",
-    "fa_attn_bwd_win_bf16",
-    "fa_attn_bwd_sink_f16",
-    "fa_attn_bwd_sink_bf16",
-    "fa_select_config",
-    "fa_num_configs",
-    "fa_config_info",
-    "fa_kernel_attrs",
-    "fa_status_string",
-    "fa_version",
-)
 
 
 class FlashAttentionError(RuntimeError):
@@ -204,6 +68,92 @@ class _KernelAttrs(ctypes.Structure):
     ]
 
 
+_I, _P, _LL, _ULL = ctypes.c_int, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_ulonglong
+
+# The launch entries' argument groups, as the macros that stamp the entries on
+# the C side name them (csrc/fa_decode_host.hpp): a family below is one line of
+# groups in C order, and no list is made from another entry's list.
+_QKVO_LSE = [_P] * 5               # q, k, v, o, lse
+_CACHE = {"": [_I, _I],            # CONTIG: kv_capacity, head_dim
+          "_paged": [_I, _I, _I, _P, _I]}  # PAGED: head_dim, num_pages, page_size, block_table, max_pages_per_seq
+_WINDOW = {"": [], "_win": [_I], "_sink": [_I]}       # PLAIN | WIN | SINK: window
+_SINKS = {"": [], "_win": [], "_sink": [_P]}          # ... sinks
+_BWD_SINKS = {"": [], "_win": [], "_sink": [_P, _P]}  # ... sinks, dsinks (the backward)
+_SCALES = {"": [], "_kv8": [_P, _P]}                  # KV16 | KV8: k_scale, v_scale
+_APPEND_HEAD = [_P] * 4 + [_I] * 3  # k_new, v_new, k_cache, v_cache, batch, heads_kv, seqlen_new / total_new
+_ROPE_TAIL = [_P, _P, _I, _P, _P, _I, _I, _I]  # q, q_out, heads_q, cos, sin, rope_len, rotary_dim, interleaved
+_STRIDES = [_LL] * 3               # the token strides of q, k, v
+_BWD_PTRS = [_P] * 10              # dout, q, k, v, out, lse, dq, dk, dv, delta
+_ATTN_DIMS = [_I] * 6              # batch, heads_q, heads_kv, total_q, total_k, head_dim
+_ATTN_SEQS = [_P, _P, _I, _I, _I]  # cu_seqlens_q, cu_seqlens_k, seqlen_q, seqlen_k, causal
+_STREAM = [_P]
+# the families whose two 16-bit cache forms have one entry for both element types, `_16`
+_ONE_16 = ("fa_cache_append", "fa_cache_append_varlen")
+
+
+def _c_entries():
+    """name -> (restype, argtypes) of every function include/fa_mi355x.h declares."""
+    fwd = [_P] * 4 + [_I] * 5  # q, k, v, o, batch, heads, seq_len, head_dim, causal
+    table = {
+        "fa_fwd_f16": (_I, fwd + _STREAM),
+        "fa_fwd_bf16": (_I, fwd + _STREAM),
+        "fa_fwd_f16_config": (_I, fwd + [_I] + _STREAM),
+        "fa_fwd_bf16_config": (_I, fwd + [_I] + _STREAM),
+        "fa_fwd_f16_splitkv": (_I, fwd + [_I, _P, _P] + _STREAM),
+        "fa_splitkv_num_splits": (_I, [_I] * 4),
+        "fa_splitkv_o_bytes": (_ULL, [_I] * 5),
+        "fa_splitkv_ml_bytes": (_ULL, [_I] * 5),
+        "fa_fwd_f16_ws": (_I, fwd + [_I, _P, _ULL] + _STREAM),
+        "fa_fwd_bf16_ws": (_I, fwd + [_I, _P, _ULL] + _STREAM),
+        "fa_fwd_ws_bytes": (_ULL, [_I] * 6),
+        "fa_fwd_split_pieces": (_I, [_I] * 5),
+        "fa_decode_num_splits": (_I, [_I] * 6),
+        "fa_decode_ws_bytes": (_ULL, [_I] * 7),
+        "fa_select_config": (_I, [_I] * 4),
+        "fa_num_configs": (_I, []),
+        "fa_config_info": (_I, [_I, ctypes.POINTER(_ConfigInfo)]),
+        "fa_kernel_attrs": (_I, [_I, ctypes.POINTER(_KernelAttrs)]),
+        "fa_status_string": (ctypes.c_char_p, [_I]),
+        "fa_version": (ctypes.c_char_p, []),
+    }
+    plain, variants = ("",), ("", "_win", "_sink")
+    no_cache = (("", ""),)
+    caches = tuple((c, s) for c in ("", "_paged") for s in ("", "_kv8"))
+
+    def bwd(v, c, s):  # (dout's stride before the three)
+        return _BWD_PTRS + _ATTN_DIMS + [_LL] + _STRIDES + _ATTN_SEQS + _WINDOW[v] + _STREAM + _BWD_SINKS[v]
+
+    # families, variants, cache forms, and the arguments of variant v over cache form c with scales s
+    for families, vs, forms, args in (
+        (("fa_decode",), variants, caches, lambda v, c, s: (
+            _QKVO_LSE + [_I] * 4 + _CACHE[c] + [_P, _I] + _WINDOW[v] + _SINKS[v] + [_I, _P, _ULL] + _STREAM
+            + _SCALES[s])),  # (batch, heads_q, heads_kv, seqlen_q; kv_lens, causal; num_splits, ws, ws_bytes)
+        (("fa_prefill", "fa_prefill_varlen"), variants, caches, lambda v, c, s: (
+            _QKVO_LSE + [_I] * 4 + _CACHE[c] + [_P, _P, _I] + _WINDOW[v] + _SINKS[v] + _STREAM
+            + _SCALES[s])),  # (...; kv_lens, q_lens / cu_seqlens_q, causal)
+        (_ONE_16, plain, caches, lambda v, c, s: (
+            _APPEND_HEAD + _CACHE[c] + [_P, _P] + _STREAM + _SCALES[s])),  # (kv_lens, new_lens / cu_seqlens)
+        (("fa_rope_append", "fa_rope_append_varlen"), plain, caches, lambda v, c, s: (
+            _APPEND_HEAD + _CACHE[c] + [_P, _P] + _STREAM + _SCALES[s] + _ROPE_TAIL)),
+        (("fa_attn_varlen",), variants, no_cache, lambda v, c, s: (
+            _QKVO_LSE + _ATTN_DIMS + _STRIDES + _ATTN_SEQS + _WINDOW[v] + _STREAM + _SINKS[v])),
+        (("fa_attn_varlen_bwd",), plain, no_cache, bwd),
+        (("fa_attn_bwd",), ("_win", "_sink"), no_cache, bwd),
+    ):
+        for family in families:
+            for v in vs:
+                for c, s in forms:
+                    for ty in ("_16",) if family in _ONE_16 and not s else ("_f16", "_bf16"):
+                        table[family + v + c + s + ty] = (_I, args(v, c, s))  # as _entry_name composes it
+    return table
+
+
+# every function include/fa_mi355x.h declares: name -> (restype, argtypes); the
+# tests check it against the header and that the .so exports every name
+C_ENTRIES = _c_entries()
+EXPORTED_SYMBOLS = tuple(C_ENTRIES)
+
+
 @dataclass(frozen=True)
 class TileConfig:
     id: int
@@ -236,133 +186,9 @@ def load_library() -> ctypes.CDLL:
             f"{LIB_PATH} not built (run `make -C {PKG_ROOT}` or __graft_entry__.build())",
         )
     lib = ctypes.CDLL(LIB_PATH)
-    vp, i, f = ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_float)
-    ull = ctypes.c_ulonglong
-    lib.fa_fwd_f16.argtypes = [vp, vp, vp, vp, i, i, i, i, i, vp]
-    lib.fa_fwd_f16.restype = i
-    lib.fa_fwd_f16_config.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, vp]
-    lib.fa_fwd_f16_config.restype = i
-    lib.fa_fwd_bf16.argtypes = [vp, vp, vp, vp, i, i, i, i, i, vp]
-    lib.fa_fwd_bf16.restype = i
-    lib.fa_fwd_bf16_config.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, vp]
-    lib.fa_fwd_bf16_config.restype = i
-    lib.fa_fwd_f16_splitkv.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, vp, vp, vp]
-    lib.fa_fwd_f16_splitkv.restype = i
-    lib.fa_splitkv_num_splits.argtypes = [i, i, i, i]
-    lib.fa_splitkv_num_splits.restype = i
-    lib.fa_splitkv_o_bytes.argtypes = [i, i, i, i, i]
-    lib.fa_splitkv_o_bytes.restype = ull
-    lib.fa_splitkv_ml_bytes.argtypes = [i, i, i, i, i]
-    lib.fa_splitkv_ml_bytes.restype = ull
-    lib.fa_fwd_f16_ws.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, vp, ull, vp]
-    lib.fa_fwd_f16_ws.restype = i
-    lib.fa_fwd_bf16_ws.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, vp, ull, vp]
-    lib.fa_fwd_bf16_ws.restype = i
-    lib.fa_fwd_ws_bytes.argtypes = [i, i, i, i, i, i]
-    lib.fa_fwd_ws_bytes.restype = ull
-    lib.fa_fwd_split_pieces.argtypes = [i, i, i, i, i]
-    lib.fa_fwd_split_pieces.restype = i
-    lib.fa_decode_f16.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, vp, i, i, vp, ull, vp]
-    lib.fa_decode_f16.restype = i
-    lib.fa_decode_bf16.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, vp, i, i, vp, ull, vp]
-    lib.fa_decode_bf16.restype = i
-    for fn in (lib.fa_decode_paged_f16, lib.fa_decode_paged_bf16):
-        fn.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, vp, i, vp, i, i, vp, ull, vp]
-        fn.restype = i
-    for fn in (lib.fa_decode_kv8_f16, lib.fa_decode_kv8_bf16):
-        fn.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, vp, i, i, vp, ull, vp, vp, vp]
-        fn.restype = i
-    for fn in (lib.fa_decode_paged_kv8_f16, lib.fa_decode_paged_kv8_bf16):
-        fn.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, vp, i, vp, i, i, vp, ull, vp, vp, vp]
-        fn.restype = i
-    lib.fa_cache_append_16.argtypes = [vp, vp, vp, vp, i, i, i, i, i, vp, vp, vp]
-    lib.fa_cache_append_paged_16.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, vp, i, vp, vp, vp]
-    for fn in (lib.fa_cache_append_kv8_f16, lib.fa_cache_append_kv8_bf16):
-        fn.argtypes = lib.fa_cache_append_16.argtypes + [vp, vp]
-    for fn in (lib.fa_cache_append_paged_kv8_f16, lib.fa_cache_append_paged_kv8_bf16):
-        fn.argtypes = lib.fa_cache_append_paged_16.argtypes + [vp, vp]
-    # the packed (cu_seqlens) twins take the same argument lists
-    lib.fa_cache_append_varlen_16.argtypes = lib.fa_cache_append_16.argtypes
-    lib.fa_cache_append_varlen_paged_16.argtypes = lib.fa_cache_append_paged_16.argtypes
-    for fn in (lib.fa_cache_append_varlen_kv8_f16, lib.fa_cache_append_varlen_kv8_bf16):
-        fn.argtypes = lib.fa_cache_append_kv8_f16.argtypes
-    for fn in (lib.fa_cache_append_varlen_paged_kv8_f16, lib.fa_cache_append_varlen_paged_kv8_bf16):
-        fn.argtypes = lib.fa_cache_append_paged_kv8_f16.argtypes
-    for name in EXPORTED_SYMBOLS:
-        if name.startswith("fa_cache_append"):
-            getattr(lib, name).restype = i
-    # the fused RoPE twins: the append's list (FP8: with the scales), then
-    # q, q_out, heads_q, cos, sin, rope_len, rotary_dim, interleaved
-    for fam in ("", "_varlen"):
-        for form, base in (("", "_16"), ("_paged", "_paged_16"), ("_kv8", "_kv8_f16"),
-                           ("_paged_kv8", "_paged_kv8_f16")):
-            for ty in ("_f16", "_bf16"):
-                fn = getattr(lib, "fa_rope_append" + fam + form + ty)
-                fn.argtypes = getattr(lib, "fa_cache_append" + base).argtypes + [vp, vp, i, vp, vp, i, i, i]
-                fn.restype = i
-    for fn in (lib.fa_prefill_f16, lib.fa_prefill_bf16):
-        fn.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, vp, vp, i, vp]
-    for fn in (lib.fa_prefill_paged_f16, lib.fa_prefill_paged_bf16):
-        fn.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, vp, i, vp, vp, i, vp]
-    for fn in (lib.fa_prefill_kv8_f16, lib.fa_prefill_kv8_bf16):
-        fn.argtypes = lib.fa_prefill_f16.argtypes + [vp, vp]
-    for fn in (lib.fa_prefill_paged_kv8_f16, lib.fa_prefill_paged_kv8_bf16):
-        fn.argtypes = lib.fa_prefill_paged_f16.argtypes + [vp, vp]
-    for form in ("", "_paged", "_kv8", "_paged_kv8"):
-        for ty in ("_f16", "_bf16"):
-            getattr(lib, "fa_prefill_varlen" + form + ty).argtypes = \
-                getattr(lib, "fa_prefill" + form + ty).argtypes
-    for name in EXPORTED_SYMBOLS:
-        if name.startswith("fa_prefill"):
-            getattr(lib, name).restype = i
-    # the sliding-window twins: `int window` directly after `causal`
-    for form in ("", "_paged", "_kv8", "_paged_kv8"):
-        for ty in ("_f16", "_bf16"):
-            for fam, after in (("fa_decode", 4), ("fa_prefill", 1), ("fa_prefill_varlen", 1)):
-                base = getattr(lib, fam + form + ty).argtypes
-                at = len(base) - after - (2 if "kv8" in form else 0)  # causal's successor
-                fn = getattr(lib, fam + "_win" + form + ty)
-                fn.argtypes = base[:at] + [i] + base[at:]
-                fn.restype = i
-                # the attention-sink twins of those: `const float* sinks` directly after `window`
-                fn = getattr(lib, fam + "_sink" + form + ty)
-                fn.argtypes = base[:at] + [i, vp] + base[at:]
-                fn.restype = i
-    # attention over token-major Q, K, V (no cache): three long long strides
-    # after head_dim; _win: `int window` after causal; _sink: `sinks` last
-    ll = ctypes.c_longlong
-    for ty in ("_f16", "_bf16"):
-        head = [vp, vp, vp, vp, vp, i, i, i, i, i, i, ll, ll, ll, vp, vp, i, i, i]
-        for variant, mid, last in (("", [], []), ("_win", [i], []), ("_sink", [i], [vp])):
-            fn = getattr(lib, "fa_attn_varlen" + variant + ty)
-            fn.argtypes = head + mid + [vp] + last
-            fn.restype = i
-        # the backward: dout, q, k, v, out, lse, dq, dk, dv, delta, then four strides
-        fn = getattr(lib, "fa_attn_varlen_bwd" + ty)
-        fn.argtypes = [vp] * 10 + [i, i, i, i, i, i, ll, ll, ll, ll, vp, vp, i, i, i, vp]
-        fn.restype = i
-        # its twins: _win: `int window` after causal; _sink: then `sinks, dsinks` last
-        for variant, last in (("_win", []), ("_sink", [vp, vp])):
-            tw = getattr(lib, "fa_attn_bwd" + variant + ty)
-            tw.argtypes = fn.argtypes[:-1] + [i, vp] + last
-            tw.restype = i
-    lib.fa_decode_num_splits.argtypes = [i, i, i, i, i, i]
-    lib.fa_decode_num_splits.restype = i
-    lib.fa_decode_ws_bytes.argtypes = [i, i, i, i, i, i, i]
-    lib.fa_decode_ws_bytes.restype = ull
-    lib.fa_select_config.argtypes = [i, i, i, i]
-    lib.fa_select_config.restype = i
-    lib.fa_num_configs.argtypes = []
-    lib.fa_num_configs.restype = i
-    lib.fa_config_info.argtypes = [i, ctypes.POINTER(_ConfigInfo)]
-    lib.fa_config_info.restype = i
-    lib.fa_kernel_attrs.argtypes = [i, ctypes.POINTER(_KernelAttrs)]
-    lib.fa_kernel_attrs.restype = i
-    lib.fa_status_string.argtypes = [i]
-    lib.fa_status_string.restype = ctypes.c_char_p
-    lib.fa_version.argtypes = []
-    lib.fa_version.restype = ctypes.c_char_p
-    del f
+    for name, (restype, argtypes) in C_ENTRIES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 
@@ -404,15 +230,59 @@ def kernel_attrs(config_id: int) -> dict:
 _DTYPES_16 = ()  # (torch.float16, torch.bfloat16) once torch is imported (lazily)
 
 
-def _stream_handle(stream, device=None) -> Optional[int]:
-    """Raw hipStream_t of `stream` (None: torch's current stream on `device`)."""
+def _raw_stream(stream, dev: int) -> int:
+    """Raw hipStream_t of `stream` (None: torch's current stream on device `dev`)."""
+    if stream is None:
+        import torch
+
+        return torch._C._cuda_getCurrentRawStream(dev)
+    return stream if isinstance(stream, int) else stream.cuda_stream
+
+
+def _entry(name: str):
+    """The C function `name` of the CURRENT library: looked up on the library
+    object at every call (its own attribute cache dies with it), so a tool that
+    swaps `_lib` is followed by every function here."""
+    return getattr(_lib or load_library(), name)
+
+
+def _entry_name(family: str, variant: str, paged, kv8, bf16) -> str:
+    """The launch entry of a family ("fa_decode"), a variant ("", "_win",
+    "_sink": :func:`_entry_variant`), a cache form and q's element type."""
+    return (family + variant + ("_paged" if paged else "") + ("_kv8" if kv8 else "")
+            + ("_16" if family in _ONE_16 and not kv8 else "_bf16" if bf16 else "_f16"))
+
+
+def _cache_args(k, head_dim: int, block_table) -> tuple:
+    """The entries' cache group: k a contiguous [B,Hkv,cap,D] cache (no block
+    table) or a [num_pages,Hkv,page_size,D] pool."""
+    if block_table is None:
+        return (k.shape[2], head_dim)
+    return (head_dim, k.shape[0], k.shape[2], block_table.data_ptr(), block_table.shape[1])
+
+
+def _scale_args(kv8, k_scale, v_scale) -> tuple:
+    """The kv8 entries' scales group, after the stream (None: 1.0)."""
+    if not kv8:
+        return ()
+    return (k_scale.data_ptr() if k_scale is not None else None,
+            v_scale.data_ptr() if v_scale is not None else None)
+
+
+def _launch(name: str, dev: int, stream, before: tuple, after: tuple = ()) -> None:
+    """Every launch but flash_attention_fwd's: entry `name` with `before`, the
+    stream and `after`, on device `dev` -- the C side launches on (and sizes
+    for) the current device -- and its status raised if nonzero."""
     import torch
 
-    if stream is None:
-        stream = torch.cuda.current_stream(device)
-    if isinstance(stream, int):
-        return stream
-    return stream.cuda_stream
+    fn = _entry(name)
+    st = _raw_stream(stream, dev)
+    if dev == torch._C._cuda_getDevice():
+        rc = fn(*before, st, *after)
+    else:
+        with torch.cuda.device(dev):
+            rc = fn(*before, st, *after)
+    _check(rc)
 
 
 def _check_qkvo(q, k, v, out):
@@ -787,19 +657,15 @@ def _entry_variant(window, sinks):
     return ("_win", (window,)) if window else ("", ())
 
 
-_DEC_ENTRY = {}  # (paged, kv8, bf16, "" / "_win" / "_sink") -> the C entry
-
-
 def _decode_call(kv8, q, k, v, out, block_table, kv_lens, causal, return_lse, num_splits, stream,
                  k_scale, v_scale, window=0, sinks=None):
-    """The call of both decode functions after their checks: the stream, the
-    optional LSE, the split workspace and the C entry of q's dtype.
-    block_table: None when k, v are a contiguous cache (the fa_decode_*
-    entries), the table when they are page pools (the fa_decode_paged_*
-    entries); kv8: the _kv8 entries, which also take the two scales; window >
-    0: the fa_decode_win_* entries, whose plan and workspace follow
-    :func:`decode_window_capacity`; sinks: the fa_decode_sink_* entries, at any
-    window."""
+    """The call of both decode functions after their checks: the optional LSE,
+    the split plan and its workspace, and the fa_decode* entry.
+    block_table: None when k, v are a contiguous cache, the table when they are
+    page pools (the _paged entries); kv8: the _kv8 entries, which also take the
+    two scales; window > 0: the fa_decode_win_* entries, whose plan and
+    workspace follow :func:`decode_window_capacity`; sinks: the
+    fa_decode_sink_* entries, at any window."""
     import torch
 
     variant, win = _entry_variant(window, sinks)  # checked by the public function
@@ -807,46 +673,33 @@ def _decode_call(kv8, q, k, v, out, block_table, kv_lens, causal, return_lse, nu
     hkv, cap = k.shape[1], k.shape[2]
     paged = block_table is not None
     if paged:
-        npages, psz, mpp = k.shape[0], cap, block_table.shape[1]
-        cap = mpp * psz
-        cache = (d, npages, psz, block_table.data_ptr(), mpp)
-    else:
-        cache = (cap, d)
-    lib = _lib or load_library()
-    which = (paged, kv8, q.dtype is torch.bfloat16, variant)
-    fn = _DEC_ENTRY.get(which)
-    if fn is None:
-        fn = _DEC_ENTRY[which] = getattr(lib, "fa_decode" + variant
-                                         + ("_paged" if paged else "")
-                                         + ("_kv8" if kv8 else "") + ("_bf16" if which[2] else "_f16"))
-    tail = ()
-    if kv8:
-        tail = (k_scale.data_ptr() if k_scale is not None else None,
-                v_scale.data_ptr() if v_scale is not None else None)
+        cap *= block_table.shape[1]
     dev = q.device.index
-    if stream is None:
-        st = torch._C._cuda_getCurrentRawStream(dev)
-    else:
-        st = stream if isinstance(stream, int) else stream.cuda_stream
+    st = _raw_stream(stream, dev)
     lse = torch.empty((b, hq, sq), dtype=torch.float32, device=q.device) if return_lse else None
     ns = int(num_splits)
-    with torch.cuda.device(dev):
-        need = 0
-        if not paged or cap <= 0x7fffffff - 64:  # (past it the paged entry itself refuses the shape)
-            # a windowed call plans (and needs a workspace) as for the window's capacity
-            pcap = decode_window_capacity(cap, sq, window)
-            key = (dev, b, hq, hkv, sq, pcap, d, ns)
-            need = _DEC_NEED.get(key)
+    need = 0
+    if not paged or cap <= 0x7fffffff - 64:  # (past it the paged entry itself refuses the shape)
+        # a windowed call plans (and needs a workspace) as for the window's capacity
+        pcap = decode_window_capacity(cap, sq, window)
+        key = (dev, b, hq, hkv, sq, pcap, d, ns)
+        need = _DEC_NEED.get(key)
+    if need is None or need:
+        # on q's device: the plan is the current device's, and _workspace asks
+        # whether the current device's stream is capturing
+        with torch.cuda.device(dev):
             if need is None:
-                need = lib.fa_decode_ws_bytes(b, hq, hkv, sq, pcap, d, ns)
-                _DEC_NEED[key] = need
-        ws = _workspace(need, dev, st) if need else None
-        rc = fn(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
-                lse.data_ptr() if return_lse else None, b, hq, hkv, sq, *cache,
-                kv_lens.data_ptr() if kv_lens is not None else None, int(bool(causal)), *win, ns,
-                ws.data_ptr() if need else None, need, st, *tail)
-    _check(rc)
+                need = _DEC_NEED[key] = _entry("fa_decode_ws_bytes")(b, hq, hkv, sq, pcap, d, ns)
+            ws = _workspace(need, dev, st) if need else None  # (a tensor: alive until the launch)
+    _launch(_entry_name("fa_decode", variant, paged, kv8, q.dtype is torch.bfloat16), dev, st,
+            (q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
+             lse.data_ptr() if return_lse else None, b, hq, hkv, sq, *_cache_args(k, d, block_table),
+             kv_lens.data_ptr() if kv_lens is not None else None, int(bool(causal)), *win, ns,
+             ws.data_ptr() if need else None, need),
+            _scale_args(kv8, k_scale, v_scale))
     return (out, lse) if return_lse else out
+
+
 
 
 def flash_attention_decode(q, k_cache, v_cache, kv_lens=None, causal: bool = True, out=None,
@@ -940,51 +793,35 @@ def flash_attention_decode_paged(q, k_pages, v_pages, block_table, kv_lens=None,
                         num_splits, stream, k_scale, v_scale, window, sinks)
 
 
-_PRE_ENTRY = {}  # (paged, kv8, bf16, "" / "_win" / "_sink") -> the C entry
-
-
-def _prefill_call(kv8, q, k, v, out, block_table, kv_lens, q_lens, causal, return_lse, stream, k_scale,
-                  v_scale, window=0, sinks=None):
-    """The call of both prefill functions after their checks (the twin of
-    :func:`_decode_call`, without a workspace): the stream, the optional LSE
-    and the C entry of the cache form and q's dtype.  The LSE is allocated
-    with empty(): rows past q_lens are not written.  window > 0: the
-    fa_prefill_win_* entries; sinks: the fa_prefill_sink_* entries, at any
+def _prefill_call(family, kv8, q, k, v, out, batch, seqlen_q, block_table, kv_lens, q_lens, causal,
+                  return_lse, stream, k_scale, v_scale, window=0, sinks=None):
+    """The call of the four prefill functions after their checks (the twin of
+    :func:`_decode_call`, without a workspace): the optional LSE and the entry
+    of the cache form and q's dtype.  fa_prefill: q [B,Hq,Sq,D], `batch` B,
+    `seqlen_q` Sq; fa_prefill_varlen: q [T,Hq,D], `batch` the sequences,
+    `seqlen_q` T and `q_lens` the cu_seqlens_q (the lists are one).  The LSE
+    ([B,Hq,Sq] / [Hq,T]) is allocated with empty(): rows past q_lens are not
+    written.  window > 0: the _win entries; sinks: the _sink entries, at any
     window."""
     import torch
 
     variant, win = _entry_variant(window, sinks)  # checked by the public function
-    b, hq, sq, d = q.shape
-    hkv = k.shape[1]
-    paged = block_table is not None
-    if paged:
-        cache = (d, k.shape[0], k.shape[2], block_table.data_ptr(), block_table.shape[1])
-    else:
-        cache = (k.shape[2], d)
-    lib = _lib or load_library()
-    which = (paged, kv8, q.dtype is torch.bfloat16, variant)
-    fn = _PRE_ENTRY.get(which)
-    if fn is None:
-        fn = _PRE_ENTRY[which] = getattr(lib, "fa_prefill" + variant
-                                         + ("_paged" if paged else "")
-                                         + ("_kv8" if kv8 else "") + ("_bf16" if which[2] else "_f16"))
-    tail = ()
-    if kv8:
-        tail = (k_scale.data_ptr() if k_scale is not None else None,
-                v_scale.data_ptr() if v_scale is not None else None)
-    dev = q.device.index
-    if stream is None:
-        st = torch._C._cuda_getCurrentRawStream(dev)
-    else:
-        st = stream if isinstance(stream, int) else stream.cuda_stream
-    lse = torch.empty((b, hq, sq), dtype=torch.float32, device=q.device) if return_lse else None
-    with torch.cuda.device(dev):
-        rc = fn(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
-                lse.data_ptr() if return_lse else None, b, hq, hkv, sq, *cache,
-                kv_lens.data_ptr() if kv_lens is not None else None,
-                q_lens.data_ptr() if q_lens is not None else None, int(bool(causal)), *win, st, *tail)
-    _check(rc)
+    hq = q.shape[1]
+    lse = None
+    if return_lse:
+        lse = torch.empty((batch, hq, seqlen_q) if q.dim() == 4 else (hq, seqlen_q), dtype=torch.float32,
+                          device=q.device)
+    _launch(_entry_name(family, variant, block_table is not None, kv8, q.dtype is torch.bfloat16),
+            q.device.index, stream,
+            (q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
+             lse.data_ptr() if return_lse else None, batch, hq, k.shape[1], seqlen_q,
+             *_cache_args(k, q.shape[-1], block_table),
+             kv_lens.data_ptr() if kv_lens is not None else None,
+             q_lens.data_ptr() if q_lens is not None else None, int(bool(causal)), *win),
+            _scale_args(kv8, k_scale, v_scale))
     return (out, lse) if return_lse else out
+
+
 
 
 def flash_attention_prefill(q, k_cache, v_cache, kv_lens=None, q_lens=None, causal: bool = True,
@@ -1038,8 +875,8 @@ def flash_attention_prefill(q, k_cache, v_cache, kv_lens=None, q_lens=None, caus
 
         out = torch.empty_like(q)
     kv8 = _check_decode(q, k_cache, v_cache, kv_lens, out, k_scale, v_scale, q_lens, sinks)
-    return _prefill_call(kv8, q, k_cache, v_cache, out, None, kv_lens, q_lens, causal, return_lse,
-                         stream, k_scale, v_scale, window, sinks)
+    return _prefill_call("fa_prefill", kv8, q, k_cache, v_cache, out, q.shape[0], q.shape[2], None, kv_lens,
+                         q_lens, causal, return_lse, stream, k_scale, v_scale, window, sinks)
 
 
 def flash_attention_prefill_paged(q, k_pages, v_pages, block_table, kv_lens=None, q_lens=None,
@@ -1069,8 +906,8 @@ def flash_attention_prefill_paged(q, k_pages, v_pages, block_table, kv_lens=None
         out = torch.empty_like(q)
     kv8 = _check_decode_paged(q, k_pages, v_pages, block_table, kv_lens, out, k_scale, v_scale, q_lens,
                               sinks)
-    return _prefill_call(kv8, q, k_pages, v_pages, out, block_table, kv_lens, q_lens, causal,
-                         return_lse, stream, k_scale, v_scale, window, sinks)
+    return _prefill_call("fa_prefill", kv8, q, k_pages, v_pages, out, q.shape[0], q.shape[2], block_table,
+                         kv_lens, q_lens, causal, return_lse, stream, k_scale, v_scale, window, sinks)
 
 
 def _check_append(k_new, v_new, kname, k, vname, v, block_table, kv_lens, new_lens, k_scale, v_scale):
@@ -1131,35 +968,23 @@ def _check_append(k_new, v_new, kname, k, vname, v, block_table, kv_lens, new_le
     return kv8
 
 
-def _append_call(kv8, k_new, v_new, k, v, block_table, kv_lens, new_lens, stream, k_scale, v_scale):
-    """The call of both append functions after their checks (the twin of
-    :func:`_decode_call`): the stream and the C entry of the cache form."""
+def _append_call(family, kv8, k_new, v_new, k, v, batch, seqlen_new, block_table, kv_lens, new_lens, stream,
+                 k_scale, v_scale, rope=()):
+    """The call of the eight append functions after their checks: the entry of
+    the cache form.  fa_cache_append / fa_rope_append: k_new [B,Hkv,Sn,D],
+    `batch` B, `seqlen_new` Sn; their _varlen twins: k_new [T,Hkv,D], `batch`
+    the sequences, `seqlen_new` T and `new_lens` the cu_seqlens (the lists are
+    one).  rope: the fa_rope_append* entries' :func:`_rope_tail`."""
     import torch
 
-    b, hkv, sn, d = k_new.shape
-    if block_table is not None:
-        cache = (d, k.shape[0], k.shape[2], block_table.data_ptr(), block_table.shape[1])
-    else:
-        cache = (k.shape[2], d)
-    lib = _lib or load_library()
-    name = "fa_cache_append" + ("_paged" if block_table is not None else "")
-    tail = ()
-    if kv8:
-        name += "_kv8_bf16" if k_new.dtype is torch.bfloat16 else "_kv8_f16"
-        tail = (k_scale.data_ptr() if k_scale is not None else None,
-                v_scale.data_ptr() if v_scale is not None else None)
-    else:
-        name += "_16"
-    dev = k_new.device.index
-    if stream is None:
-        st = torch._C._cuda_getCurrentRawStream(dev)
-    else:
-        st = stream if isinstance(stream, int) else stream.cuda_stream
-    with torch.cuda.device(dev):
-        rc = getattr(lib, name)(k_new.data_ptr(), v_new.data_ptr(), k.data_ptr(), v.data_ptr(), b, hkv,
-                                sn, *cache, kv_lens.data_ptr(),
-                                new_lens.data_ptr() if new_lens is not None else None, st, *tail)
-    _check(rc)
+    _launch(_entry_name(family, "", block_table is not None, kv8, k_new.dtype is torch.bfloat16),
+            k_new.device.index, stream,
+            (k_new.data_ptr(), v_new.data_ptr(), k.data_ptr(), v.data_ptr(), batch, k_new.shape[1],
+             seqlen_new, *_cache_args(k, k_new.shape[-1], block_table), kv_lens.data_ptr(),
+             new_lens.data_ptr() if new_lens is not None else None),
+            _scale_args(kv8, k_scale, v_scale) + rope)
+
+
 
 
 def flash_attention_cache_append(k_new, v_new, k_cache, v_cache, kv_lens, new_lens=None,
@@ -1186,7 +1011,8 @@ def flash_attention_cache_append(k_new, v_new, k_cache, v_cache, kv_lens, new_le
     """
     kv8 = _check_append(k_new, v_new, "k_cache", k_cache, "v_cache", v_cache, None, kv_lens, new_lens,
                         k_scale, v_scale)
-    _append_call(kv8, k_new, v_new, k_cache, v_cache, None, kv_lens, new_lens, stream, k_scale, v_scale)
+    _append_call("fa_cache_append", kv8, k_new, v_new, k_cache, v_cache, k_new.shape[0], k_new.shape[2], None,
+                 kv_lens, new_lens, stream, k_scale, v_scale)
 
 
 def flash_attention_cache_append_paged(k_new, v_new, k_pages, v_pages, block_table, kv_lens,
@@ -1208,8 +1034,8 @@ def flash_attention_cache_append_paged(k_new, v_new, k_pages, v_pages, block_tab
         raise FlashAttentionError(FA_ERR_NULL_POINTER, "block_table is required")
     kv8 = _check_append(k_new, v_new, "k_pages", k_pages, "v_pages", v_pages, block_table, kv_lens,
                         new_lens, k_scale, v_scale)
-    _append_call(kv8, k_new, v_new, k_pages, v_pages, block_table, kv_lens, new_lens, stream, k_scale,
-                 v_scale)
+    _append_call("fa_cache_append", kv8, k_new, v_new, k_pages, v_pages, k_new.shape[0], k_new.shape[2],
+                 block_table, kv_lens, new_lens, stream, k_scale, v_scale)
 
 
 def _check_cu_seqlens(cu, name, nseq, ref, where):
@@ -1292,56 +1118,16 @@ def _check_packed(x, xname, y, yname, kname, k, vname, v, block_table, cu, cunam
     return kv8, nseq
 
 
-def _packed_call(name, kv8, x, y, extra, nseq, heads, k, v, block_table, kv_lens, cu, mid, stream,
-                 k_scale, v_scale):
-    """The call of the four packed functions after their checks: the stream and
-    the C entry `name`.  x: the first packed tensor (q or k_new); y: the
-    pointers between it and the caches (append: v_new); extra: those between
-    the caches and the counts (prefill: o and lse); heads: the head counts;
-    mid: what stands between cu_seqlens and the stream (prefill: causal)."""
-    import torch
-
-    total, d = x.shape[0], x.shape[2]
-    if block_table is not None:
-        cache = (d, k.shape[0], k.shape[2], block_table.data_ptr(), block_table.shape[1])
-    else:
-        cache = (k.shape[2], d)
-    tail = ()
-    if kv8:
-        tail = (k_scale.data_ptr() if k_scale is not None else None,
-                v_scale.data_ptr() if v_scale is not None else None)
-    dev = x.device.index
-    if stream is None:
-        st = torch._C._cuda_getCurrentRawStream(dev)
-    else:
-        st = stream if isinstance(stream, int) else stream.cuda_stream
-    lib = _lib or load_library()
-    with torch.cuda.device(dev):
-        rc = getattr(lib, name)(x.data_ptr(), *y, k.data_ptr(), v.data_ptr(), *extra, nseq, *heads, total,
-                                *cache, kv_lens.data_ptr() if kv_lens is not None else None,
-                                cu.data_ptr(), *mid, st, *tail)
-    _check(rc)
-
-
 def _prefill_varlen(q, k, v, block_table, names, cu_seqlens_q, kv_lens, causal, out, return_lse, stream,
                     k_scale, v_scale, window=0, sinks=None):
-    import torch
-
     if out is None:
+        import torch
+
         out = torch.empty_like(q)
     kv8, nseq = _check_packed(q, "q", out, "out", names[0], k, names[1], v, block_table, cu_seqlens_q,
                               "cu_seqlens_q", kv_lens, k_scale, v_scale, False, sinks)
-    variant, win = _entry_variant(window, sinks)  # window: checked by the public function
-    total, hq = q.shape[0], q.shape[1]
-    lse = torch.empty((hq, total), dtype=torch.float32, device=q.device) if return_lse else None
-    name = ("fa_prefill_varlen" + variant
-            + ("_paged" if block_table is not None else "") + ("_kv8" if kv8 else "")
-            + ("_bf16" if q.dtype is torch.bfloat16 else "_f16"))
-    _packed_call(name, kv8, q, (), (out.data_ptr(), lse.data_ptr() if return_lse else None), nseq,
-                 (hq, k.shape[1]), k, v, block_table, kv_lens, cu_seqlens_q, (int(bool(causal)), *win),
-                 stream, k_scale, v_scale)
-    return (out, lse) if return_lse else out
-
+    return _prefill_call("fa_prefill_varlen", kv8, q, k, v, out, nseq, q.shape[0], block_table, kv_lens,
+                         cu_seqlens_q, causal, return_lse, stream, k_scale, v_scale, window, sinks)
 
 def flash_attention_prefill_varlen(q, k_cache, v_cache, cu_seqlens_q, kv_lens=None, causal: bool = True,
                                    out=None, return_lse: bool = False, stream=None, k_scale=None,
@@ -1484,29 +1270,19 @@ def _check_attn(q, k, v, out, rank, cu_q, cu_k, sinks):
 
 def _attn_call(q, k, v, out, strides, batch, total_q, total_k, cu_q, cu_k, seqlen_q, seqlen_k, causal,
                lse, stream, window, sinks):
-    """The call of the two functions below after their checks: the stream and
-    the fa_attn_varlen[_win|_sink]_* entry of q's dtype."""
+    """The call of the two functions below after their checks: the
+    fa_attn_varlen[_win|_sink]_* entry of q's dtype."""
     import torch
 
     variant, win = _entry_variant(window, sinks)  # window: checked by the public function
-    last = ()
-    if sinks is not None:
-        win, last = win[:1], win[1:]  # these entries take `sinks` after the stream
-    name = "fa_attn_varlen" + variant + ("_bf16" if q.dtype is torch.bfloat16 else "_f16")
-    dev = q.device.index
-    if stream is None:
-        st = torch._C._cuda_getCurrentRawStream(dev)
-    else:
-        st = stream if isinstance(stream, int) else stream.cuda_stream
-    lib = _lib or load_library()
-    with torch.cuda.device(dev):
-        rc = getattr(lib, name)(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
-                                lse.data_ptr() if lse is not None else None, batch, q.shape[-2],
-                                k.shape[-2], total_q, total_k, q.shape[-1], *strides,
-                                cu_q.data_ptr() if cu_q is not None else None,
-                                cu_k.data_ptr() if cu_k is not None else None, seqlen_q, seqlen_k,
-                                int(bool(causal)), *win, st, *last)
-    _check(rc)
+    _launch(_entry_name("fa_attn_varlen", variant, False, False, q.dtype is torch.bfloat16),
+            q.device.index, stream,
+            (q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
+             lse.data_ptr() if lse is not None else None, batch, q.shape[-2], k.shape[-2], total_q,
+             total_k, q.shape[-1], *strides, cu_q.data_ptr() if cu_q is not None else None,
+             cu_k.data_ptr() if cu_k is not None else None, seqlen_q, seqlen_k, int(bool(causal)),
+             *win[:1]),
+            win[1:])  # these entries take `sinks` after the stream
 
 
 def flash_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k=None, causal: bool = False, out=None,
@@ -1637,34 +1413,22 @@ def _check_attn_bwd(dout, q, k, v, out, lse, rank, cu_q, cu_k, dq, dk, dv, sinks
 def _attn_bwd_call(dout, q, k, v, out, lse, grads, strides, batch, total_q, total_k, cu_q, cu_k, seqlen_q,
                    seqlen_k, causal, stream, window=0, sinks=None, dsinks=None):
     """The call of the two functions below after their checks: delta (the only
-    workspace), the stream and the entry of q's dtype: fa_attn_varlen_bwd_*, or
-    with a window fa_attn_bwd_win_*, or with sinks fa_attn_bwd_sink_*."""
+    workspace) and the entry of q's dtype: fa_attn_varlen_bwd_*, or with a
+    window fa_attn_bwd_win_*, or with sinks fa_attn_bwd_sink_*."""
     import torch
 
     variant, win = _entry_variant(window, sinks)  # window: checked by the public function
-    last = ()
-    if sinks is not None:
-        win, last = win[:1], win[1:] + (dsinks.data_ptr(),)  # `sinks, dsinks` after the stream
-    name = ("fa_attn_bwd" + variant if variant else "fa_attn_varlen_bwd") + (
-        "_bf16" if q.dtype is torch.bfloat16 else "_f16")
-    dev = q.device.index
     delta = torch.empty((q.shape[-2], total_q), dtype=torch.float32, device=q.device)
-    if stream is None:
-        st = torch._C._cuda_getCurrentRawStream(dev)
-    else:
-        st = stream if isinstance(stream, int) else stream.cuda_stream
-    lib = _lib or load_library()
     dq, dk, dv = grads
-    with torch.cuda.device(dev):
-        rc = getattr(lib, name)(dout.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
-                                lse.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
-                                delta.data_ptr(), batch, q.shape[-2], k.shape[-2], total_q, total_k,
-                                q.shape[-1], *strides,
-                                cu_q.data_ptr() if cu_q is not None else None,
-                                cu_k.data_ptr() if cu_k is not None else None, seqlen_q, seqlen_k,
-                                int(bool(causal)), *win, st, *last)
-    _check(rc)
-
+    _launch(_entry_name("fa_attn_bwd" if variant else "fa_attn_varlen_bwd", variant, False, False,
+                        q.dtype is torch.bfloat16),
+            q.device.index, stream,
+            (dout.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(),
+             dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), delta.data_ptr(), batch, q.shape[-2], k.shape[-2],
+             total_q, total_k, q.shape[-1], *strides, cu_q.data_ptr() if cu_q is not None else None,
+             cu_k.data_ptr() if cu_k is not None else None, seqlen_q, seqlen_k, int(bool(causal)),
+             *win[:1]),
+            win[1:] + (dsinks.data_ptr(),) if sinks is not None else ())  # `sinks, dsinks` after the stream
 
 def flash_attention_varlen_backward(dout, q, k, v, out, lse, cu_seqlens_q, cu_seqlens_k=None,
                                     causal: bool = False, dq=None, dk=None, dv=None, stream=None,
@@ -1736,18 +1500,10 @@ def flash_attn_func(q, k, v, causal: bool = False, window: int = 0, sinks=None):
 
 
 def _append_varlen(k_new, v_new, k, v, block_table, names, cu_seqlens, kv_lens, k_scale, v_scale, stream):
-    import torch
-
     kv8, nseq = _check_packed(k_new, "k_new", v_new, "v_new", names[0], k, names[1], v, block_table,
                               cu_seqlens, "cu_seqlens", kv_lens, k_scale, v_scale, True)
-    name = "fa_cache_append_varlen" + ("_paged" if block_table is not None else "")
-    if kv8:
-        name += "_kv8_bf16" if k_new.dtype is torch.bfloat16 else "_kv8_f16"
-    else:
-        name += "_16"
-    _packed_call(name, kv8, k_new, (v_new.data_ptr(),), (), nseq, (k_new.shape[1],), k, v, block_table,
-                 kv_lens, cu_seqlens, (), stream, k_scale, v_scale)
-
+    _append_call("fa_cache_append_varlen", kv8, k_new, v_new, k, v, nseq, k_new.shape[0], block_table,
+                 kv_lens, cu_seqlens, stream, k_scale, v_scale)
 
 def flash_attention_cache_append_varlen(k_new, v_new, k_cache, v_cache, cu_seqlens, kv_lens,
                                         k_scale=None, v_scale=None, stream=None) -> None:
@@ -1847,39 +1603,17 @@ def _rope_tail(q, q_out, cos, sin, interleaved):
 
 def _rope_append(q, k_new, v_new, k, v, block_table, names, kv_lens, cos, sin, new_lens, interleaved,
                  q_out, k_scale, v_scale, stream):
-    import torch
-
     _check_rope(k_new, "k_new", 4, q, q_out, cos, sin, False)
     kv8 = _check_append(k_new, v_new, names[0], k, names[1], v, block_table, kv_lens, new_lens,
                         k_scale, v_scale)
     if q is not None and q_out is None:
+        import torch
+
         q_out = torch.empty_like(q)
     _check_rope(k_new, "k_new", 4, q, q_out, cos, sin, True)
-    b, hkv, sn, d = k_new.shape
-    if block_table is not None:
-        cache = (d, k.shape[0], k.shape[2], block_table.data_ptr(), block_table.shape[1])
-    else:
-        cache = (k.shape[2], d)
-    name = ("fa_rope_append" + ("_paged" if block_table is not None else "") + ("_kv8" if kv8 else "")
-            + ("_bf16" if k_new.dtype is torch.bfloat16 else "_f16"))
-    tail = ()
-    if kv8:
-        tail = (k_scale.data_ptr() if k_scale is not None else None,
-                v_scale.data_ptr() if v_scale is not None else None)
-    dev = k_new.device.index
-    if stream is None:
-        st = torch._C._cuda_getCurrentRawStream(dev)
-    else:
-        st = stream if isinstance(stream, int) else stream.cuda_stream
-    lib = _lib or load_library()
-    with torch.cuda.device(dev):
-        rc = getattr(lib, name)(k_new.data_ptr(), v_new.data_ptr(), k.data_ptr(), v.data_ptr(), b, hkv,
-                                sn, *cache, kv_lens.data_ptr(),
-                                new_lens.data_ptr() if new_lens is not None else None, st, *tail,
-                                *_rope_tail(q, q_out, cos, sin, interleaved))
-    _check(rc)
+    _append_call("fa_rope_append", kv8, k_new, v_new, k, v, k_new.shape[0], k_new.shape[2], block_table,
+                 kv_lens, new_lens, stream, k_scale, v_scale, _rope_tail(q, q_out, cos, sin, interleaved))
     return q_out
-
 
 def flash_attention_rope_append(q, k_new, v_new, k_cache, v_cache, kv_lens, cos, sin, new_lens=None,
                                 interleaved: bool = False, q_out=None, k_scale=None, v_scale=None,
@@ -1929,38 +1663,17 @@ def flash_attention_rope_append_paged(q, k_new, v_new, k_pages, v_pages, block_t
 
 def _rope_append_varlen(q, k_new, v_new, k, v, block_table, names, cu_seqlens, kv_lens, cos, sin,
                         interleaved, q_out, k_scale, v_scale, stream):
-    import torch
-
     _check_rope(k_new, "k_new", 3, q, q_out, cos, sin, False)
     kv8, nseq = _check_packed(k_new, "k_new", v_new, "v_new", names[0], k, names[1], v, block_table,
                               cu_seqlens, "cu_seqlens", kv_lens, k_scale, v_scale, True)
     if q is not None and q_out is None:
+        import torch
+
         q_out = torch.empty_like(q)
     _check_rope(k_new, "k_new", 3, q, q_out, cos, sin, True)
-    name = ("fa_rope_append_varlen" + ("_paged" if block_table is not None else "")
-            + ("_kv8" if kv8 else "") + ("_bf16" if k_new.dtype is torch.bfloat16 else "_f16"))
-    total, d = k_new.shape[0], k_new.shape[2]
-    if block_table is not None:
-        cache = (d, k.shape[0], k.shape[2], block_table.data_ptr(), block_table.shape[1])
-    else:
-        cache = (k.shape[2], d)
-    tail = ()
-    if kv8:
-        tail = (k_scale.data_ptr() if k_scale is not None else None,
-                v_scale.data_ptr() if v_scale is not None else None)
-    dev = k_new.device.index
-    if stream is None:
-        st = torch._C._cuda_getCurrentRawStream(dev)
-    else:
-        st = stream if isinstance(stream, int) else stream.cuda_stream
-    lib = _lib or load_library()
-    with torch.cuda.device(dev):
-        rc = getattr(lib, name)(k_new.data_ptr(), v_new.data_ptr(), k.data_ptr(), v.data_ptr(), nseq,
-                                k_new.shape[1], total, *cache, kv_lens.data_ptr(), cu_seqlens.data_ptr(),
-                                st, *tail, *_rope_tail(q, q_out, cos, sin, interleaved))
-    _check(rc)
+    _append_call("fa_rope_append_varlen", kv8, k_new, v_new, k, v, nseq, k_new.shape[0], block_table,
+                 kv_lens, cu_seqlens, stream, k_scale, v_scale, _rope_tail(q, q_out, cos, sin, interleaved))
     return q_out
-
 
 def flash_attention_rope_append_varlen(q, k_new, v_new, k_cache, v_cache, cu_seqlens, kv_lens, cos, sin,
                                        interleaved: bool = False, q_out=None, k_scale=None,
@@ -2027,7 +1740,7 @@ def flash_attention_fwd_splitkv(q, k, v, causal: bool = False, num_splits: int =
             raise FlashAttentionError(FA_ERR_WORKSPACE,
                                       f"{name} must be contiguous float32 on {q.device}")
     with torch.cuda.device(q.device):
-        st = ctypes.c_void_p(_stream_handle(stream, q.device))
+        st = ctypes.c_void_p(_raw_stream(stream, q.device.index))
         _check(lib.fa_fwd_f16_splitkv(
             ctypes.c_void_p(q.data_ptr()), ctypes.c_void_p(k.data_ptr()),
             ctypes.c_void_p(v.data_ptr()), ctypes.c_void_p(out.data_ptr()), b, h, s, d,
@@ -2062,7 +1775,7 @@ def flash_attention_v9_dispatch(Q, K, V, Output, splitk_buf_O, splitk_buf_ml, ba
         return x if isinstance(x, int) else x.data_ptr()
 
     lib = load_library()
-    st = ctypes.c_void_p(_stream_handle(stream) if stream not in (0, None) else None)
+    st = ctypes.c_void_p(_raw_stream(stream, None) if stream not in (0, None) else None)  # (0, None: the null stream)
     q, k, v, o = (ctypes.c_void_p(ptr(x)) for x in (Q, K, V, Output))
     _check(lib.fa_fwd_f16(q, k, v, o, batch_size, num_heads, seq_len, head_dim,
                           int(bool(causal)), st))

@@ -22,6 +22,13 @@ def fa():
     return fa_mi355x
 
 
+def header_text(header):
+    """A public header's text without its comments."""
+    text = open(os.path.join(ROOT, "include", header)).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    return re.sub(r"//.*", "", text)
+
+
 def exported_symbols():
     """The dynamic symbols the built library defines."""
     out = subprocess.run(["nm", "-D", "--defined-only", fa().library_path()], capture_output=True,

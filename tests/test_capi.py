@@ -11,13 +11,9 @@ import pytest
 import capi_checks
 from capi_checks import ROOT, fa as _fa
 
-INCLUDE = os.path.join(ROOT, "include")
-
 
 def _declared_functions(header):
-    text = open(os.path.join(INCLUDE, header)).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    text = re.sub(r"//.*", "", text)
+    text = capi_checks.header_text(header)
     # return-type name(  ... ) ;   at file scope (no typedef/struct bodies)
     names = re.findall(r"^[A-Za-z_][\w \*]*?\b([a-z_][a-z0-9_]*)\s*\([^;{]*\)\s*;", text, re.M)
     return sorted(set(names))

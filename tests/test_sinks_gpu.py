@@ -346,6 +346,26 @@ def test_packed_prefill_over_a_contiguous_fp8_cache_against_the_references(dtype
     sr.check(*packed, refs, q_lens, dtype, f"packed fp8 contiguous {dr.name(dtype)} W={window}")
 
 
+@pytest.mark.parametrize("dtype", dr.DTYPES)
+def test_packed_prefill_over_a_paged_16_bit_pool_against_the_references(dtype):
+    """fa_prefill_varlen_sink_paged_*, of which no Python function reached the
+    bf16 entry (packed Q over 16-bit page pools), at the shape of the test above:
+    the gates, and the contiguous packed call's result bit for bit."""
+    b, hq, hkv, sq, cap, d, window = 2, 4, 2, 130, 192, 64, 80
+    kv_lens, q_lens = (192, 70), (130, 40)
+    _, (q, k, v), _ = _inputs(b, hq, hkv, sq, cap, d, dtype, False)
+    sinks, refs = _refs(b, hq, hkv, sq, cap, d, dtype, False, kv_lens, q_lens, window, True, 12)
+    cu = vr.cu_of(q_lens)
+    qp = vr.pack(q, q_lens, total=cu[-1] + 7, fill=dr.NAN_BITS)
+    kw = dict(return_lse=True, window=window, sinks=_dev32(sinks))
+    kp, vp, table = _paginate(k, v, 64, kv_lens, seed=13)
+    po, pl = prefill_varlen_paged(qp, kp, vp, table, _lens(cu), _lens(kv_lens), **kw)
+    packed = (vr.unpack(po, cu, sq), vr.unpack(pl, cu, sq, fill=NINF))
+    sr.check(*packed, refs, q_lens, dtype, f"packed paged {dr.name(dtype)} W={window}")
+    co, cl = prefill_varlen(qp, _pad(k, kv_lens), _pad(v, kv_lens), _lens(cu), _lens(kv_lens), **kw)
+    assert _same_rows(packed, (vr.unpack(co, cu, sq), vr.unpack(cl, cu, sq, fill=NINF)), q_lens)
+
+
 @pytest.mark.parametrize("window,causal", [(0, True), (100, True), (0, False)])
 @pytest.mark.parametrize("sq", [1, 4, 16])
 @pytest.mark.parametrize("dtype", dr.DTYPES)
