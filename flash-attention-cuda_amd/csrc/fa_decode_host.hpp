@@ -193,14 +193,17 @@ inline void decode_set_pages(Params& p, const DecodePages& pg, int heads_kv, int
 }
 
 // the fields a variant adds: the window (W = 0, no window, runs as W =
-// capacity, which masks nothing), the sinks and the FP8 scales
+// capacity, which masks nothing), the sinks, the FP8 scales and (decode only)
+// the tree mask
 template <bool KV8, bool WIN, bool SINK, class Params>
 inline void decode_set_variant(Params& p, [[maybe_unused]] int kv_capacity, [[maybe_unused]] int window,
                                [[maybe_unused]] const float* sinks,
                                [[maybe_unused]] const float* k_scale,
-                               [[maybe_unused]] const float* v_scale) {
+                               [[maybe_unused]] const float* v_scale,
+                               [[maybe_unused]] const int* tree_mask = nullptr) {
   if constexpr (WIN) p.window = window > 0 ? std::min(window, kv_capacity) : kv_capacity;
   if constexpr (SINK) p.sinks = sinks;
+  if constexpr (ParamsTreed<Params>::value) p.tree = tree_mask;
   if constexpr (KV8) {
     p.k_scale = k_scale;
     p.v_scale = v_scale;
@@ -250,23 +253,33 @@ inline int dispatch_elem_dim(int dtype, int head_dim, Launch&& launch) {
 // SINK (the fa_decode_sink_* entries; with WIN): `sinks`
 // goes to the Sinked<Windowed<>> instantiations (nullptr: no sinks); the
 // statuses, the plan and the workspace are the windowed twin's.
-template <bool PAGED, bool KV8, bool WIN, bool SINK>
+// TREE (the fa_decode_tree_* entries of include/fa_mi355x_tree.h; with SINK):
+// `tree_mask` goes to the Treed<Sinked<Windowed<>>> instantiations (nullptr:
+// the chain); the mask replaces the causal rule, so causal = 0 is refused, and
+// so is a window shorter than the drafts (0 < W < seqlen_q), both where the
+// sink twin refuses a window without causal; everything else is that twin's.
+// Without TREE `tree_mask` is not looked at (the entries pass nullptr).
+template <bool PAGED, bool KV8, bool WIN, bool SINK, bool TREE>
 static int decode_entry(int dtype, const void* q, const void* k, const void* v, void* o, float* lse,
                         int batch, int heads_q, int heads_kv, int seqlen_q, int kv_capacity,
                         int head_dim, const DecodePages& pg, const int* kv_lens, int causal,
-                        int window, const float* sinks, int num_splits, void* ws,
-                        unsigned long long ws_bytes, void* hip_stream, const float* k_scale,
+                        int window, const float* sinks, const int* tree_mask, int num_splits,
+                        void* ws, unsigned long long ws_bytes, void* hip_stream, const float* k_scale,
                         const float* v_scale) {
   static_assert(WIN || !SINK, "the sink kernels are instantiated over the windowed ones");
   using P0 = std::conditional_t<PAGED, std::conditional_t<KV8, DecodePagedKv8Params, DecodePagedParams>,
                                 std::conditional_t<KV8, DecodeKv8Params, DecodeParams>>;
-  using P = std::conditional_t<SINK, Sinked<Windowed<P0>>, std::conditional_t<WIN, Windowed<P0>, P0>>;
+  static_assert(SINK || !TREE, "the tree kernels are instantiated over the sink ones");
+  using P = std::conditional_t<
+      TREE, Treed<Sinked<Windowed<P0>>>,
+      std::conditional_t<SINK, Sinked<Windowed<P0>>, std::conditional_t<WIN, Windowed<P0>, P0>>>;
   if (batch < 0 || heads_q < 0 || heads_kv < 0 || kv_capacity < 0 || head_dim < 0 || num_splits < 0)
     return FA_ERR_BAD_SHAPE;
   if (WIN && window < 0) return FA_ERR_BAD_SHAPE;
   if (head_dim != 128 && head_dim != 64) return FA_ERR_UNSUPPORTED_HEAD_DIM;
   if (seqlen_q < 1 || seqlen_q > 16) return FA_ERR_BAD_SHAPE;
   if (WIN && window > 0 && !causal) return FA_ERR_BAD_SHAPE;
+  if (TREE && (!causal || (window > 0 && window < seqlen_q))) return FA_ERR_BAD_SHAPE;
   if constexpr (PAGED) {
     if (const int st = decode_check_pages(pg, head_dim, &kv_capacity)) return st;
   }
@@ -318,7 +331,7 @@ static int decode_entry(int dtype, const void* q, const void* k, const void* v, 
   p.causal = causal ? 1 : 0;
   p.c = 1.4426950408889634f / sqrtf((float)head_dim);
   if (ns > 1) decode_set_workspace(p, ge, ns, ws);
-  decode_set_variant<KV8, WIN, SINK>(p, kv_capacity, window, sinks, k_scale, v_scale);
+  decode_set_variant<KV8, WIN, SINK>(p, kv_capacity, window, sinks, k_scale, v_scale, tree_mask);
   if constexpr (PAGED) {
     decode_set_pages<KV8>(p, pg, heads_kv, head_dim);
     p.adv_pages = 4 / p.tpp;
@@ -338,6 +351,7 @@ static int decode_entry(int dtype, const void* q, const void* k, const void* v, 
 // bodies' template arguments).  An entry macro picks one of each kind by tag:
 //   cache:   CONTIG | PAGED       in kv_capacity's place
 //   variant: PLAIN | WIN | SINK   `window` (and `sinks`) after `causal`
+//            TREE (decode only)   SINK's, then `tree_mask`
 //   scales:  KV16 | KV8           the FP8 scales, last
 #define FA_CONTIG_PARAMS int kv_capacity, int head_dim
 #define FA_CONTIG_ARGS kv_capacity, head_dim, {}
@@ -360,6 +374,23 @@ static int decode_entry(int dtype, const void* q, const void* k, const void* v, 
 #define FA_SINK_SINKS , const float* sinks
 #define FA_SINK_ARGS window, sinks
 #define FA_SINK_FLAGS true, true
+// (the decode entries alone take a tree mask, hence a group of its own: MASK)
+#define FA_PLAIN_MASK
+#define FA_PLAIN_MASK_ARG nullptr
+#define FA_PLAIN_MASK_FLAG false
+#define FA_WIN_MASK
+#define FA_WIN_MASK_ARG nullptr
+#define FA_WIN_MASK_FLAG false
+#define FA_SINK_MASK
+#define FA_SINK_MASK_ARG nullptr
+#define FA_SINK_MASK_FLAG false
+#define FA_TREE_WINDOW , int window
+#define FA_TREE_SINKS , const float* sinks
+#define FA_TREE_ARGS window, sinks
+#define FA_TREE_FLAGS true, true
+#define FA_TREE_MASK , const int* tree_mask
+#define FA_TREE_MASK_ARG tree_mask
+#define FA_TREE_MASK_FLAG true
 
 #define FA_KV16_PARAMS
 #define FA_KV16_ARGS nullptr, nullptr
@@ -368,19 +399,22 @@ static int decode_entry(int dtype, const void* q, const void* k, const void* v, 
 #define FA_KV8_ARGS k_scale, v_scale
 #define FA_KV8_FLAG true
 
-// PREFIX_f16 and PREFIX_bf16 of include/fa_mi355x.h, e.g.
+// PREFIX_f16 and PREFIX_bf16 of include/fa_mi355x.h (TREE: of
+// include/fa_mi355x_tree.h), e.g.
 // FA_DECODE_ENTRIES(fa_decode_win_paged_kv8, PAGED, WIN, KV8); the paged lists
 // name `k` / `v` k_pages / v_pages there.
 #define FA_DECODE_ENTRY(NAME, DTYPE, CACHE, VARIANT, SCALES)                                        \
   extern "C" int NAME(const void* q, const void* k, const void* v, void* o, float* lse, int batch,  \
                       int heads_q, int heads_kv, int seqlen_q, FA_##CACHE##_PARAMS,                 \
-                      const int* kv_lens, int causal FA_##VARIANT##_WINDOW FA_##VARIANT##_SINKS,    \
+                      const int* kv_lens, int causal FA_##VARIANT##_WINDOW FA_##VARIANT##_SINKS     \
+                          FA_##VARIANT##_MASK,                                                      \
                       int num_splits, void* workspace, unsigned long long ws_bytes,                 \
                       void* hip_stream FA_##SCALES##_PARAMS) {                                      \
-    return fa::decode_entry<FA_##CACHE##_FLAG, FA_##SCALES##_FLAG, FA_##VARIANT##_FLAGS>(           \
+    return fa::decode_entry<FA_##CACHE##_FLAG, FA_##SCALES##_FLAG, FA_##VARIANT##_FLAGS,            \
+                            FA_##VARIANT##_MASK_FLAG>(                                              \
         DTYPE, q, k, v, o, lse, batch, heads_q, heads_kv, seqlen_q, FA_##CACHE##_ARGS, kv_lens,     \
-        causal, FA_##VARIANT##_ARGS, num_splits, workspace, ws_bytes, hip_stream,                   \
-        FA_##SCALES##_ARGS);                                                                        \
+        causal, FA_##VARIANT##_ARGS, FA_##VARIANT##_MASK_ARG, num_splits, workspace, ws_bytes,      \
+        hip_stream, FA_##SCALES##_ARGS);                                                            \
   }
 #define FA_DECODE_ENTRIES(PREFIX, CACHE, VARIANT, SCALES)                 \
   FA_DECODE_ENTRY(PREFIX##_f16, FA_DTYPE_F16, CACHE, VARIANT, SCALES)     \

@@ -134,6 +134,30 @@ template <class Base>
 struct ParamsSinked<Sinked<Base>> : std::true_type {};
 template <class Base>
 struct ParamsWindowed<Sinked<Base>> : ParamsWindowed<Base> {};
+// The tree-masked decode entries (fa_decode_tree_*, include/fa_mi355x_tree.h)
+// pass Treed<Sinked<Windowed<...>>>: the Sq query tokens are the draft tokens
+// of a speculation tree, the last Sq keys of the cache, and `tree` is a device
+// int32 [B][Sq] (nullptr: the chain), word t the set of draft tokens row t
+// sees, its ancestors and itself.  With base = len - Sq and
+// m_t = tree[b][t] & ((1 << Sq) - 1):
+//   draft key i (cache row base + i >= 0): seen iff bit i of m_t is set;
+//   prefix key j < base: seen iff j > pos_t - W, pos_t = base + depth_t,
+//     depth_t = max(popcount(m_t) - 1, 0)  (W = capacity: every prefix key).
+// The chain is m_t = (2 << t) - 1.  The kernel takes TREE from the type as it
+// takes WIN and SINK; the words are read only in the tiles that hold a draft
+// key or a window edge, so any contents are safe: they deselect keys, no more.
+template <class Base>
+struct Treed : Base {
+  const int* tree;
+};
+template <class P>
+struct ParamsTreed : std::false_type {};
+template <class Base>
+struct ParamsTreed<Treed<Base>> : std::true_type {};
+template <class Base>
+struct ParamsWindowed<Treed<Base>> : ParamsWindowed<Base> {};
+template <class Base>
+struct ParamsSinked<Treed<Base>> : ParamsSinked<Base> {};
 
 // Rows but no keys, with sinks: LSE[row] = sinks[head of the row].  Padded
 // layouts [B][Hq][Sq] (head = row / sq % hq); PACKED: [Hq][T] (head = row / sq,
@@ -261,6 +285,8 @@ __global__ __launch_bounds__(256, 1) void fa_decode_kernel(P p) {
   constexpr bool KV8 = !std::is_same<KV, T>::value;
   constexpr bool WIN = ParamsWindowed<P>::value;
   constexpr bool SINK = ParamsSinked<P>::value;
+  constexpr bool TREE = ParamsTreed<P>::value;
+  static_assert(!TREE || (WIN && SINK), "the tree kernels are instantiated over the sink ones");
   static_assert(!KV8 || std::is_same<KV, unsigned char>::value, "the cache holds T or E4M3 bytes");
   constexpr int ROW = 2 * HDIM;      // bytes per Q/O row
   constexpr int CROW = KV8 ? HDIM : 2 * HDIM;  // bytes per K/V cache row
@@ -365,7 +391,10 @@ __global__ __launch_bounds__(256, 1) void fa_decode_kernel(P p) {
     const int r = row0 + 16 * nb + r16;
     lim[nb] = p.causal ? len - p.sq + 1 + r % p.sq : len;
   }
-  const int mask_from = p.causal ? len - p.sq + 1 : len;  // tiles ending past it need the mask
+  // tiles ending past it need the mask.  TREE: draft key 0 itself (row len -
+  // sq) may be hidden from a row; `lim` is unused there (the rows' bounds come
+  // from the mask words, read where the mask is applied)
+  const int mask_from = TREE ? len - p.sq : p.causal ? len - p.sq + 1 : len;
   // WIN: row r also masks the keys below lim - win; tiles starting below the
   // last row's bound need the mask
   [[maybe_unused]] const int mask_below = WIN ? len - win : 0;
@@ -578,16 +607,49 @@ __global__ __launch_bounds__(256, 1) void fa_decode_kernel(P p) {
           s[nb][cb] *= p.c;
       }
       if (need_mask) {
+        if constexpr (TREE) {
+          // the row's mask word, loaded here and not held across the tile loop
+          // (at most two tiles of a wave come here, and the words hit in
+          // cache): with base = len - sq, a draft key d = key - base >= 0 is
+          // seen iff bit d is set (keys from len on have d >= sq), a prefix key
+          // iff it lies inside the window of the row's position base + depth.
+          // The row's token is row % sq: the block's first row by a scalar
+          // division, then u < sq + 16 in fp32 ((u + 1/2) / sq is at least 1 / 32
+          // away from an integer, far more than the reciprocal's error).  Nothing
+          // of it is computed ahead of the loop: the scalar registers are as
+          // scarce as the vector ones
+          const int u = (row0 + 16 * nb) % p.sq + (lane & 15);
+          const int t = u - p.sq * (int)(((float)u + 0.5f) * __builtin_amdgcn_rcpf((float)p.sq));
+          const int mt = p.tree ? p.tree[(size_t)b * p.sq + t] & ((1 << p.sq) - 1) : (2 << t) - 1;
+          const int depth = max(__builtin_popcount(mt) - 1, 0);
+          // d of the lane's first key, kept one vector register: as a sum of
+          // scalars and constants per key the tests spill scalar registers
+          int d0 = kv0 + 4 * sg - (len - p.sq);
+          asm volatile("" : "+v"(d0));
 #pragma unroll
-        for (int cb = 0; cb < 4; ++cb)
+          for (int cb = 0; cb < 4; ++cb)
 #pragma unroll
-          for (int i = 0; i < 4; ++i)
-            if constexpr (WIN)  // lim - win <= key < lim, as one unsigned compare
-              s[nb][cb][i] = (unsigned)(lim[nb] - 1 - (kv0 + 16 * cb + 4 * sg + i)) < (unsigned)win
-                                 ? s[nb][cb][i]
-                                 : ninf();
-            else
-              s[nb][cb][i] = kv0 + 16 * cb + 4 * sg + i < lim[nb] ? s[nb][cb][i] : ninf();
+            for (int i = 0; i < 4; ++i) {
+              // pos - key = depth - d; bit 31 of the word is clear (sq <= 16)
+              const int d = d0 + 16 * cb + i;
+              const bool vis = d < 0 ? (unsigned)(depth - d) < (unsigned)win : (mt >> min(d, 31) & 1) != 0;
+              s[nb][cb][i] = vis ? s[nb][cb][i] : ninf();
+              // one key at a time: sixteen tests in flight hold thirty-two
+              // scalar registers of lane masks and spill the descriptors
+              asm volatile("" : "+v"(s[nb][cb][i]));
+            }
+        } else {
+#pragma unroll
+          for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+              if constexpr (WIN)  // lim - win <= key < lim, as one unsigned compare
+                s[nb][cb][i] = (unsigned)(lim[nb] - 1 - (kv0 + 16 * cb + 4 * sg + i)) < (unsigned)win
+                                   ? s[nb][cb][i]
+                                   : ninf();
+              else
+                s[nb][cb][i] = kv0 + 16 * cb + 4 * sg + i < lim[nb] ? s[nb][cb][i] : ninf();
+        }
       }
       float mx = s[nb][0][0];
 #pragma unroll

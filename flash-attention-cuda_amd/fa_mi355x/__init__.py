@@ -80,6 +80,7 @@ _WINDOW = {"": [], "_win": [_I], "_sink": [_I]}       # PLAIN | WIN | SINK: wind
 _SINKS = {"": [], "_win": [], "_sink": [_P]}          # ... sinks
 _BWD_SINKS = {"": [], "_win": [], "_sink": [_P, _P]}  # ... sinks, dsinks (the backward)
 _SCALES = {"": [], "_kv8": [_P, _P]}                  # KV16 | KV8: k_scale, v_scale
+_TREE_MASK = [_P]                                     # TREE: tree_mask, after sinks
 _APPEND_HEAD = [_P] * 4 + [_I] * 3  # k_new, v_new, k_cache, v_cache, batch, heads_kv, seqlen_new / total_new
 _ROPE_TAIL = [_P, _P, _I, _P, _P, _I, _I, _I]  # q, q_out, heads_q, cos, sin, rope_len, rotary_dim, interleaved
 _STRIDES = [_LL] * 3               # the token strides of q, k, v
@@ -154,6 +155,20 @@ C_ENTRIES = _c_entries()
 EXPORTED_SYMBOLS = tuple(C_ENTRIES)
 
 
+def _tree_entries():
+    """name -> (restype, argtypes) of every function include/fa_mi355x_tree.h
+    declares: the `_sink` decode lists with `tree_mask` directly after `sinks`."""
+    return {"fa_decode_tree" + c + s + ty: (_I, (
+                _QKVO_LSE + [_I] * 4 + _CACHE[c] + [_P, _I] + _WINDOW["_sink"] + _SINKS["_sink"] + _TREE_MASK
+                + [_I, _P, _ULL] + _STREAM + _SCALES[s]))
+            for c in ("", "_paged") for s in ("", "_kv8") for ty in ("_f16", "_bf16")}
+
+
+# the tree-masked decode entries (speculative-decoding verification), a table
+# of their own beside a header of their own: C_ENTRIES stays fa_mi355x.h's
+TREE_ENTRIES = _tree_entries()
+
+
 @dataclass(frozen=True)
 class TileConfig:
     id: int
@@ -186,9 +201,10 @@ def load_library() -> ctypes.CDLL:
             f"{LIB_PATH} not built (run `make -C {PKG_ROOT}` or __graft_entry__.build())",
         )
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in C_ENTRIES.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = restype, argtypes
+    for table in (C_ENTRIES, TREE_ENTRIES):
+        for name, (restype, argtypes) in table.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 
@@ -496,7 +512,7 @@ def _check_table_type(block_table):
 
 
 def _check_decode_tail(q, kname, k, vname, v, out, k_scale, v_scale, block_table, kv_lens,
-                       qname="q", oname="out", batch=None, sinks=None):
+                       qname="q", oname="out", batch=None, sinks=None, tree_mask=None):
     """What both decode checks end with, after the family's own shape checks:
     Hq % Hkv, each scale (if given) a contiguous float32 [Hkv] tensor, the
     block table (paged only: None otherwise), kv_lens, and then where all of
@@ -505,7 +521,8 @@ def _check_decode_tail(q, kname, k, vname, v, out, k_scale, v_scale, block_table
     sequences where q's first extent is not it (the packed wrappers, whose q is
     [T,Hq,D]: heads are extent 1 there too).  `sinks` (the decode and prefill
     wrappers only): a contiguous float32 [Hq] tensor, checked after the scales
-    and like them; its values are not looked at."""
+    and like them; its values are not looked at.  `tree_mask` (the decode
+    wrappers only): :func:`_check_tree_mask`, after kv_lens in both stages."""
     import torch
 
     if batch is None:
@@ -544,6 +561,7 @@ def _check_decode_tail(q, kname, k, vname, v, out, k_scale, v_scale, block_table
             raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"kv_lens must be int32, got {kv_lens.dtype}")
         if kv_lens.dim() != 1 or kv_lens.shape[0] != batch or not kv_lens.is_contiguous():
             raise FlashAttentionError(FA_ERR_BAD_SHAPE, "kv_lens must be a contiguous [B] tensor")
+    _check_tree_mask(q, tree_mask, False)
     for name, t in ((qname, q), (kname, k), (vname, v), (oname, out)):
         if not t.is_cuda:
             raise FlashAttentionError(FA_ERR_NULL_POINTER, f"{name} must be a device tensor")
@@ -556,6 +574,7 @@ def _check_decode_tail(q, kname, k, vname, v, out, k_scale, v_scale, block_table
     _check_scales_device(q, k_scale, v_scale)
     if sinks is not None and (not sinks.is_cuda or sinks.device != q.device):
         raise FlashAttentionError(FA_ERR_NULL_POINTER, f"sinks must be a tensor on {q.device}")
+    _check_tree_mask(q, tree_mask, True)
 
 
 def _check_q_lens(q, q_lens, where):
@@ -576,7 +595,8 @@ def _check_q_lens(q, q_lens, where):
         raise FlashAttentionError(FA_ERR_BAD_SHAPE, "q_lens must be a contiguous [B] tensor")
 
 
-def _check_decode(q, k_cache, v_cache, kv_lens, out, k_scale=None, v_scale=None, q_lens=None, sinks=None):
+def _check_decode(q, k_cache, v_cache, kv_lens, out, k_scale=None, v_scale=None, q_lens=None, sinks=None,
+                  tree_mask=None):
     """Raise FlashAttentionError unless q/out are contiguous [B,Hq,Sq,D] and
     k_cache/v_cache contiguous [B,Hkv,cap,D] device tensors of one 16-bit dtype
     (or both torch.float8_e4m3fn beside a 16-bit q, with optional float32
@@ -584,7 +604,8 @@ def _check_decode(q, k_cache, v_cache, kv_lens, out, k_scale=None, v_scale=None,
     kv_lens (if given) is int32 [B] there.
     Dtypes, ranks and shapes are checked before where the tensors live, so
     each rejection names its own cause whatever the device.  q_lens (the
-    prefill wrappers only): int32 [B], checked like kv_lens."""
+    prefill wrappers only): int32 [B], checked like kv_lens.  tree_mask (the
+    decode wrappers only): int32 [B, Sq], checked like them, last."""
     kv8 = _check_decode_head(q, "k_cache", k_cache, "v_cache", v_cache, out, k_scale, v_scale, " (BHSD)")
     if k_cache.shape != v_cache.shape:
         raise FlashAttentionError(FA_ERR_BAD_SHAPE, "k_cache and v_cache must have one shape")
@@ -592,13 +613,13 @@ def _check_decode(q, k_cache, v_cache, kv_lens, out, k_scale=None, v_scale=None,
         raise FlashAttentionError(FA_ERR_BAD_SHAPE, "q and the caches must agree in batch and head_dim")
     _check_q_lens(q, q_lens, False)
     _check_decode_tail(q, "k_cache", k_cache, "v_cache", v_cache, out, k_scale, v_scale, None, kv_lens,
-                       sinks=sinks)
+                       sinks=sinks, tree_mask=tree_mask)
     _check_q_lens(q, q_lens, True)
     return kv8
 
 
 def _check_decode_paged(q, k_pages, v_pages, block_table, kv_lens, out, k_scale=None, v_scale=None,
-                        q_lens=None, sinks=None):
+                        q_lens=None, sinks=None, tree_mask=None):
     """Raise FlashAttentionError unless q/out are contiguous [B,Hq,Sq,D],
     k_pages/v_pages contiguous [num_pages,Hkv,page_size,D] pools of q's 16-bit
     dtype (or both torch.float8_e4m3fn, with optional float32 [Hkv] scales:
@@ -619,7 +640,7 @@ def _check_decode_paged(q, k_pages, v_pages, block_table, kv_lens, out, k_scale=
                                   f"page_size {k_pages.shape[2]} is not a positive multiple of 64")
     _check_q_lens(q, q_lens, False)
     _check_decode_tail(q, "k_pages", k_pages, "v_pages", v_pages, out, k_scale, v_scale, block_table,
-                       kv_lens, sinks=sinks)
+                       kv_lens, sinks=sinks, tree_mask=tree_mask)
     _check_q_lens(q, q_lens, True)
     return kv8
 
@@ -657,18 +678,84 @@ def _entry_variant(window, sinks):
     return ("_win", (window,)) if window else ("", ())
 
 
+def _check_tree_mask(q, tree_mask, where):
+    """The decode wrappers' tree_mask, worded like sinks: a contiguous int32
+    [B, Sq] tensor (`where` false, before the tensors' devices are looked at),
+    then its device (`where` true).  Its values are not looked at (no sync)."""
+    t = tree_mask
+    if t is None:
+        return
+    if where:
+        if not t.is_cuda or t.device != q.device:
+            raise FlashAttentionError(FA_ERR_NULL_POINTER, f"tree_mask must be a tensor on {q.device}")
+        return
+    import torch
+
+    if (not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 2
+            or tuple(t.shape) != (q.shape[0], q.shape[2]) or not t.is_contiguous()):
+        got = f"{t.dtype} {list(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise FlashAttentionError(
+            FA_ERR_BAD_SHAPE,
+            f"tree_mask must be a contiguous int32 [B = {q.shape[0]}, Sq = {q.shape[2]}] tensor, got {got}")
+
+
+def _check_tree_rules(q, causal, window):
+    """What the tree entries refuse beyond their `_sink` twins, after the
+    tensors: causal=False (the mask replaces the causal rule) and a window
+    shorter than the drafts."""
+    if not causal:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE,
+                                  "tree_mask needs causal=True (the mask replaces the causal rule)")
+    if 0 < window < q.shape[2]:
+        raise FlashAttentionError(
+            FA_ERR_BAD_SHAPE,
+            f"with tree_mask a window must be 0 or >= Sq = {q.shape[2]} (every ancestor inside it), got {window}")
+
+
+def tree_mask_from_parents(parents):
+    """The tree_mask of :func:`flash_attention_decode` from parent indices.
+
+    parents: an integer tensor [B, Sq] (Sq <= 16), parents[b, t] < t the draft
+    token that token t hangs from, -1 for a child of the cached prefix.
+    Returns the int32 [B, Sq] ancestor masks m_t = (1 << t) | m_parent (the
+    chain parents[b, t] = t - 1 gives (2 << t) - 1), computed on parents'
+    device in ceil(log2(Sq)) rounds of pointer doubling: no loop over tokens,
+    no sync, graph-capturable.  The values are not validated: an index outside
+    [-1, Sq) is read as the nearest inside it."""
+    import torch
+
+    if (not isinstance(parents, torch.Tensor) or parents.dim() != 2 or parents.dtype.is_floating_point
+            or parents.dtype in (torch.bool, torch.complex64, torch.complex128) or not 1 <= parents.shape[1] <= 16):
+        got = f"{parents.dtype} {list(parents.shape)}" if isinstance(parents, torch.Tensor) else type(parents).__name__
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE,
+                                  f"parents must be an integer [B, Sq <= 16] tensor, got {got}")
+    b, sq = parents.shape
+    up = parents.to(torch.int64).clamp(-1, sq - 1)  # the ancestor `span` levels up, -1 past the root
+    m = (1 << torch.arange(sq, dtype=torch.int64, device=parents.device)).expand(b, sq)  # levels < span
+    span = 1
+    while span < sq:
+        has, idx = up >= 0, up.clamp(min=0)
+        m = m | torch.where(has, m.gather(1, idx), 0)
+        up = torch.where(has, up.gather(1, idx), up)
+        span *= 2
+    return m.to(torch.int32).contiguous()
+
+
 def _decode_call(kv8, q, k, v, out, block_table, kv_lens, causal, return_lse, num_splits, stream,
-                 k_scale, v_scale, window=0, sinks=None):
+                 k_scale, v_scale, window=0, sinks=None, tree_mask=None):
     """The call of both decode functions after their checks: the optional LSE,
     the split plan and its workspace, and the fa_decode* entry.
     block_table: None when k, v are a contiguous cache, the table when they are
     page pools (the _paged entries); kv8: the _kv8 entries, which also take the
     two scales; window > 0: the fa_decode_win_* entries, whose plan and
     workspace follow :func:`decode_window_capacity`; sinks: the
-    fa_decode_sink_* entries, at any window."""
+    fa_decode_sink_* entries, at any window; tree_mask: the fa_decode_tree_*
+    entries (include/fa_mi355x_tree.h), at any window and sinks."""
     import torch
 
     variant, win = _entry_variant(window, sinks)  # checked by the public function
+    if tree_mask is not None:
+        variant, win = "_tree", (window, sinks.data_ptr() if sinks is not None else None, tree_mask.data_ptr())
     b, hq, sq, d = q.shape
     hkv, cap = k.shape[1], k.shape[2]
     paged = block_table is not None
@@ -704,7 +791,7 @@ def _decode_call(kv8, q, k, v, out, block_table, kv_lens, causal, return_lse, nu
 
 def flash_attention_decode(q, k_cache, v_cache, kv_lens=None, causal: bool = True, out=None,
                            return_lse: bool = False, num_splits: int = 0, stream=None,
-                           k_scale=None, v_scale=None, window: int = 0, sinks=None):
+                           k_scale=None, v_scale=None, window: int = 0, sinks=None, tree_mask=None):
     """Decode attention over a K/V cache (fa_decode_f16 / fa_decode_bf16, or
     fa_decode_kv8_* over an FP8 cache).
 
@@ -747,20 +834,38 @@ def flash_attention_decode(q, k_cache, v_cache, kv_lens=None, causal: bool = Tru
     device, so a captured graph follows them; the split plan and the workspace
     are unchanged.  lse includes the sink: a caller merging partial states by
     their lse must pass sinks to ONE partial only.
+
+    tree_mask: None (exactly the call above), or the tree of a speculative
+    decoding step (EAGLE / Medusa style verification; the fa_decode_tree_*
+    entries of include/fa_mi355x_tree.h, at the given window and sinks): a
+    contiguous int32 [B, Sq] tensor on q's device, shared by the heads.  The Sq
+    query tokens are draft tokens whose K/V were appended before the call (the
+    last Sq rows below kv_lens); bit i of tree_mask[b, t] says that token t sees
+    draft token i -- its ancestors and itself, :func:`tree_mask_from_parents` --
+    and every token sees the whole prefix.  With a window, token t's position
+    is kv_lens[b] - Sq + depth_t, depth_t = popcount - 1, and a prefix key j is
+    seen iff j > position - W; W must be 0 or >= Sq.  causal must be True (the
+    mask replaces the causal rule).  The chain mask (2 << t) - 1 gives the call
+    without tree_mask bit for bit.  Bits from Sq on are ignored and any contents
+    are safe: the mask only deselects keys.  It is read on the device: no sync,
+    and a captured graph follows a mask rewritten between replays.  A row that
+    sees no key gives zeros and lse = -inf (sinks[h] with sinks).
     """
     window = _check_window(window, causal)  # before the tensors: a bad window is named whatever they are
     if out is None:
         import torch
 
         out = torch.empty_like(q)
-    kv8 = _check_decode(q, k_cache, v_cache, kv_lens, out, k_scale, v_scale, sinks=sinks)
+    kv8 = _check_decode(q, k_cache, v_cache, kv_lens, out, k_scale, v_scale, sinks=sinks, tree_mask=tree_mask)
+    if tree_mask is not None:
+        _check_tree_rules(q, causal, window)
     return _decode_call(kv8, q, k_cache, v_cache, out, None, kv_lens, causal, return_lse, num_splits,
-                        stream, k_scale, v_scale, window, sinks)
+                        stream, k_scale, v_scale, window, sinks, tree_mask)
 
 
 def flash_attention_decode_paged(q, k_pages, v_pages, block_table, kv_lens=None, causal: bool = True,
                                  out=None, return_lse: bool = False, num_splits: int = 0, stream=None,
-                                 k_scale=None, v_scale=None, window: int = 0, sinks=None):
+                                 k_scale=None, v_scale=None, window: int = 0, sinks=None, tree_mask=None):
     """Decode attention over a paged K/V cache (fa_decode_paged_f16 / _bf16, or
     fa_decode_paged_kv8_* over an FP8 pool).
 
@@ -781,6 +886,7 @@ def flash_attention_decode_paged(q, k_pages, v_pages, block_table, kv_lens=None,
     function (fa_decode_win_paged_*); block-table entries of pages wholly
     below the window are never read.  sinks: as for that function
     (fa_decode_sink_paged_*): pass them to one partial only when merging by lse.
+    tree_mask: as for that function (fa_decode_tree_paged_*).
     """
     window = _check_window(window, causal)  # before the tensors: a bad window is named whatever they are
     if out is None:
@@ -788,9 +894,11 @@ def flash_attention_decode_paged(q, k_pages, v_pages, block_table, kv_lens=None,
 
         out = torch.empty_like(q)
     kv8 = _check_decode_paged(q, k_pages, v_pages, block_table, kv_lens, out, k_scale, v_scale,
-                              sinks=sinks)
+                              sinks=sinks, tree_mask=tree_mask)
+    if tree_mask is not None:
+        _check_tree_rules(q, causal, window)
     return _decode_call(kv8, q, k_pages, v_pages, out, block_table, kv_lens, causal, return_lse,
-                        num_splits, stream, k_scale, v_scale, window, sinks)
+                        num_splits, stream, k_scale, v_scale, window, sinks, tree_mask)
 
 
 def _prefill_call(family, kv8, q, k, v, out, batch, seqlen_q, block_table, kv_lens, q_lens, causal,

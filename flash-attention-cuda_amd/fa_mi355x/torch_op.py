@@ -142,9 +142,11 @@ def _no_grad_needed(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> None:
                            "torch.no_grad() / inference_mode or on tensors that do not require grad")
 
 
-def _register(op: _Op) -> None:
+def _register(op: _Op, lib=None, ns: str = "fa_mi355x") -> None:
     """Defines fa_mi355x::<packet>[.<overload>] and registers its CUDA, CPU, fake
-    and (forward_only) Autograd kernels."""
+    and (forward_only) Autograd kernels.  lib, ns: another module's library and
+    its namespace (torch_op_tree.py), under the same rules."""
+    lib = _LIB if lib is None else lib
     full = op.packet + ("." + op.overload if op.overload else "")
     names = [n for _, n, _ in op.args]
     defaults = {n: d for _, n, d in op.args if d is not _REQUIRED}
@@ -180,7 +182,7 @@ def _register(op: _Op) -> None:
         return fn(*vals[:lead], **dict(zip(keywords, vals[lead:])))
 
     def cpu(*a, **kw):
-        raise ValueError("fa_mi355x::%s needs GPU tensors (no CPU path)" % op.packet)
+        raise ValueError("%s::%s needs GPU tensors (no CPU path)" % (ns, op.packet))
 
     def fake_impl(*a, **kw):
         vals = {**defaults, **dict(zip(names, a)), **kw}
@@ -189,12 +191,12 @@ def _register(op: _Op) -> None:
         return fake(vals)
 
     schema = ", ".join("%s %s%s" % (ty, n, "" if d is _REQUIRED else "=" + str(d)) for ty, n, d in op.args)
-    _LIB.define("%s(%s) -> %s" % (full, schema, op.returns))
-    _LIB.impl(full, gpu, "CUDA")
+    lib.define("%s(%s) -> %s" % (full, schema, op.returns))
+    lib.impl(full, gpu, "CUDA")
     if guarded:
-        _LIB.impl(full, torch.library.fallthrough_kernel, "Autograd")
-    _LIB.impl(full, cpu, "CPU")
-    torch.library.register_fake("fa_mi355x::" + full, fake_impl, lib=_LIB)
+        lib.impl(full, torch.library.fallthrough_kernel, "Autograd")
+    lib.impl(full, cpu, "CPU")
+    torch.library.register_fake(ns + "::" + full, fake_impl, lib=lib)
 
 
 # The fake checks, one per family.

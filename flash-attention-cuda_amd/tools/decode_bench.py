@@ -53,6 +53,22 @@ the --window rows and in the same way (run_sinks): base / sinks / base / paged
 sinks, sink_over_base beside base_aa.
 
     python3 tools/decode_bench.py --sinks [--window 4096] [--out profiles/decode_sinks_bench.jsonl]
+
+--tree (composable with --window) times the tree-masked entries fa_decode_tree_*
+(include/fa_mi355x_tree.h) under a seeded random tree against their `_sink`
+twins under the chain rule at the same shape, window and sinks (run_tree): B =
+64 at 4k and 32k keys and B = 1 at 32k (split), Sq 4, 8 and 16, fp16 and bf16,
+over the contiguous 16-bit cache and over a paged FP8 pool (page 256), captured
+into HIP graphs and replayed alternately twin / tree / twin for each cache
+form, so every row carries its own A/A spread: tree_over_sink beside sink_aa,
+tree_pkv8_over_sink_pkv8 beside sink_pkv8_aa.  The fp16 rows add what a caller
+does without the entries: one `_sink` decode call per root-to-leaf path of the
+same tree on the same cache (paths_over_tree; the cache rows a real caller
+would also rewrite per path are not counted), and SDPA with an explicit mask
+on the GQA-expanded 16-bit cache (sdpa_over_tree; gathering and dequantising a
+paged FP8 pool first is not counted either).
+
+    python3 tools/decode_bench.py --tree [--window 4096] [--out profiles/decode_tree_bench.jsonl]
 """
 import argparse
 import json
@@ -695,6 +711,155 @@ def run_sinks(row, window, cus, page_size=256, rounds=9):
                 base_aa=round(med[2] / med[0], 4))
 
 
+def tree_shapes():
+    rows = []
+    for bf16 in (False, True):
+        for b, n in ((64, 4096), (64, 32768), (1, 32768)):
+            for sq in (4, 8, 16):
+                rows.append(dict(name=f"tree B={b} len={n} Sq={sq} {'bf16' if bf16 else 'fp16'}", b=b, hq=32,
+                                 hkv=8, sq=sq, d=128, n=n, bf16=bf16))
+    return rows
+
+
+def run_tree(row, window, cus, page_size=256, rounds=9):
+    """The `_tree` entries under a seeded random tree against the `_sink` twins
+    under the chain rule, contiguous 16-bit and paged FP8: us per call from
+    alternately replayed HIP graphs, and (fp16 rows) one twin call per
+    root-to-leaf path and SDPA with an explicit mask."""
+    import numpy as np
+
+    lib = fa_mi355x.load_library()
+    dt = torch.bfloat16 if row["bf16"] else torch.float16
+    ty = "_bf16" if row["bf16"] else "_f16"
+    b, hq, hkv, sq, d, cap = row["b"], row["hq"], row["hkv"], row["sq"], row["d"], row["n"]
+    mpp = cap // page_size
+    npages = b * mpp
+    kv_bytes = 2 * b * hkv * cap * d * 2
+    copies = max(1, min(32, -(-(512 << 20) // kv_bytes)))
+    gen = torch.Generator(device="cuda").manual_seed(1)
+
+    def rnd(*shape):
+        return (torch.rand(shape, generator=gen, device="cuda", dtype=torch.float32) * 2 - 1).to(dt)
+
+    ks, vs, kps, vps, tabs = [], [], [], [], []
+    for _ in range(copies):
+        k, v = rnd(b, hkv, cap, d), rnd(b, hkv, cap, d)
+        perm = torch.randperm(npages, generator=gen, device="cuda")
+        ks.append(k), vs.append(v)
+        for x, dst in ((k, kps), (v, vps)):
+            out = torch.empty((npages, hkv, page_size, d), dtype=torch.float8_e4m3fn, device="cuda")
+            out[perm] = x.view(b, hkv, mpp, page_size, d).permute(0, 2, 1, 3, 4).reshape(
+                npages, hkv, page_size, d).to(torch.float8_e4m3fn)
+            dst.append(out)
+        tabs.append(perm.view(b, mpp).to(torch.int32).contiguous())
+    q = rnd(b, hq, sq, d)
+    sinks = torch.randn(hq, generator=gen, device="cuda", dtype=torch.float32) * 2.0 ** 0.5
+    # one seeded random tree, shared by the batch so that its paths are one call each
+    rng = np.random.default_rng(sq)
+    parents = [int(rng.integers(-1, t)) if t else -1 for t in range(sq)]
+    mask = fa_mi355x.tree_mask_from_parents(torch.tensor([parents] * b, device="cuda"))
+    leaves = [t for t in range(sq) if t not in parents]
+    depth = [bin(int(m)).count("1") for m in mask[0].tolist()]
+    paths = [depth[t] for t in leaves]  # tokens per root-to-leaf path
+    wcap = fa_mi355x.decode_window_capacity(cap, sq, window)
+    plan = fa_mi355x.decode_num_splits(b, hq, hkv, sq, wcap, d)
+    need = max(lib.fa_decode_ws_bytes(b, hq, hkv, n, fa_mi355x.decode_window_capacity(cap, n, window), d, 0)
+               for n in set(paths) | {sq})
+    ws = torch.zeros(max(need, 1), dtype=torch.uint8, device="cuda")
+    wsp = ws.data_ptr() if need else None
+    outs = [torch.empty_like(q) for _ in range(5)]
+    iters = 20 if kv_bytes < (1 << 30) else 5
+    sp, mp = sinks.data_ptr(), mask.data_ptr()
+
+    def contig(name, out, extra, nq=sq):
+        fn = getattr(lib, name + ty)
+
+        def enqueue(st):
+            for i in range(iters):
+                c = i % copies
+                rc = fn(q.data_ptr(), ks[c].data_ptr(), vs[c].data_ptr(), out.data_ptr(), None, b, hq, hkv, nq,
+                        cap, d, None, 1, window, sp, *extra, 0, wsp, need, st)
+                assert rc == 0, rc
+        return enqueue
+
+    def paged8(name, out, extra):
+        fn = getattr(lib, name + ty)
+
+        def enqueue(st):
+            for i in range(iters):
+                c = i % copies
+                rc = fn(q.data_ptr(), kps[c].data_ptr(), vps[c].data_ptr(), out.data_ptr(), None, b, hq, hkv, sq,
+                        d, npages, page_size, tabs[c].data_ptr(), mpp, None, 1, window, sp, *extra, 0, wsp, need,
+                        st, None, None)
+                assert rc == 0, rc
+        return enqueue
+
+    def per_path(st):  # q's first rows stand for a path's tokens: the time, not the values
+        for n in paths:
+            contig("fa_decode_sink", outs[4], (), n)(st)
+
+    fns = [contig("fa_decode_sink", outs[0], ()), contig("fa_decode_tree", outs[1], (mp,)),
+           paged8("fa_decode_sink_paged_kv8", outs[2], ()), paged8("fa_decode_tree_paged_kv8", outs[3], (mp,))]
+    legs = [0, 1, 0, 2, 3, 2]
+    if not row["bf16"]:
+        fns.append(per_path)
+        legs.append(4)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):  # first-launch set-up outside the captures
+        for fn in fns:
+            fn(side.cuda_stream)
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    graphs = []
+    for fn in fns:
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            fn(torch.cuda.current_stream().cuda_stream)
+        g.replay()
+        graphs.append(g)
+    torch.cuda.synchronize()
+    ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+           for _ in range(rounds)] for _ in legs]
+    for r in range(rounds):
+        for j, gi in enumerate(legs):
+            ev[j][r][0].record()
+            graphs[gi].replay()
+            ev[j][r][1].record()
+    torch.cuda.synchronize()
+    ts = [sorted(a.elapsed_time(c) * 1e3 / iters for a, c in e) for e in ev]
+    med = [t[len(t) // 2] for t in ts]
+    rec = dict(name=row["name"], tree=True, window=window, batch=b, heads_q=hq, heads_kv=hkv, seqlen_q=sq,
+               head_dim=d, dtype="bfloat16" if row["bf16"] else "float16", kv_len=cap, page_size=page_size,
+               copies=copies, num_splits=plan, rounds=rounds, iters=iters, parents=parents, paths=paths,
+               sink_us=round(med[0], 2), tree_us=round(med[1], 2), sink2_us=round(med[2], 2),
+               sink_min_us=round(min(ts[0][0], ts[2][0]), 2), sink_max_us=round(max(ts[0][-1], ts[2][-1]), 2),
+               tree_min_us=round(ts[1][0], 2), tree_max_us=round(ts[1][-1], 2),
+               tree_over_sink=round(med[1] / med[0], 4), sink_aa=round(med[2] / med[0], 4),
+               sink_pkv8_us=round(med[3], 2), tree_pkv8_us=round(med[4], 2), sink_pkv8_2_us=round(med[5], 2),
+               tree_pkv8_over_sink_pkv8=round(med[4] / med[3], 4), sink_pkv8_aa=round(med[5] / med[3], 4))
+    if not row["bf16"]:
+        rec.update(paths_us=round(med[6], 2), paths_over_tree=round(med[6] / med[1], 4))
+        # SDPA with the tree as an explicit mask on the GQA-expanded cache (window 0 only: the
+        # mask below has no window)
+        g = hq // hkv
+        seen = torch.ones((b, 1, sq, cap), dtype=torch.bool, device="cuda")
+        bits = (mask[:, :, None] >> torch.arange(sq, device="cuda")[None, None, :]) & 1
+        seen[:, 0, :, cap - sq:] = bits.bool()
+        if window:
+            pos = cap - sq + torch.tensor(depth, device="cuda") - 1
+            key = torch.arange(cap - sq, device="cuda")
+            seen[:, 0, :, :cap - sq] = key[None, None, :] > (pos - window)[None, :, None]
+        ke, ve = ks[0].repeat_interleave(g, 1), vs[0].repeat_interleave(g, 1)
+        sd = time_pair([lambda i: F.scaled_dot_product_attention(q, ke, ve, attn_mask=seen)], 2, 3)[0]
+        err = float((F.scaled_dot_product_attention(q, ke, ve, attn_mask=seen).float()
+                     - fa_mi355x.flash_attention_decode(q, ks[0], vs[0], tree_mask=mask, window=window).float()
+                     ).abs().max())
+        rec.update(sdpa_us=round(sd, 2), sdpa_over_tree=round(sd / med[1], 4), sdpa_max_abs_diff=err)
+        del ke, ve, seen
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="default profiles/decode_bench.jsonl "
@@ -710,11 +875,15 @@ def main():
     ap.add_argument("--sinks", action="store_true",
                     help="the attention-sink entries at --window (0 included) against the entries without "
                          "sinks at the same window")
+    ap.add_argument("--tree", action="store_true",
+                    help="the tree-masked entries under a random tree against the `_sink` twins under the chain "
+                         "rule at --window (0 included), and against per-path calls and masked SDPA")
     ap.add_argument("--placement", choices=("random", "identity"), default="random",
                     help="--paged: pool pages under a random permutation (default) or in logical order")
     args = ap.parse_args()
     if args.out is None:
         args.out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "profiles",
+                                "decode_tree_bench.jsonl" if args.tree else
                                 "decode_sinks_bench.jsonl" if args.sinks else
                                 "decode_window_bench.jsonl" if args.window else
                                 "decode_kv8_bench.jsonl" if args.kv8 else
@@ -723,7 +892,9 @@ def main():
         sys.exit("decode_bench.py needs a GPU")
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    if args.sinks:
+    if args.tree:
+        jobs = [(run_tree, (row, args.window, cus)) for row in tree_shapes()]
+    elif args.sinks:
         jobs = [(run_sinks, (row, args.window, cus)) for row in window_shapes()]
     elif args.window:
         jobs = [(run_window, (row, args.window, cus)) for row in window_shapes()]
