@@ -2,6 +2,12 @@
 reference that is not this kernel (fa_decode_* and fa_decode_paged_*:
 T in {fp16, bf16} x HDIM in {64, 128} x NB in {1, 2, 4} x {contiguous, paged}).
 
+The table below is the plain 16-bit quarter of the decode instantiations: the
+FP8 forms, the `_win` and `_sink` twins and the tree entries multiply it to 192
+kernels.  tests/instantiation_matrix.py lists all of them with the prefill and
+no-cache families (300 cells) and tests/test_instantiation_matrix_gpu.py holds
+each to a closed form.
+
 Helpers, references and gates are those of tests/decode_refs.py; no new
 tolerance:
   * fp16 O: the CPU oracle, 1e-3.
