@@ -168,6 +168,27 @@ def _tree_entries():
 # of their own beside a header of their own: C_ENTRIES stays fa_mi355x.h's
 TREE_ENTRIES = _tree_entries()
 
+_F = ctypes.c_float
+_MLA_CACHE = {"": [_I],                     # CONTIG: kv_capacity
+              "_paged": [_I, _I, _P, _I]}   # PAGED: num_pages, page_size, block_table, max_pages_per_seq
+
+
+def _mla_entries():
+    """name -> (restype, argtypes) of every function include/fa_mi355x_mla.h
+    declares: q, ckv, o, lse; batch, heads_q, seqlen_q; the cache group;
+    kv_lens, causal, softmax_scale; num_splits, workspace, ws_bytes; the stream."""
+    table = {"fa_mla_decode" + c + ty: (_I, [_P] * 4 + [_I] * 3 + _MLA_CACHE[c] + [_P, _I, _F]
+                                        + [_I, _P, _ULL] + _STREAM)
+             for c in ("", "_paged") for ty in ("_f16", "_bf16")}
+    table["fa_mla_decode_num_splits"] = (_I, [_I] * 4)
+    table["fa_mla_decode_ws_bytes"] = (_ULL, [_I] * 4)
+    return table
+
+
+# the MLA decode entries (attention over a latent cache), a table of their own
+# beside a header of their own, as the tree entries'
+MLA_ENTRIES = _mla_entries()
+
 
 @dataclass(frozen=True)
 class TileConfig:
@@ -201,7 +222,7 @@ def load_library() -> ctypes.CDLL:
             f"{LIB_PATH} not built (run `make -C {PKG_ROOT}` or __graft_entry__.build())",
         )
     lib = ctypes.CDLL(LIB_PATH)
-    for table in (C_ENTRIES, TREE_ENTRIES):
+    for table in (C_ENTRIES, TREE_ENTRIES, MLA_ENTRIES):
         for name, (restype, argtypes) in table.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
@@ -899,6 +920,158 @@ def flash_attention_decode_paged(q, k_pages, v_pages, block_table, kv_lens=None,
         _check_tree_rules(q, causal, window)
     return _decode_call(kv8, q, k_pages, v_pages, out, block_table, kv_lens, causal, return_lse,
                         num_splits, stream, k_scale, v_scale, window, sinks, tree_mask)
+
+
+MLA_DQK, MLA_DV = 576, 512  # dims of a latent / query row, and of the value it starts with
+_MLA_NEED = {}  # (device, B, Hq, Sq, cap, num_splits) -> (workspace bytes, pieces)
+
+
+def mla_decode_num_splits(batch: int, heads_q: int, seqlen_q: int, kv_capacity: int, device=None) -> int:
+    """Pieces the MLA decode entry's plan cuts each latent cache into on `device` (1: no split)."""
+    import torch
+
+    dev = torch.cuda.current_device() if device is None else torch.device(device).index
+    with torch.cuda.device(dev):
+        return load_library().fa_mla_decode_num_splits(batch, heads_q, seqlen_q, kv_capacity)
+
+
+def _check_mla(q, cname, ckv, block_table, kv_lens, out, softmax_scale):
+    """Raise FlashAttentionError unless q is a contiguous [B,Hq,Sq,576] and out a
+    contiguous [B,Hq,Sq,512] tensor of one 16-bit dtype, the latent cache a
+    contiguous [B,cap,576] tensor (no block table) or [num_pages,page_size,576]
+    pool (page_size % 64 == 0) of that dtype, the table int32 [B,max_pages] and
+    kv_lens (if given) int32 [B], all on q's device, and softmax_scale a finite
+    number > 0.  Worded and ordered like the decode checks: the scale, dtypes,
+    ranks and shapes before where the tensors live."""
+    import math
+
+    import torch
+
+    if isinstance(softmax_scale, bool) or not isinstance(softmax_scale, (int, float)):
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE,
+                                  f"softmax_scale must be a number, got {type(softmax_scale).__name__}")
+    if not (math.isfinite(softmax_scale) and softmax_scale > 0):
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"softmax_scale must be finite and > 0, got {softmax_scale}")
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"q must be float16 or bfloat16, got {q.dtype}")
+    paged = block_table is not None
+    for name, t, rank in (("q", q, 4), (cname, ckv, 3), ("out", out, 4)):
+        if t.dtype != q.dtype:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be {q.dtype}, got {t.dtype}")
+        if t.dim() != rank:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be {rank}-D")
+        if not t.is_contiguous():
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be contiguous")
+    if q.shape[3] != MLA_DQK or ckv.shape[2] != MLA_DQK:
+        raise FlashAttentionError(FA_ERR_UNSUPPORTED_HEAD_DIM,
+                                  f"q and {cname} must have a last dim of {MLA_DQK} ([c_kv 512 | k_pe 64])")
+    if tuple(out.shape) != (*q.shape[:3], MLA_DV):
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"out must be [B,Hq,Sq,{MLA_DV}] beside q [B,Hq,Sq,{MLA_DQK}]")
+    if paged:
+        if ckv.shape[0] == 0:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, "the page pool holds no page")
+        if ckv.shape[1] == 0 or ckv.shape[1] % 64 != 0:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE,
+                                      f"page_size {ckv.shape[1]} is not a positive multiple of 64")
+        _check_table_type(block_table)
+        if block_table.shape[0] != q.shape[0]:
+            raise FlashAttentionError(
+                FA_ERR_BAD_SHAPE, f"block_table has {block_table.shape[0]} rows, q a batch of {q.shape[0]}")
+        if not block_table.is_contiguous():
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, "block_table must be contiguous")
+    elif ckv.shape[0] != q.shape[0]:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"q and {cname} must agree in batch")
+    if kv_lens is not None:
+        if kv_lens.dtype != torch.int32:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"kv_lens must be int32, got {kv_lens.dtype}")
+        if kv_lens.dim() != 1 or kv_lens.shape[0] != q.shape[0] or not kv_lens.is_contiguous():
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, "kv_lens must be a contiguous [B] tensor")
+    for name, t in (("q", q), (cname, ckv), ("out", out)):
+        if not t.is_cuda:
+            raise FlashAttentionError(FA_ERR_NULL_POINTER, f"{name} must be a device tensor")
+        if t.device != q.device:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} is on {t.device}, q on {q.device}: one device only")
+    for name, t in (("block_table", block_table), ("kv_lens", kv_lens)):
+        if t is not None and (not t.is_cuda or t.device != q.device):
+            raise FlashAttentionError(FA_ERR_NULL_POINTER, f"{name} must be a tensor on {q.device}")
+
+
+def _mla_call(q, cname, ckv, block_table, kv_lens, softmax_scale, causal, out, return_lse, num_splits, stream):
+    """Both MLA decode functions: out, the checks, the optional LSE, the split
+    plan and its workspace (the decode functions' per-(device, stream) buffer)
+    and the fa_mla_decode* entry."""
+    import torch
+
+    if out is None:
+        out = torch.empty((*q.shape[:-1], MLA_DV), dtype=q.dtype, device=q.device)
+    _check_mla(q, cname, ckv, block_table, kv_lens, out, softmax_scale)
+    b, hq, sq, _ = q.shape
+    paged = block_table is not None
+    cap = ckv.shape[1] * (block_table.shape[1] if paged else 1)
+    dev = q.device.index
+    st = _raw_stream(stream, dev)
+    lse = torch.empty((b, hq, sq), dtype=torch.float32, device=q.device) if return_lse else None
+    ns = int(num_splits)
+    need = 0
+    if 0 < cap <= 0x7fffffff - 64 and 0 <= ns <= 64:  # (otherwise the entry itself refuses or fills)
+        key = (dev, b, hq, sq, cap, ns)
+        need = _MLA_NEED.get(key)
+        if need is None or need:
+            with torch.cuda.device(dev):
+                if need is None:
+                    pieces = ns or _entry("fa_mla_decode_num_splits")(b, hq, sq, cap)
+                    need = _MLA_NEED[key] = _entry("fa_mla_decode_ws_bytes")(b, hq, sq, pieces)
+                ws = _workspace(need, dev, st) if need else None  # (a tensor: alive until the launch)
+    cache = ((ckv.shape[0], ckv.shape[1], block_table.data_ptr(), block_table.shape[1]) if paged
+             else (ckv.shape[1],))
+    _launch("fa_mla_decode" + ("_paged" if paged else "") + ("_bf16" if q.dtype is torch.bfloat16 else "_f16"),
+            dev, st,
+            (q.data_ptr(), ckv.data_ptr(), out.data_ptr(), lse.data_ptr() if return_lse else None, b, hq, sq,
+             *cache, kv_lens.data_ptr() if kv_lens is not None else None, int(bool(causal)),
+             float(softmax_scale), ns, ws.data_ptr() if need else None, need))
+    return (out, lse) if return_lse else out
+
+
+def flash_attention_mla_decode(q, ckv_cache, kv_lens=None, *, softmax_scale, causal: bool = True, out=None,
+                               return_lse: bool = False, num_splits: int = 0, stream=None):
+    """MLA decode: attention over a latent K/V cache in the weight-absorbed
+    form of DeepSeek-V2 / V3 / R1 and Kimi K2 (fa_mla_decode_f16 / _bf16 of
+    include/fa_mi355x_mla.h).
+
+    q: [B, Hq, Sq, 576] (1 <= Sq <= 16, any Hq), W_UK absorbed into q_nope and
+    q_pe appended; ckv_cache: [B, cap, 576], one shared row [c_kv (512) | k_pe
+    (64)] per token; fp16 or bf16 contiguous device tensors of one dtype.  The
+    score contracts over all 576 dims, the value is the row's first 512:
+    returns out [B, Hq, Sq, 512] (the caller applies W_UV), or (out, lse) with
+    lse fp32 [B, Hq, Sq] (natural log) when return_lse.  softmax_scale is
+    required -- the model's own (1/sqrt(192) times its YaRN factor), not
+    1/sqrt(576).  kv_lens: int32 [B] on the same device (None: every length is
+    cap); rows past a length are never read.  causal: bottom-right aligned
+    (token t sees keys <= len - Sq + t).  num_splits: 0 = the plan's choice
+    (:func:`mla_decode_num_splits`), > 0 forces that many key pieces.  Nothing
+    is copied or cast.  Enqueued on ``stream`` (default: torch's current
+    stream); no sync, graph-capturable; a split launch takes its workspace
+    from the decode functions' per-(device, stream) buffer."""
+    return _mla_call(q, "ckv_cache", ckv_cache, None, kv_lens, softmax_scale, causal, out, return_lse,
+                     num_splits, stream)
+
+
+def flash_attention_mla_decode_paged(q, ckv_pages, block_table, kv_lens=None, *, softmax_scale,
+                                     causal: bool = True, out=None, return_lse: bool = False,
+                                     num_splits: int = 0, stream=None):
+    """:func:`flash_attention_mla_decode` over a paged latent cache
+    (fa_mla_decode_paged_f16 / _bf16): ckv_pages is the pool [num_pages,
+    page_size, 576] with page_size % 64 == 0 and block_table int32 [B,
+    max_pages_per_seq], entry j of row b the pool page holding keys [j *
+    page_size, (j + 1) * page_size) of element b.  kv_lens None: every length
+    is max_pages_per_seq * page_size.  Only table entries and rows below a
+    length are read, nothing is validated on the host, and a page id outside
+    the pool reads as zero rows.  The result equals the contiguous function's
+    on the gathered cache bit for bit at the same num_splits."""
+    if block_table is None:
+        raise FlashAttentionError(FA_ERR_NULL_POINTER, "block_table must be a tensor")
+    return _mla_call(q, "ckv_pages", ckv_pages, block_table, kv_lens, softmax_scale, causal, out, return_lse,
+                     num_splits, stream)
 
 
 def _prefill_call(family, kv8, q, k, v, out, batch, seqlen_q, block_table, kv_lens, q_lens, causal,

@@ -134,10 +134,11 @@ class _Op:
     as_is: set = frozenset(_CACHE_OPS_AS_IS)
     returns: str = "Tensor"
     forward_only: bool = True  # the Autograd fallthrough and the forward-only guard
+    guard: int = 3  # the leading tensors the guard looks at (2: an op whose third argument is no tensor)
 
 
-def _no_grad_needed(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> None:
-    if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
+def _no_grad_needed(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor = None) -> None:
+    if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or (v is not None and v.requires_grad)):
         raise RuntimeError("fa_mi355x::fwd is forward-only (no backward): call it under "
                            "torch.no_grad() / inference_mode or on tensors that do not require grad")
 
@@ -150,7 +151,7 @@ def _register(op: _Op, lib=None, ns: str = "fa_mi355x") -> None:
     full = op.packet + ("." + op.overload if op.overload else "")
     names = [n for _, n, _ in op.args]
     defaults = {n: d for _, n, d in op.args if d is not _REQUIRED}
-    fn, fake, guarded = op.fn, op.fake, op.forward_only
+    fn, fake, guarded, nguard = op.fn, op.fake, op.forward_only, op.guard
     # The dispatcher hands a kernel positionals only and leaves out the trailing
     # ones that equal their defaults, which are fn's own defaults too.  So the call
     # path is a few list operations: the given arguments go to fn as they come,
@@ -171,7 +172,7 @@ def _register(op: _Op, lib=None, ns: str = "fa_mi355x") -> None:
 
     def gpu(*a):
         if guarded:
-            _no_grad_needed(a[0], a[1], a[2])
+            _no_grad_needed(a[0], a[1], a[2] if nguard == 3 else None)
         vals = list(a)
         for i in dense[len(a)]:
             x = a[i]
@@ -187,7 +188,7 @@ def _register(op: _Op, lib=None, ns: str = "fa_mi355x") -> None:
     def fake_impl(*a, **kw):
         vals = {**defaults, **dict(zip(names, a)), **kw}
         if guarded:
-            _no_grad_needed(*(vals[n] for n in names[:3]))
+            _no_grad_needed(*(vals[n] for n in names[:nguard]))
         return fake(vals)
 
     schema = ", ".join("%s %s%s" % (ty, n, "" if d is _REQUIRED else "=" + str(d)) for ty, n, d in op.args)
