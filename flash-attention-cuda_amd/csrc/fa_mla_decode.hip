@@ -7,7 +7,7 @@
 
 using namespace fa;
 
-FA_MLA_ENTRIES(fa_mla_decode, CONTIG, false)
+FA_MLA_ENTRIES(fa_mla_decode, CONTIG, false, KV16)
 
 extern "C" int fa_mla_decode_num_splits(int batch, int heads_q, int seqlen_q, int kv_capacity) {
   return mla_plan(mla_geom(batch, heads_q, seqlen_q), kv_capacity);

@@ -5,4 +5,4 @@
 // the build stays parallel.
 #include "fa_mla_decode_host.hpp"
 
-FA_MLA_ENTRIES(fa_mla_decode_paged, PAGED, true)
+FA_MLA_ENTRIES(fa_mla_decode_paged, PAGED, true, KV16)

@@ -188,6 +188,10 @@ def _mla_entries():
 # the MLA decode entries (attention over a latent cache), a table of their own
 # beside a header of their own, as the tree entries'
 MLA_ENTRIES = _mla_entries()
+# the same over an FP8 (E4M3) latent cache, include/fa_mi355x_mla_kv8.h: each
+# 16-bit launch entry's list followed by `ckv_scale`, after the stream
+MLA_KV8_ENTRIES = {"fa_mla_decode" + c + "_kv8" + ty: (_I, MLA_ENTRIES["fa_mla_decode" + c + ty][1] + [_P])
+                   for c in ("", "_paged") for ty in ("_f16", "_bf16")}
 
 
 @dataclass(frozen=True)
@@ -222,7 +226,7 @@ def load_library() -> ctypes.CDLL:
             f"{LIB_PATH} not built (run `make -C {PKG_ROOT}` or __graft_entry__.build())",
         )
     lib = ctypes.CDLL(LIB_PATH)
-    for table in (C_ENTRIES, TREE_ENTRIES, MLA_ENTRIES):
+    for table in (C_ENTRIES, TREE_ENTRIES, MLA_ENTRIES, MLA_KV8_ENTRIES):
         for name, (restype, argtypes) in table.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
@@ -935,14 +939,16 @@ def mla_decode_num_splits(batch: int, heads_q: int, seqlen_q: int, kv_capacity: 
         return load_library().fa_mla_decode_num_splits(batch, heads_q, seqlen_q, kv_capacity)
 
 
-def _check_mla(q, cname, ckv, block_table, kv_lens, out, softmax_scale):
+def _check_mla(q, cname, ckv, block_table, kv_lens, out, softmax_scale, kv8=False, ckv_scale=None):
     """Raise FlashAttentionError unless q is a contiguous [B,Hq,Sq,576] and out a
     contiguous [B,Hq,Sq,512] tensor of one 16-bit dtype, the latent cache a
     contiguous [B,cap,576] tensor (no block table) or [num_pages,page_size,576]
     pool (page_size % 64 == 0) of that dtype, the table int32 [B,max_pages] and
     kv_lens (if given) int32 [B], all on q's device, and softmax_scale a finite
     number > 0.  Worded and ordered like the decode checks: the scale, dtypes,
-    ranks and shapes before where the tensors live."""
+    ranks and shapes before where the tensors live.  kv8: the cache holds
+    E4M3 bytes (torch.float8_e4m3fn or torch.uint8) and ckv_scale (if given) is
+    a contiguous float32 tensor of one element on q's device."""
     import math
 
     import torch
@@ -956,7 +962,11 @@ def _check_mla(q, cname, ckv, block_table, kv_lens, out, softmax_scale):
         raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"q must be float16 or bfloat16, got {q.dtype}")
     paged = block_table is not None
     for name, t, rank in (("q", q, 4), (cname, ckv, 3), ("out", out, 4)):
-        if t.dtype != q.dtype:
+        if kv8 and t is ckv:
+            if t.dtype not in (torch.float8_e4m3fn, torch.uint8):
+                raise FlashAttentionError(FA_ERR_BAD_SHAPE,
+                                          f"{name} must be torch.float8_e4m3fn or torch.uint8, got {t.dtype}")
+        elif t.dtype != q.dtype:
             raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be {q.dtype}, got {t.dtype}")
         if t.dim() != rank:
             raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be {rank}-D")
@@ -986,25 +996,30 @@ def _check_mla(q, cname, ckv, block_table, kv_lens, out, softmax_scale):
             raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"kv_lens must be int32, got {kv_lens.dtype}")
         if kv_lens.dim() != 1 or kv_lens.shape[0] != q.shape[0] or not kv_lens.is_contiguous():
             raise FlashAttentionError(FA_ERR_BAD_SHAPE, "kv_lens must be a contiguous [B] tensor")
+    if ckv_scale is not None:
+        if ckv_scale.dtype != torch.float32 or ckv_scale.numel() != 1 or not ckv_scale.is_contiguous():
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, "ckv_scale must be a contiguous float32 tensor of one element")
     for name, t in (("q", q), (cname, ckv), ("out", out)):
         if not t.is_cuda:
             raise FlashAttentionError(FA_ERR_NULL_POINTER, f"{name} must be a device tensor")
         if t.device != q.device:
             raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} is on {t.device}, q on {q.device}: one device only")
-    for name, t in (("block_table", block_table), ("kv_lens", kv_lens)):
+    for name, t in (("block_table", block_table), ("kv_lens", kv_lens), ("ckv_scale", ckv_scale)):
         if t is not None and (not t.is_cuda or t.device != q.device):
             raise FlashAttentionError(FA_ERR_NULL_POINTER, f"{name} must be a tensor on {q.device}")
 
 
-def _mla_call(q, cname, ckv, block_table, kv_lens, softmax_scale, causal, out, return_lse, num_splits, stream):
-    """Both MLA decode functions: out, the checks, the optional LSE, the split
-    plan and its workspace (the decode functions' per-(device, stream) buffer)
-    and the fa_mla_decode* entry."""
+def _mla_call(q, cname, ckv, block_table, kv_lens, softmax_scale, causal, out, return_lse, num_splits, stream,
+              kv8=False, ckv_scale=None):
+    """The four MLA decode functions: out, the checks, the optional LSE, the
+    split plan and its workspace (the decode functions' per-(device, stream)
+    buffer) and the fa_mla_decode* entry; kv8: the E4M3 cache's entry, with
+    ckv_scale after the stream."""
     import torch
 
     if out is None:
         out = torch.empty((*q.shape[:-1], MLA_DV), dtype=q.dtype, device=q.device)
-    _check_mla(q, cname, ckv, block_table, kv_lens, out, softmax_scale)
+    _check_mla(q, cname, ckv, block_table, kv_lens, out, softmax_scale, kv8, ckv_scale)
     b, hq, sq, _ = q.shape
     paged = block_table is not None
     cap = ckv.shape[1] * (block_table.shape[1] if paged else 1)
@@ -1024,11 +1039,12 @@ def _mla_call(q, cname, ckv, block_table, kv_lens, softmax_scale, causal, out, r
                 ws = _workspace(need, dev, st) if need else None  # (a tensor: alive until the launch)
     cache = ((ckv.shape[0], ckv.shape[1], block_table.data_ptr(), block_table.shape[1]) if paged
              else (ckv.shape[1],))
-    _launch("fa_mla_decode" + ("_paged" if paged else "") + ("_bf16" if q.dtype is torch.bfloat16 else "_f16"),
-            dev, st,
+    _launch("fa_mla_decode" + ("_paged" if paged else "") + ("_kv8" if kv8 else "")
+            + ("_bf16" if q.dtype is torch.bfloat16 else "_f16"), dev, st,
             (q.data_ptr(), ckv.data_ptr(), out.data_ptr(), lse.data_ptr() if return_lse else None, b, hq, sq,
              *cache, kv_lens.data_ptr() if kv_lens is not None else None, int(bool(causal)),
-             float(softmax_scale), ns, ws.data_ptr() if need else None, need))
+             float(softmax_scale), ns, ws.data_ptr() if need else None, need),
+            ((ckv_scale.data_ptr() if ckv_scale is not None else None,) if kv8 else ()))
     return (out, lse) if return_lse else out
 
 
@@ -1072,6 +1088,36 @@ def flash_attention_mla_decode_paged(q, ckv_pages, block_table, kv_lens=None, *,
         raise FlashAttentionError(FA_ERR_NULL_POINTER, "block_table must be a tensor")
     return _mla_call(q, "ckv_pages", ckv_pages, block_table, kv_lens, softmax_scale, causal, out, return_lse,
                      num_splits, stream)
+
+
+def flash_attention_mla_decode_kv8(q, ckv_cache, kv_lens=None, *, ckv_scale=None, softmax_scale,
+                                   causal: bool = True, out=None, return_lse: bool = False, num_splits: int = 0,
+                                   stream=None):
+    """:func:`flash_attention_mla_decode` over an FP8 latent cache
+    (fa_mla_decode_kv8_f16 / _bf16 of include/fa_mi355x_mla_kv8.h): ckv_cache
+    is [B, cap, 576] of OCP E4M3 bytes (torch.float8_e4m3fn or torch.uint8) and
+    is read as ckv_scale * ckv_cache; ckv_scale: a float32 device tensor of one
+    element (None: 1.0), read on the device, so a captured graph follows a
+    rewritten scale.  q and out stay 16-bit and nothing is dequantised in
+    memory: the scale enters the score scale (and so lse) and the final
+    normalisation.  A writer stores E4M3(clamp(x / ckv_scale, -448, 448)),
+    round to nearest even.  Everything else is the 16-bit function's."""
+    return _mla_call(q, "ckv_cache", ckv_cache, None, kv_lens, softmax_scale, causal, out, return_lse,
+                     num_splits, stream, True, ckv_scale)
+
+
+def flash_attention_mla_decode_paged_kv8(q, ckv_pages, block_table, kv_lens=None, *, ckv_scale=None,
+                                         softmax_scale, causal: bool = True, out=None,
+                                         return_lse: bool = False, num_splits: int = 0, stream=None):
+    """:func:`flash_attention_mla_decode_kv8` over a paged FP8 latent cache
+    (fa_mla_decode_paged_kv8_f16 / _bf16): ckv_pages is the pool [num_pages,
+    page_size, 576] of E4M3 bytes with :func:`flash_attention_mla_decode_paged`'s
+    block table.  The result equals the contiguous function's on the gathered
+    cache bit for bit at the same num_splits."""
+    if block_table is None:
+        raise FlashAttentionError(FA_ERR_NULL_POINTER, "block_table must be a tensor")
+    return _mla_call(q, "ckv_pages", ckv_pages, block_table, kv_lens, softmax_scale, causal, out, return_lse,
+                     num_splits, stream, True, ckv_scale)
 
 
 def _prefill_call(family, kv8, q, k, v, out, batch, seqlen_q, block_table, kv_lens, q_lens, causal,

@@ -17,6 +17,12 @@ same bytes as a randomly permuted pool of 64-key pages; gathering them for the
 composition is not counted.
 
     python3 tools/mla_decode_bench.py [--out profiles/mla_decode_bench.jsonl] [--quick]
+
+--kv8: the FP8 latent cache's legs over the same shapes (fp16), kv8 kernel /
+16-bit kernel on the dequantised cache (the baseline) / kv8 kernel / dequantise
+into a 16-bit cache, then the 16-bit kernel (what a caller without the kv8
+entries does) / paged kv8 kernel; the copy-rate share is on B * len * 576
+bytes.  Default output profiles/mla_decode_kv8_bench.jsonl.
 """
 import argparse
 import json
@@ -77,19 +83,61 @@ def run(b, n, hq, sq, dtype, rounds=7):
                 nonfinite_composition=nonfinite[1], paged_equals_contig=same)
 
 
+def run_kv8(b, n, hq, sq, dtype, rounds=7):
+    dev = "cuda"
+    scale, ckv = 192 ** -0.5, 0.37
+    copies = max(1, -(-(512 << 20) // (b * n * DQK)))
+    gen = torch.Generator(device=dev).manual_seed(b * 131 + n + hq + sq)
+    q = (torch.rand((b, hq, sq, DQK), generator=gen, device=dev) * 2 - 1).to(dtype)
+    c8s = [((torch.rand((b, n, DQK), generator=gen, device=dev) * 2 - 1) / ckv).to(torch.float8_e4m3fn)
+           for _ in range(copies)]
+    sc = torch.tensor([ckv], dtype=torch.float32, device=dev)
+    deq = lambda c8: (c8.to(torch.float32) * sc).to(dtype)
+    c16s = [deq(c8) for c8 in c8s[:max(1, copies // 2)]]  # 16-bit rows are twice the bytes
+    lens = torch.full((b,), n, dtype=torch.int32, device=dev)
+    perm = torch.randperm(b * n // PAGE, generator=gen, device=dev)
+    table = torch.empty_like(perm)
+    table[perm] = torch.arange(perm.numel(), device=dev)
+    pools = [c.view(-1, PAGE, DQK)[perm].contiguous() for c in c8s]
+    table = table.view(b, n // PAGE).to(torch.int32)
+    kw = dict(softmax_scale=scale, causal=False)
+    kv8 = lambda i: fa_mi355x.flash_attention_mla_decode_kv8(q, c8s[i % copies], lens, ckv_scale=sc, **kw)
+    fns = [kv8,
+           lambda i: fa_mi355x.flash_attention_mla_decode(q, c16s[i % len(c16s)], lens, **kw),
+           kv8,
+           lambda i: fa_mi355x.flash_attention_mla_decode(q, deq(c8s[i % copies]), lens, **kw),
+           lambda i: fa_mi355x.flash_attention_mla_decode_paged_kv8(q, pools[i % copies], table, lens, ckv_scale=sc,
+                                                                    **kw)]
+    diff = float((fns[0](0).float() - fns[1](0).float()).abs().max())
+    same = bool(torch.equal(fns[0](0), fns[4](0)))
+    iters = 20 if b * n <= 64 * 4096 else 5
+    t_k, t_16, t_k2, t_dq, t_p = time_pair(fns, iters, rounds)
+    rows = hq * sq
+    return dict(name=f"B={b} len={n} Hq={hq} Sq={sq}", dtype=str(dtype).split(".")[-1],
+                regime="narrow" if rows <= 16 else "wide",
+                num_splits=fa_mi355x.mla_decode_num_splits(b, hq, sq, n), copies=copies,
+                kv8_us=round(t_k, 2), aa=round(t_k2 / t_k, 4), kernel16_us=round(t_16, 2),
+                kv8_over_kernel16=round(t_k / t_16, 4), dequant_then_kernel16_us=round(t_dq, 2),
+                dequant_over_kv8=round(t_dq / t_k, 3), paged_us=round(t_p, 2), paged_over_contig=round(t_p / t_k, 4),
+                share_of_copy_rate=round(b * n * DQK / (t_k * 1e-6) / COPY_RATE, 4),
+                tflops=round(2.0 * b * rows * n * (DQK + DV) / (t_k * 1e-6) / 1e12, 2),
+                max_abs_diff_vs_kernel16=diff, paged_equals_contig=same)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="default profiles/mla_decode_bench.jsonl")
     ap.add_argument("--quick", action="store_true", help="B = 64 at 4k keys, fp16 only")
+    ap.add_argument("--kv8", action="store_true", help="the FP8 latent cache's legs (fp16)")
     args = ap.parse_args()
     root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..")
-    out = args.out or os.path.join(root, "profiles", "mla_decode_bench.jsonl")
+    out = args.out or os.path.join(root, "profiles", "mla_decode_kv8_bench.jsonl" if args.kv8 else "mla_decode_bench.jsonl")
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     with open(out, "w") as f:
-        for dtype in (torch.float16,) if args.quick else (torch.float16, torch.bfloat16):
+        for dtype in (torch.float16,) if args.quick or args.kv8 else (torch.float16, torch.bfloat16):
             for b, n in ((64, 4096),) if args.quick else ((64, 4096), (64, 32768), (1, 4096), (1, 32768)):
                 for hq, sq in ((16, 1), (128, 1), (128, 2)):
-                    rec = run(b, n, hq, sq, dtype)
+                    rec = (run_kv8 if args.kv8 else run)(b, n, hq, sq, dtype)
                     print(json.dumps(rec), flush=True)
                     f.write(json.dumps(rec) + "\n")
                     torch.cuda.empty_cache()
