@@ -192,6 +192,11 @@ MLA_ENTRIES = _mla_entries()
 # 16-bit launch entry's list followed by `ckv_scale`, after the stream
 MLA_KV8_ENTRIES = {"fa_mla_decode" + c + "_kv8" + ty: (_I, MLA_ENTRIES["fa_mla_decode" + c + ty][1] + [_P])
                    for c in ("", "_paged") for ty in ("_f16", "_bf16")}
+# MLA prefill (the non-absorbed 192/128 form), include/fa_mi355x_mla_prefill.h:
+# the fa_attn_varlen_* list without head_dim and with softmax_scale after causal
+MLA_PREFILL_ENTRIES = {"fa_mla_prefill_varlen" + ty: (_I, _QKVO_LSE + _ATTN_DIMS[:-1] + _STRIDES + _ATTN_SEQS
+                                                      + [_F] + _STREAM)
+                       for ty in ("_f16", "_bf16")}
 
 
 @dataclass(frozen=True)
@@ -226,7 +231,7 @@ def load_library() -> ctypes.CDLL:
             f"{LIB_PATH} not built (run `make -C {PKG_ROOT}` or __graft_entry__.build())",
         )
     lib = ctypes.CDLL(LIB_PATH)
-    for table in (C_ENTRIES, TREE_ENTRIES, MLA_ENTRIES, MLA_KV8_ENTRIES):
+    for table in (C_ENTRIES, TREE_ENTRIES, MLA_ENTRIES, MLA_KV8_ENTRIES, MLA_PREFILL_ENTRIES):
         for name, (restype, argtypes) in table.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
@@ -1675,6 +1680,164 @@ def flash_attention_bshd(q, k, v, causal: bool = False, out=None, return_lse: bo
     lse = torch.empty((hq, b * sq), dtype=torch.float32, device=q.device) if return_lse else None
     _attn_call(q, k, v, out, strides, b, b * sq, b * sk, None, None, sq, sk, causal, lse, stream, window,
                sinks)
+    return (out, lse.view(hq, b, sq).permute(1, 0, 2)) if return_lse else out
+
+
+MLA_PREFILL_DQK, MLA_PREFILL_DV = 192, 128  # dims of a query / key row ([k_nope 128 | k_pe 64]) and of a value row
+
+
+def _check_mla_prefill(q, k, v, out, rank, cu_q, cu_k, softmax_scale):
+    """What flash_attention_mla_prefill_varlen (rank 3) and _bshd (rank 4)
+    check, in _check_attn's order behind _check_mla's scale check: the scale,
+    dtypes, ranks and shapes, then where the tensors live, never values.
+    Returns the three token strides."""
+    import math
+
+    import torch
+
+    dqk, dv = MLA_PREFILL_DQK, MLA_PREFILL_DV
+    layout = " [T,H,D]" if rank == 3 else " [B,S,H,D]"
+    if isinstance(softmax_scale, bool) or not isinstance(softmax_scale, (int, float)):
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE,
+                                  f"softmax_scale must be a number, got {type(softmax_scale).__name__}")
+    if not (math.isfinite(softmax_scale) and softmax_scale > 0):
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"softmax_scale must be finite and > 0, got {softmax_scale}")
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"q must be float16 or bfloat16, got {q.dtype}")
+    for name, t in (("q", q), ("k", k), ("v", v), ("out", out)):
+        if t.dtype != q.dtype:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be {q.dtype}, got {t.dtype}")
+        if t.dim() != rank:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be {rank}-D{layout}")
+    if q.shape[-1] != dqk or k.shape[-1] != dqk or v.shape[-1] != dv:
+        raise FlashAttentionError(
+            FA_ERR_UNSUPPORTED_HEAD_DIM,
+            f"q and k must have a last dim of {dqk} ([k_nope 128 | k_pe 64]) and v one of {dv}")
+    if not out.is_contiguous():
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"out must be contiguous{layout}")
+    if tuple(out.shape) != (*q.shape[:-1], dv):
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"out must be{layout} like q with a last dim of {dv}")
+    if k.shape[:-1] != v.shape[:-1]:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, "k and v must have one shape but for the last dim")
+    if rank == 4 and k.shape[0] != q.shape[0]:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, "q, k and v must agree in batch")
+    strides = tuple(_token_stride(t, name, rank) for name, t in (("q", q), ("k", k), ("v", v)))
+    hq, hkv = q.shape[-2], k.shape[-2]
+    if hkv == 0 or hq % hkv != 0:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"heads_q {hq} is not a multiple of heads_kv {hkv}")
+    nseq = 0
+    if rank == 3:
+        if cu_q is None:
+            _check_cu_seqlens(None, "cu_seqlens_q", 0, q, False)
+        if cu_q.dim() != 1 or cu_q.shape[0] < 1:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, "cu_seqlens_q must be a [B + 1] tensor")
+        nseq = cu_q.shape[0] - 1
+        _check_cu_seqlens(cu_q, "cu_seqlens_q", nseq, q, False)
+        if cu_k is not None:
+            _check_cu_seqlens(cu_k, "cu_seqlens_k", nseq, q, False)
+    for name, t in (("q", q), ("k", k), ("v", v), ("out", out)):
+        if not t.is_cuda:
+            raise FlashAttentionError(FA_ERR_NULL_POINTER, f"{name} must be a device tensor")
+        if t.device != q.device:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE,
+                                      f"{name} is on {t.device}, q on {q.device}: one device only")
+    if rank == 3:
+        _check_cu_seqlens(cu_q, "cu_seqlens_q", nseq, q, True)
+        if cu_k is not None:
+            _check_cu_seqlens(cu_k, "cu_seqlens_k", nseq, q, True)
+    return strides
+
+
+def _mla_prefill_call(q, k, v, out, strides, batch, total_q, total_k, cu_q, cu_k, seqlen_q, seqlen_k, causal,
+                      softmax_scale, lse, stream):
+    """The call of the two functions below after their checks: the
+    fa_mla_prefill_varlen_* entry of q's dtype."""
+    import torch
+
+    _launch("fa_mla_prefill_varlen" + ("_bf16" if q.dtype is torch.bfloat16 else "_f16"), q.device.index, stream,
+            (q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
+             lse.data_ptr() if lse is not None else None, batch, q.shape[-2], k.shape[-2], total_q, total_k,
+             *strides, cu_q.data_ptr() if cu_q is not None else None,
+             cu_k.data_ptr() if cu_k is not None else None, seqlen_q, seqlen_k, int(bool(causal)),
+             float(softmax_scale)))
+
+
+def flash_attention_mla_prefill_varlen(q, k, v, cu_seqlens_q=None, cu_seqlens_k=None, *, softmax_scale,
+                                       causal: bool = True, seqlen_q=None, seqlen_k=None, out=None,
+                                       return_lse: bool = False, stream=None):
+    """MLA prefill (fa_mla_prefill_varlen_f16 / _bf16; flash-attn's
+    ``flash_attn_varlen_func`` at headdim 192 / headdim_v 128): attention over
+    token-major Q, K and V in the non-absorbed form of Multi-head Latent
+    Attention, the prompt's half of the layer that
+    :func:`flash_attention_mla_decode` decodes.
+
+    q: [T_q, Hq, 192]; k: [T_k, Hkv, 192] = [k_nope (128) | k_pe (64)]; v:
+    [T_k, Hkv, 128]; Hq % Hkv == 0; fp16 or bf16 device tensors of one dtype.
+    Each may be a VIEW as for :func:`flash_attention_varlen` (last two dims
+    contiguous, token stride a multiple of 8 elements): v is read in place as
+    the second half ``kv.view(T, 2, Hkv, 128)[:, 1]`` of a per-token buffer
+    [k_nope (Hkv * 128) | v (Hkv * 128)].  The per-head interleaved layout,
+    ``kv.view(T, Hkv, 256)[..., 128:]`` (kv_b_proj's output under the usual
+    weight order), has stride(-2) == 256 and raises: there is no head stride;
+    permute the projection's weight rows once, or ``.contiguous()`` the slice.
+    Anything else raises too (nothing is ever copied).  softmax_scale
+    (required, finite, > 0) is the model's (192**-0.5 * mscale**2); the scores
+    are scaled in fp32.  cu_seqlens_q, cu_seqlens_k, causal (bottom-right), the
+    rows of no sequence and a row that sees no key: as for
+    :func:`flash_attention_varlen`.  cu_seqlens_q=None: uniform lengths, q
+    [B * seqlen_q, ...] and k, v [B * seqlen_k, ...] with seqlen_q and
+    seqlen_k given, and no array is read.  causal=False with return_lse is the
+    chunked-prefill context call, whose partial results merge by LSE.  out: a
+    contiguous [T_q, Hq, 128] tensor.  Returns out, or (out, lse) with lse fp32
+    [Hq, T_q] (natural log) when return_lse.  No sync, no workspace,
+    graph-capturable."""
+    import torch
+
+    if out is None:
+        out = torch.empty((*q.shape[:-1], MLA_PREFILL_DV), dtype=q.dtype, device=q.device)
+    total_q, total_k = q.shape[0], k.shape[0]
+    if (seqlen_q is None) != (seqlen_k is None):
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, "seqlen_q and seqlen_k (the uniform mode) must be given together")
+    if seqlen_q is not None and (cu_seqlens_q is not None or cu_seqlens_k is not None):
+        raise FlashAttentionError(
+            FA_ERR_BAD_SHAPE, "give cu_seqlens_q [and cu_seqlens_k] or seqlen_q and seqlen_k (the uniform mode), not both")
+    if seqlen_q is not None:
+        # the uniform mode on token-major tensors
+        strides = _check_mla_prefill(q[None], k[None], v[None], out[None], 4, None, None, softmax_scale)
+        if (not isinstance(seqlen_q, int) or not isinstance(seqlen_k, int) or seqlen_q <= 0 or seqlen_k < 0
+                or total_q % seqlen_q != 0 or total_q // seqlen_q * seqlen_k != total_k):
+            raise FlashAttentionError(
+                FA_ERR_BAD_SHAPE,
+                f"uniform lengths: T_q = {total_q} and T_k = {total_k} must be B * seqlen_q and B * seqlen_k, "
+                f"got seqlen_q = {seqlen_q}, seqlen_k = {seqlen_k}")
+        batch, sq, sk = total_q // seqlen_q, seqlen_q, seqlen_k
+    else:
+        strides = _check_mla_prefill(q, k, v, out, 3, cu_seqlens_q, cu_seqlens_k, softmax_scale)
+        batch, sq, sk = cu_seqlens_q.shape[0] - 1, 0, 0
+    lse = torch.empty((q.shape[1], total_q), dtype=torch.float32, device=q.device) if return_lse else None
+    _mla_prefill_call(q, k, v, out, strides, batch, total_q, total_k, cu_seqlens_q, cu_seqlens_k, sq, sk, causal,
+                      softmax_scale, lse, stream)
+    return (out, lse) if return_lse else out
+
+
+def flash_attention_mla_prefill_bshd(q, k, v, *, softmax_scale, causal: bool = True, out=None,
+                                     return_lse: bool = False, stream=None):
+    """:func:`flash_attention_mla_prefill_varlen` for uniform lengths: q [B, Sq,
+    Hq, 192], k [B, Sk, Hkv, 192], v [B, Sk, Hkv, 128], taken as they are (the
+    entries' uniform mode, no cu_seqlens tensor); views as for
+    :func:`flash_attention_bshd`.  Returns out [B, Sq, Hq, 128] (contiguous), or
+    (out, lse) with lse a [B, Hq, Sq] VIEW of the fp32 [Hq, B * Sq] result when
+    return_lse."""
+    import torch
+
+    if out is None:
+        out = torch.empty((*q.shape[:-1], MLA_PREFILL_DV), dtype=q.dtype, device=q.device)
+    strides = _check_mla_prefill(q, k, v, out, 4, None, None, softmax_scale)
+    b, sq, hq, _ = q.shape
+    sk = k.shape[1]
+    lse = torch.empty((hq, b * sq), dtype=torch.float32, device=q.device) if return_lse else None
+    _mla_prefill_call(q, k, v, out, strides, b, b * sq, b * sk, None, None, sq, sk, causal, softmax_scale, lse,
+                      stream)
     return (out, lse.view(hq, b, sq).permute(1, 0, 2)) if return_lse else out
 
 
