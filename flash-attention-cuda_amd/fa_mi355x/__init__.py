@@ -197,6 +197,11 @@ MLA_KV8_ENTRIES = {"fa_mla_decode" + c + "_kv8" + ty: (_I, MLA_ENTRIES["fa_mla_d
 MLA_PREFILL_ENTRIES = {"fa_mla_prefill_varlen" + ty: (_I, _QKVO_LSE + _ATTN_DIMS[:-1] + _STRIDES + _ATTN_SEQS
                                                       + [_F] + _STREAM)
                        for ty in ("_f16", "_bf16")}
+# MLA sparse attention (top-k rows of a latent pool per query token),
+# include/fa_mi355x_mla_sparse.h: q, ckv, indices, o, lse; num_tokens, heads_q,
+# topk, num_rows; softmax_scale; num_splits, workspace, ws_bytes; the stream
+MLA_SPARSE_ENTRIES = {"fa_mla_sparse" + ty: (_I, [_P] * 5 + [_I] * 4 + [_F] + [_I, _P, _ULL] + _STREAM)
+                      for ty in ("_f16", "_bf16")}
 
 
 @dataclass(frozen=True)
@@ -231,7 +236,7 @@ def load_library() -> ctypes.CDLL:
             f"{LIB_PATH} not built (run `make -C {PKG_ROOT}` or __graft_entry__.build())",
         )
     lib = ctypes.CDLL(LIB_PATH)
-    for table in (C_ENTRIES, TREE_ENTRIES, MLA_ENTRIES, MLA_KV8_ENTRIES, MLA_PREFILL_ENTRIES):
+    for table in (C_ENTRIES, TREE_ENTRIES, MLA_ENTRIES, MLA_KV8_ENTRIES, MLA_PREFILL_ENTRIES, MLA_SPARSE_ENTRIES):
         for name, (restype, argtypes) in table.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
@@ -1123,6 +1128,110 @@ def flash_attention_mla_decode_paged_kv8(q, ckv_pages, block_table, kv_lens=None
         raise FlashAttentionError(FA_ERR_NULL_POINTER, "block_table must be a tensor")
     return _mla_call(q, "ckv_pages", ckv_pages, block_table, kv_lens, softmax_scale, causal, out, return_lse,
                      num_splits, stream, True, ckv_scale)
+
+
+def _check_mla_sparse(q, ckv, indices, out, softmax_scale):
+    """Raise FlashAttentionError unless q is a contiguous [N,Hq,576] or
+    [B,Sq,Hq,576] tensor of a 16-bit dtype, indices a contiguous int32 tensor of
+    q's leading shape (all but Hq and 576) and a last dim of topk, ckv a
+    contiguous tensor of q's dtype with at least two dims and a last dim of 576,
+    out a contiguous tensor of q's dtype and shape but for a last dim of 512,
+    all on q's device, and softmax_scale a finite number > 0.  Ordered like
+    :func:`_check_mla`."""
+    import math
+
+    import torch
+
+    if isinstance(softmax_scale, bool) or not isinstance(softmax_scale, (int, float)):
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE,
+                                  f"softmax_scale must be a number, got {type(softmax_scale).__name__}")
+    if not (math.isfinite(softmax_scale) and softmax_scale > 0):
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"softmax_scale must be finite and > 0, got {softmax_scale}")
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"q must be float16 or bfloat16, got {q.dtype}")
+    if indices.dtype != torch.int32:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"indices must be int32, got {indices.dtype}")
+    if q.dim() not in (3, 4):
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, "q must be [N,Hq,576] or [B,Sq,Hq,576]")
+    for name, t, rank in (("q", q, q.dim()), ("ckv", ckv, max(ckv.dim(), 2)), ("indices", indices, q.dim() - 1),
+                          ("out", out, q.dim())):
+        if t is not indices and t.dtype != q.dtype:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be {q.dtype}, got {t.dtype}")
+        if t.dim() != rank:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be {rank}-D beside a {q.dim()}-D q")
+        if not t.is_contiguous():
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be contiguous")
+    if q.shape[-1] != MLA_DQK or ckv.shape[-1] != MLA_DQK:
+        raise FlashAttentionError(FA_ERR_UNSUPPORTED_HEAD_DIM,
+                                  f"q and ckv must have a last dim of {MLA_DQK} ([c_kv 512 | k_pe 64])")
+    if tuple(out.shape) != (*q.shape[:-1], MLA_DV):
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"out must have q's shape with a last dim of {MLA_DV}")
+    if tuple(indices.shape[:-1]) != tuple(q.shape[:-2]):
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE,
+                                  f"indices {tuple(indices.shape)} must be one list per token of q {tuple(q.shape)}")
+    if q.numel() // MLA_DQK > 0x7fffffff:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, "tokens * Hq exceeds INT_MAX")
+    if ckv.numel() // MLA_DQK > 0x7fffffff:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, "the pool holds more rows than an int32 index reaches")
+    for name, t in (("q", q), ("ckv", ckv), ("out", out)):
+        if not t.is_cuda:
+            raise FlashAttentionError(FA_ERR_NULL_POINTER, f"{name} must be a device tensor")
+        if t.device != q.device:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} is on {t.device}, q on {q.device}: one device only")
+    if not indices.is_cuda or indices.device != q.device:
+        raise FlashAttentionError(FA_ERR_NULL_POINTER, f"indices must be a tensor on {q.device}")
+
+
+def flash_attention_mla_sparse(q, ckv, indices, *, softmax_scale, out=None, return_lse: bool = False,
+                               num_splits: int = 0, stream=None):
+    """MLA sparse attention (DeepSeek-V3.2's DSA; fa_mla_sparse_f16 / _bf16 of
+    include/fa_mi355x_mla_sparse.h): the weight-absorbed 576/512 attention of
+    :func:`flash_attention_mla_decode` where every query token attends only to
+    the latent rows its index list names, for decode and prefill alike.
+
+    q: [N, Hq, 576] with indices int32 [N, topk], or [B, Sq, Hq, 576] with
+    indices [B, Sq, topk] (FlashMLA's layouts); ckv: any contiguous tensor with
+    a last dim of 576, viewed as a flat pool [-1, 576] of rows [c_kv (512) |
+    k_pe (64)] -- row b * cap + j of a [B, cap, 576] cache, row page *
+    page_size + off of a [num_pages, page_size, 576] page pool, which may
+    exceed 4 GiB.  An entry outside [0, rows) (-1, ...) is a hole: nothing is
+    read for it and it carries no weight; a row listed twice counts twice.
+    Returns out with q's leading shape and a last dim of 512, or (out, lse)
+    with lse fp32 of q's leading shape (natural log) when return_lse; a token
+    with no valid entry gives out = 0 and lse = -inf.  softmax_scale is
+    required.  num_splits: 0 = the plan's choice (:func:`mla_decode_num_splits`
+    of (N, Hq, 1, topk)), > 0 forces that many pieces of each list.  Nothing is
+    copied or cast: a non-contiguous input, indices that are not int32, mixed
+    dtypes or devices raise.  Enqueued on ``stream`` (default: torch's current
+    stream); no sync, graph-capturable; a split launch takes its workspace from
+    the decode functions' per-(device, stream) buffer."""
+    import torch
+
+    if out is None:
+        out = torch.empty((*q.shape[:-1], MLA_DV), dtype=q.dtype, device=q.device)
+    _check_mla_sparse(q, ckv, indices, out, softmax_scale)
+    hq, topk = q.shape[-2], indices.shape[-1]
+    n = q.numel() // (hq * MLA_DQK) if hq else 0
+    rows = ckv.numel() // MLA_DQK
+    dev = q.device.index
+    st = _raw_stream(stream, dev)
+    lse = torch.empty(q.shape[:-1], dtype=torch.float32, device=q.device) if return_lse else None
+    ns = int(num_splits)
+    need = 0
+    if 0 < n <= 0x7fffffff and topk > 0 and rows > 0 and 0 <= ns <= 64:  # (otherwise the entry refuses or fills)
+        key = (dev, n, hq, 1, topk, ns)
+        need = _MLA_NEED.get(key)
+        if need is None or need:
+            with torch.cuda.device(dev):
+                if need is None:
+                    pieces = ns or _entry("fa_mla_decode_num_splits")(n, hq, 1, topk)
+                    need = _MLA_NEED[key] = _entry("fa_mla_decode_ws_bytes")(n, hq, 1, pieces)
+                ws = _workspace(need, dev, st) if need else None  # (a tensor: alive until the launch)
+    _launch("fa_mla_sparse" + ("_bf16" if q.dtype is torch.bfloat16 else "_f16"), dev, st,
+            (q.data_ptr(), ckv.data_ptr(), indices.data_ptr(), out.data_ptr(),
+             lse.data_ptr() if return_lse else None, n, hq, topk, rows, float(softmax_scale), ns,
+             ws.data_ptr() if need else None, need))
+    return (out, lse) if return_lse else out
 
 
 def _prefill_call(family, kv8, q, k, v, out, batch, seqlen_q, block_table, kv_lens, q_lens, causal,
