@@ -202,6 +202,15 @@ MLA_PREFILL_ENTRIES = {"fa_mla_prefill_varlen" + ty: (_I, _QKVO_LSE + _ATTN_DIMS
 # topk, num_rows; softmax_scale; num_splits, workspace, ws_bytes; the stream
 MLA_SPARSE_ENTRIES = {"fa_mla_sparse" + ty: (_I, [_P] * 5 + [_I] * 4 + [_F] + [_I, _P, _ULL] + _STREAM)
                       for ty in ("_f16", "_bf16")}
+# the MLA sparse indexer (index logits and top-k row selection),
+# include/fa_mi355x_mla_indexer.h: q, k, weights, ks, ke, logits; num_tokens,
+# heads, num_rows, max_len, logits_stride; the stream; the _k8 entries' k_scale
+MLA_INDEXER_ENTRIES = {"fa_mla_indexer_logits" + k8 + ty: (_I, [_P] * 6 + [_I] * 4 + [_LL] + _STREAM
+                                                           + ([_P] if k8 else []))
+                       for k8 in ("", "_k8") for ty in ("_f16", "_bf16")}
+# logits, ks, ke, indices; num_tokens, num_rows, max_len, logits_stride, topk; the stream
+MLA_INDEXER_ENTRIES["fa_mla_indexer_topk"] = (_I, [_P] * 4 + [_I] * 3 + [_LL, _I] + _STREAM)
+MLA_INDEXER_HEADS, MLA_INDEXER_DIM = 64, 128
 
 
 @dataclass(frozen=True)
@@ -236,7 +245,8 @@ def load_library() -> ctypes.CDLL:
             f"{LIB_PATH} not built (run `make -C {PKG_ROOT}` or __graft_entry__.build())",
         )
     lib = ctypes.CDLL(LIB_PATH)
-    for table in (C_ENTRIES, TREE_ENTRIES, MLA_ENTRIES, MLA_KV8_ENTRIES, MLA_PREFILL_ENTRIES, MLA_SPARSE_ENTRIES):
+    for table in (C_ENTRIES, TREE_ENTRIES, MLA_ENTRIES, MLA_KV8_ENTRIES, MLA_PREFILL_ENTRIES, MLA_SPARSE_ENTRIES,
+                  MLA_INDEXER_ENTRIES):
         for name, (restype, argtypes) in table.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
@@ -1232,6 +1242,142 @@ def flash_attention_mla_sparse(q, ckv, indices, *, softmax_scale, out=None, retu
              lse.data_ptr() if return_lse else None, n, hq, topk, rows, float(softmax_scale), ns,
              ws.data_ptr() if need else None, need))
     return (out, lse) if return_lse else out
+
+
+def _check_indexer_ranges(n, ks, ke, dev, where):
+    """ks and ke: contiguous int32 [n] tensors on device `dev` (None: the types and shapes only)."""
+    import torch
+
+    for name, t in (("ks", ks), ("ke", ke)):
+        if t.dtype != torch.int32:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: {name} must be int32, got {t.dtype}")
+        if tuple(t.shape) != (n,) or not t.is_contiguous():
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: {name} must be a contiguous [{n}] tensor")
+        if dev is not None and (not t.is_cuda or t.device != dev):
+            raise FlashAttentionError(FA_ERR_NULL_POINTER, f"{where}: {name} must be a tensor on {dev}")
+
+
+def _check_indexer_logits(logits, n, max_len, dev, where):
+    """logits: an fp32 [n, >= max_len] tensor on `dev` with unit column stride
+    and a row stride of at least its width; returns (max_len, row stride)."""
+    import torch
+
+    if logits.dtype != torch.float32:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: logits must be float32, got {logits.dtype}")
+    if logits.dim() != 2 or logits.shape[0] != n:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: logits must be [{n}, max_len]")
+    max_len = logits.shape[1] if max_len is None else int(max_len)
+    if not 0 <= max_len <= min(logits.shape[1], 0x7fffffff):
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE,
+                                  f"{where}: max_len {max_len} must lie in [0, {logits.shape[1]}], the logits' width")
+    if logits.shape[1] > 1 and logits.stride(1) != 1 or n > 1 and logits.stride(0) < logits.shape[1]:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: logits must have unit column stride and rows that "
+                                                    "do not overlap")
+    if not logits.is_cuda or logits.device != dev:
+        raise FlashAttentionError(FA_ERR_NULL_POINTER, f"{where}: logits must be a tensor on {dev}")
+    return max_len, (logits.stride(0) if n > 1 else max(logits.stride(0), logits.shape[1]))
+
+
+def flash_attention_mla_indexer_logits(q, k, weights, ks, ke, *, k_scale=None, max_len=None, out=None, stream=None):
+    """The index logits of the MLA sparse indexer (DeepSeek-V3.2's DSA;
+    fa_mla_indexer_logits[_k8]_{f16,bf16} of include/fa_mi355x_mla_indexer.h):
+
+        out[n, j - ks[n]] = k_scale[j] * sum_h weights[n, h] * relu(q[n, h] . k[j])     ks[n] <= j < ke[n]
+
+    q: [N, 64, 128] fp16 or bf16; k: any contiguous tensor with a last dim of
+    128, viewed as a flat pool [-1, 128] of index keys, of q's dtype, or with
+    ``k_scale`` (fp32, one per pool row) of torch.float8_e4m3fn or uint8;
+    weights: fp32 [N, 64]; ks, ke: int32 [N] on the device, clamped there.
+    out: an fp32 [N, >= max_len] tensor (its row stride may exceed its width)
+    or None, which allocates [N, max_len] (``max_len`` is then required;
+    otherwise it defaults to out's width).  Columns at or beyond a token's
+    length are not written.  Nothing is copied or cast: wrong dtypes, devices
+    or non-contiguous inputs raise.  Enqueued on ``stream`` (default: torch's
+    current stream); no sync, no workspace, graph-capturable."""
+    import torch
+
+    where = "mla_indexer_logits"
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: q must be float16 or bfloat16, got {q.dtype}")
+    if q.dim() != 3 or tuple(q.shape[1:]) != (MLA_INDEXER_HEADS, MLA_INDEXER_DIM):
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: q must be [N, {MLA_INDEXER_HEADS}, {MLA_INDEXER_DIM}]")
+    k8 = k_scale is not None
+    kinds = (torch.float8_e4m3fn, torch.uint8) if k8 else (q.dtype,)
+    if k.dtype not in kinds:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: k must be {' or '.join(map(str, kinds))}, got {k.dtype}")
+    if k.dim() < 2 or k.shape[-1] != MLA_INDEXER_DIM:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: k must have a last dim of {MLA_INDEXER_DIM}")
+    n, rows = q.shape[0], k.numel() // MLA_INDEXER_DIM
+    if n > 0x7fffffff or rows > 0x7fffffff:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: tokens and pool rows must fit an int32")
+    if weights.dtype != torch.float32 or tuple(weights.shape) != (n, MLA_INDEXER_HEADS):
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: weights must be float32 [{n}, {MLA_INDEXER_HEADS}]")
+    if k8 and (k_scale.dtype != torch.float32 or k_scale.numel() != rows):
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: k_scale must be float32 with one scale per pool row")
+    if out is None and max_len is None:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: max_len is required when out is not given")
+    tensors = [("q", q), ("k", k), ("weights", weights)] + ([("k_scale", k_scale)] if k8 else [])
+    for name, t in tensors:
+        if not t.is_contiguous():
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: {name} must be contiguous")
+    _check_indexer_ranges(n, ks, ke, None, where)
+    for name, t in tensors:
+        if not t.is_cuda or t.device != q.device:
+            raise FlashAttentionError(FA_ERR_NULL_POINTER, f"{where}: {name} must be a tensor on q's GPU")
+    _check_indexer_ranges(n, ks, ke, q.device, where)
+    if out is None:
+        if not 0 <= int(max_len) <= 0x7fffffff:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: max_len {max_len} must lie in [0, INT_MAX]")
+        out = torch.empty((n, int(max_len)), dtype=torch.float32, device=q.device)
+    max_len, stride = _check_indexer_logits(out, n, max_len, q.device, where)
+    _launch("fa_mla_indexer_logits" + ("_k8" if k8 else "") + ("_bf16" if q.dtype is torch.bfloat16 else "_f16"),
+            q.device.index, stream,
+            (q.data_ptr(), k.data_ptr(), weights.data_ptr(), ks.data_ptr(), ke.data_ptr(), out.data_ptr(), n,
+             MLA_INDEXER_HEADS, rows, max_len, stride), (k_scale.data_ptr(),) if k8 else ())
+    return out
+
+
+def flash_attention_mla_indexer_topk(logits, ks, ke, topk, *, num_rows, max_len=None, out=None, stream=None):
+    """The selection of the MLA sparse indexer (fa_mla_indexer_topk of
+    include/fa_mi355x_mla_indexer.h): int32 [N, topk], per token the flat pool
+    rows ks[n] + c of its min(topk, length) largest logits (by IEEE value; ties
+    at the threshold go to the lowest columns), in ascending row order, padded
+    with -1 -- the lists :func:`flash_attention_mla_sparse` reads.  logits:
+    fp32 [N, >= max_len] (``max_len`` defaults to its width), read in columns
+    [0, ke - ks) after the clamp of :func:`flash_attention_mla_indexer_logits`
+    with the same ``num_rows`` (the key pool's rows).  out: a contiguous int32
+    [N, topk] tensor or None.  No sync, no workspace, graph-capturable."""
+    import torch
+
+    where = "mla_indexer_topk"
+    if isinstance(topk, bool) or not isinstance(topk, int) or not 0 <= topk <= 0x7fffffff:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: topk must be an int in [0, INT_MAX], got {topk!r}")
+    if isinstance(num_rows, bool) or not isinstance(num_rows, int) or not 0 <= num_rows <= 0x7fffffff:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: num_rows must be an int in [0, INT_MAX], got {num_rows!r}")
+    if logits.dim() != 2 or logits.shape[0] > 0x7fffffff:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: logits must be [N, max_len]")
+    n = logits.shape[0]
+    max_len, stride = _check_indexer_logits(logits, n, max_len, logits.device, where)
+    _check_indexer_ranges(n, ks, ke, logits.device, where)
+    if out is None:
+        out = torch.empty((n, topk), dtype=torch.int32, device=logits.device)
+    if out.dtype != torch.int32 or tuple(out.shape) != (n, topk) or not out.is_contiguous():
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: out must be a contiguous int32 [{n}, {topk}] tensor")
+    if not out.is_cuda or out.device != logits.device:
+        raise FlashAttentionError(FA_ERR_NULL_POINTER, f"{where}: out must be a tensor on {logits.device}")
+    _launch("fa_mla_indexer_topk", logits.device.index, stream,
+            (logits.data_ptr(), ks.data_ptr(), ke.data_ptr(), out.data_ptr(), n, num_rows, max_len, stride, topk))
+    return out
+
+
+def flash_attention_mla_indexer(q, k, weights, ks, ke, *, topk, max_len, k_scale=None, stream=None):
+    """The MLA sparse indexer: :func:`flash_attention_mla_indexer_logits` into a
+    fresh fp32 [N, max_len] buffer, then :func:`flash_attention_mla_indexer_topk`
+    over it -- exactly one call after the other.  Returns int32 [N, topk]."""
+    logits = flash_attention_mla_indexer_logits(q, k, weights, ks, ke, k_scale=k_scale, max_len=max_len,
+                                                stream=stream)
+    return flash_attention_mla_indexer_topk(logits, ks, ke, topk, num_rows=k.numel() // MLA_INDEXER_DIM,
+                                            max_len=max_len, stream=stream)
 
 
 def _prefill_call(family, kv8, q, k, v, out, batch, seqlen_q, block_table, kv_lens, q_lens, causal,
