@@ -211,6 +211,11 @@ MLA_INDEXER_ENTRIES = {"fa_mla_indexer_logits" + k8 + ty: (_I, [_P] * 6 + [_I] *
 # logits, ks, ke, indices; num_tokens, num_rows, max_len, logits_stride, topk; the stream
 MLA_INDEXER_ENTRIES["fa_mla_indexer_topk"] = (_I, [_P] * 4 + [_I] * 3 + [_LL, _I] + _STREAM)
 MLA_INDEXER_HEADS, MLA_INDEXER_DIM = 64, 128
+# MLA sparse attention over an FP8 (E4M3) latent pool,
+# include/fa_mi355x_mla_sparse_kv8.h: the sparse entries' list with `ckv_scale`
+# after `indices`
+MLA_SPARSE_KV8_ENTRIES = {"fa_mla_sparse_kv8" + ty: (_I, [_P] * 6 + [_I] * 4 + [_F] + [_I, _P, _ULL] + _STREAM)
+                          for ty in ("_f16", "_bf16")}
 
 
 @dataclass(frozen=True)
@@ -246,7 +251,7 @@ def load_library() -> ctypes.CDLL:
         )
     lib = ctypes.CDLL(LIB_PATH)
     for table in (C_ENTRIES, TREE_ENTRIES, MLA_ENTRIES, MLA_KV8_ENTRIES, MLA_PREFILL_ENTRIES, MLA_SPARSE_ENTRIES,
-                  MLA_INDEXER_ENTRIES):
+                  MLA_INDEXER_ENTRIES, MLA_SPARSE_KV8_ENTRIES):
         for name, (restype, argtypes) in table.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
@@ -1140,14 +1145,16 @@ def flash_attention_mla_decode_paged_kv8(q, ckv_pages, block_table, kv_lens=None
                      num_splits, stream, True, ckv_scale)
 
 
-def _check_mla_sparse(q, ckv, indices, out, softmax_scale):
+def _check_mla_sparse(q, ckv, indices, out, softmax_scale, kv8=False, ckv_scale=None):
     """Raise FlashAttentionError unless q is a contiguous [N,Hq,576] or
     [B,Sq,Hq,576] tensor of a 16-bit dtype, indices a contiguous int32 tensor of
     q's leading shape (all but Hq and 576) and a last dim of topk, ckv a
     contiguous tensor of q's dtype with at least two dims and a last dim of 576,
     out a contiguous tensor of q's dtype and shape but for a last dim of 512,
     all on q's device, and softmax_scale a finite number > 0.  Ordered like
-    :func:`_check_mla`."""
+    :func:`_check_mla`.  kv8: the pool holds E4M3 bytes (torch.float8_e4m3fn or
+    torch.uint8) at a 16-byte aligned address and ckv_scale (if given) is a
+    contiguous float32 tensor of one element on q's device."""
     import math
 
     import torch
@@ -1165,7 +1172,11 @@ def _check_mla_sparse(q, ckv, indices, out, softmax_scale):
         raise FlashAttentionError(FA_ERR_BAD_SHAPE, "q must be [N,Hq,576] or [B,Sq,Hq,576]")
     for name, t, rank in (("q", q, q.dim()), ("ckv", ckv, max(ckv.dim(), 2)), ("indices", indices, q.dim() - 1),
                           ("out", out, q.dim())):
-        if t is not indices and t.dtype != q.dtype:
+        if kv8 and t is ckv:
+            if t.dtype not in (torch.float8_e4m3fn, torch.uint8):
+                raise FlashAttentionError(FA_ERR_BAD_SHAPE,
+                                          f"{name} must be torch.float8_e4m3fn or torch.uint8, got {t.dtype}")
+        elif t is not indices and t.dtype != q.dtype:
             raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be {q.dtype}, got {t.dtype}")
         if t.dim() != rank:
             raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{name} must be {rank}-D beside a {q.dim()}-D q")
@@ -1183,6 +1194,13 @@ def _check_mla_sparse(q, ckv, indices, out, softmax_scale):
         raise FlashAttentionError(FA_ERR_BAD_SHAPE, "tokens * Hq exceeds INT_MAX")
     if ckv.numel() // MLA_DQK > 0x7fffffff:
         raise FlashAttentionError(FA_ERR_BAD_SHAPE, "the pool holds more rows than an int32 index reaches")
+    if kv8 and ckv.data_ptr() % 16 != 0:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, "ckv must start at a multiple of 16 bytes")
+    if ckv_scale is not None:
+        if ckv_scale.dtype != torch.float32 or ckv_scale.numel() != 1 or not ckv_scale.is_contiguous():
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, "ckv_scale must be a contiguous float32 tensor of one element")
+        if not ckv_scale.is_cuda or ckv_scale.device != q.device:
+            raise FlashAttentionError(FA_ERR_NULL_POINTER, f"ckv_scale must be a tensor on {q.device}")
     for name, t in (("q", q), ("ckv", ckv), ("out", out)):
         if not t.is_cuda:
             raise FlashAttentionError(FA_ERR_NULL_POINTER, f"{name} must be a device tensor")
@@ -1215,11 +1233,19 @@ def flash_attention_mla_sparse(q, ckv, indices, *, softmax_scale, out=None, retu
     dtypes or devices raise.  Enqueued on ``stream`` (default: torch's current
     stream); no sync, graph-capturable; a split launch takes its workspace from
     the decode functions' per-(device, stream) buffer."""
+    return _mla_sparse_call(q, ckv, indices, softmax_scale, out, return_lse, num_splits, stream)
+
+
+def _mla_sparse_call(q, ckv, indices, softmax_scale, out, return_lse, num_splits, stream, kv8=False,
+                     ckv_scale=None):
+    """The two MLA sparse functions: out, the checks, the optional LSE, the
+    split plan and its workspace and the fa_mla_sparse* entry; kv8: the E4M3
+    pool's entry, with ckv_scale after indices."""
     import torch
 
     if out is None:
         out = torch.empty((*q.shape[:-1], MLA_DV), dtype=q.dtype, device=q.device)
-    _check_mla_sparse(q, ckv, indices, out, softmax_scale)
+    _check_mla_sparse(q, ckv, indices, out, softmax_scale, kv8, ckv_scale)
     hq, topk = q.shape[-2], indices.shape[-1]
     n = q.numel() // (hq * MLA_DQK) if hq else 0
     rows = ckv.numel() // MLA_DQK
@@ -1237,11 +1263,30 @@ def flash_attention_mla_sparse(q, ckv, indices, *, softmax_scale, out=None, retu
                     pieces = ns or _entry("fa_mla_decode_num_splits")(n, hq, 1, topk)
                     need = _MLA_NEED[key] = _entry("fa_mla_decode_ws_bytes")(n, hq, 1, pieces)
                 ws = _workspace(need, dev, st) if need else None  # (a tensor: alive until the launch)
-    _launch("fa_mla_sparse" + ("_bf16" if q.dtype is torch.bfloat16 else "_f16"), dev, st,
-            (q.data_ptr(), ckv.data_ptr(), indices.data_ptr(), out.data_ptr(),
+    _launch("fa_mla_sparse" + ("_kv8" if kv8 else "") + ("_bf16" if q.dtype is torch.bfloat16 else "_f16"), dev, st,
+            (q.data_ptr(), ckv.data_ptr(), indices.data_ptr(),
+             *((ckv_scale.data_ptr() if ckv_scale is not None else None,) if kv8 else ()), out.data_ptr(),
              lse.data_ptr() if return_lse else None, n, hq, topk, rows, float(softmax_scale), ns,
              ws.data_ptr() if need else None, need))
     return (out, lse) if return_lse else out
+
+
+def flash_attention_mla_sparse_kv8(q, ckv8, indices, softmax_scale, ckv_scale=None, return_lse: bool = False,
+                                   num_splits: int = 0, *, out=None, stream=None):
+    """:func:`flash_attention_mla_sparse` over an FP8 latent pool
+    (fa_mla_sparse_kv8_f16 / _bf16 of include/fa_mi355x_mla_sparse_kv8.h): ckv8
+    is any contiguous tensor of OCP E4M3 bytes (torch.float8_e4m3fn or
+    torch.uint8) with a last dim of 576, starting at a multiple of 16 bytes,
+    viewed as a flat pool [-1, 576] and read as ckv_scale * ckv8; ckv_scale: a
+    float32 device tensor of one element (None: 1.0), read on the device, so a
+    captured graph follows a rewritten scale.  q and out stay 16-bit and
+    nothing is dequantised in memory: the scale enters the score scale (and so
+    lse) and the final normalisation.  A writer stores
+    ``x.div(s).clamp(-448, 448).to(torch.float8_e4m3fn)``: one scale per pool
+    and all 576 dims as bytes, not FlashMLA's 656-byte row.  Everything else
+    is the 16-bit function's: the 3-D and 4-D forms, holes, lse, num_splits,
+    the workspace; nothing is copied or cast."""
+    return _mla_sparse_call(q, ckv8, indices, softmax_scale, out, return_lse, num_splits, stream, True, ckv_scale)
 
 
 def _check_indexer_ranges(n, ks, ke, dev, where):

@@ -21,6 +21,13 @@ before it fetched them; the prefill chunk's 38 MB of rows stay cache-resident
 by the nature of the workload.
 
     python3 tools/mla_sparse_bench.py [--out profiles/mla_sparse_bench.jsonl] [--quick]
+
+--kv8: fa_mi355x.flash_attention_mla_sparse_kv8 over the same pool as E4M3 bytes
+(576 B per row), five legs alternated round by round: the kernel, the 16-bit
+sparse kernel on the dequantised pool, the kernel again (aa), index_select of
+the bytes into a scratch cache + flash_attention_mla_decode_kv8, and that
+decode alone on pre-gathered rows (the floor).  fp16; decode B = 64, decode B =
+1 and the prefill chunk; rows to profiles/mla_sparse_kv8_bench.jsonl.
 """
 import argparse
 import json
@@ -81,14 +88,79 @@ def run(name, n, per_seq, hq, dtype, pool, rounds=7):
                 max_abs_diff_vs_gather_decode=diff, nonfinite=int((~torch.isfinite(out)).sum()))
 
 
+def run_kv8(name, n, per_seq, hq, pool8, pool16, sc, rounds=7):
+    dev, dtype = "cuda", pool16.dtype
+    scale = 192 ** -0.5
+    gathered = n * TOPK * DQK
+    copies = max(1, -(-(512 << 20) // gathered))
+    gen = torch.Generator(device=dev).manual_seed(n * 131 + hq)
+    q = (torch.rand((n, hq, DQK), generator=gen, device=dev) * 2 - 1).to(dtype)
+    lists = [draw_lists(n, per_seq, gen) for _ in range(copies)]
+    scratch = torch.empty((n, TOPK, DQK), dtype=torch.uint8, device=dev)
+    gather = lambda idx, out: torch.index_select(pool8, 0, idx.view(-1), out=out.view(-1, DQK))
+    contig = [scratch] if copies == 1 else [torch.empty_like(scratch) for _ in range(copies)]
+    for idx, c in zip(lists, contig):
+        gather(idx, c)
+    q4 = q.view(n, hq, 1, DQK)
+    kw = dict(softmax_scale=scale, ckv_scale=sc)
+    sparse8 = lambda i: fa_mi355x.flash_attention_mla_sparse_kv8(q, pool8, lists[i % copies], scale, sc)
+
+    def gather_decode(i):
+        gather(lists[i % copies], scratch)
+        return fa_mi355x.flash_attention_mla_decode_kv8(q4, scratch, causal=False, **kw)
+
+    fns = [sparse8, lambda i: fa_mi355x.flash_attention_mla_sparse(q, pool16, lists[i % copies], softmax_scale=scale),
+           sparse8, gather_decode,
+           lambda i: fa_mi355x.flash_attention_mla_decode_kv8(q4, contig[i % copies], causal=False, **kw)]
+    out = fns[0](0)
+    diff = float((out.float() - fns[3](0).view(n, hq, DV).float()).abs().max())
+    diff16 = float((out.float() - fns[1](0).float()).abs().max())
+    iters = 20 if n <= 128 else 5
+    t_s, t_16, t_s2, t_a, t_b = time_pair(fns, iters, rounds)
+    return dict(name=name, dtype=str(dtype).split(".")[-1], tokens=n, heads_q=hq, topk=TOPK,
+                regime="narrow" if hq <= 16 else "wide", num_splits=fa_mi355x.mla_decode_num_splits(n, hq, 1, TOPK),
+                list_sets=copies, sparse_kv8_us=round(t_s, 2), aa=round(t_s2 / t_s, 4),
+                sparse_16bit_us=round(t_16, 2), kv8_over_16bit=round(t_s / t_16, 3),
+                gather_decode_kv8_us=round(t_a, 2), gather_decode_over_sparse=round(t_a / t_s, 3),
+                contig_kv8_us=round(t_b, 2), sparse_over_contig=round(t_s / t_b, 3),
+                share_of_copy_rate=round(gathered / (t_s * 1e-6) / COPY_RATE, 4),
+                tflops=round(2.0 * n * hq * TOPK * (DQK + DV) / (t_s * 1e-6) / 1e12, 2),
+                max_abs_diff_vs_gather_decode=diff, max_abs_diff_vs_16bit=diff16,
+                nonfinite=int((~torch.isfinite(out)).sum()))
+
+
+def main_kv8(out):
+    """The --kv8 rows: E4M3 codes of magnitude <= 1 under the scale 0.75, and their exact fp16 image."""
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    shape = (BATCH * SEQ, DQK)
+    pool8 = (torch.randint(0, 0x39, shape, generator=gen, device="cuda", dtype=torch.uint8)
+             | (torch.randint(0, 2, shape, generator=gen, device="cuda", dtype=torch.uint8) << 7))
+    sc = torch.tensor([0.75], dtype=torch.float32, device="cuda")
+    pool16 = torch.empty(shape, dtype=torch.float16, device="cuda")
+    for i in range(0, shape[0], 1 << 18):  # in slabs: no fp32 image of the whole pool
+        pool16[i:i + (1 << 18)] = (pool8[i:i + (1 << 18)].view(torch.float8_e4m3fn).float() * 0.75).half()
+    with open(out, "w") as f:
+        for name, n, per_seq in (("decode B=64 Sq=1", BATCH, 1), ("decode B=1 Sq=1", 1, 1),
+                                 ("prefill chunk N=4096", 4096, 4096)):
+            for hq in (128, 16):
+                rec = run_kv8(name, n, per_seq, hq, pool8, pool16, sc)
+                print(json.dumps(rec), flush=True)
+                f.write(json.dumps(rec) + "\n")
+                torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="default profiles/mla_sparse_bench.jsonl")
     ap.add_argument("--quick", action="store_true", help="decode B = 64 Sq = 1 only, fp16")
+    ap.add_argument("--kv8", action="store_true", help="the FP8 pool's kernel and its four comparison legs")
     args = ap.parse_args()
     root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..")
-    out = args.out or os.path.join(root, "profiles", "mla_sparse_bench.jsonl")
+    out = args.out or os.path.join(root, "profiles", "mla_sparse_kv8_bench.jsonl" if args.kv8
+                                   else "mla_sparse_bench.jsonl")
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    if args.kv8:
+        return main_kv8(out)
     cases = [("decode B=64 Sq=1", BATCH, 1), ("decode B=64 Sq=2", 2 * BATCH, 2), ("decode B=1 Sq=1", 1, 1),
              ("prefill chunk N=4096", 4096, 4096)]
     with open(out, "w") as f:
