@@ -217,6 +217,21 @@ MLA_INDEXER_HEADS, MLA_INDEXER_DIM = 64, 128
 MLA_SPARSE_KV8_ENTRIES = {"fa_mla_sparse_kv8" + ty: (_I, [_P] * 6 + [_I] * 4 + [_F] + [_I, _P, _ULL] + _STREAM)
                           for ty in ("_f16", "_bf16")}
 
+# the writers of the MLA caches, include/fa_mi355x_mla_append.h.  The latent
+# append: ckv_new, kpe_new, ckv_cache; their two token strides; batch,
+# total_new, seqlen_new; the cache group; cu_seqlens, kv_lens; q_pe, q_out,
+# heads_q; q's four strides; cos, sin, rope_len, interleaved; the stream; the
+# _kv8 entries' ckv_scale
+MLA_APPEND_ENTRIES = {"fa_mla_append" + c + s + ty: (_I, [_P] * 3 + [_LL] * 2 + [_I] * 3 + _MLA_CACHE[c] + [_P] * 2
+                                                     + [_P, _P, _I] + [_LL] * 4 + [_P, _P, _I, _I] + _STREAM
+                                                     + ([_P] if s else []))
+                      for c in ("", "_paged") for s in ("", "_kv8") for ty in ("_f16", "_bf16")}
+# the indexer key pool's writer: k_new, k_pool, k_scale; k_stride; batch,
+# total_new, seqlen_new; the cache group; cu_seqlens, kv_lens; scale_pow2; the stream
+MLA_APPEND_ENTRIES.update({"fa_mla_indexer_append_k8" + c + ty: (_I, [_P] * 3 + [_LL] + [_I] * 3 + _MLA_CACHE[c]
+                                                                 + [_P] * 2 + [_I] + _STREAM)
+                           for c in ("", "_paged") for ty in ("_f16", "_bf16")})
+
 
 @dataclass(frozen=True)
 class TileConfig:
@@ -251,7 +266,7 @@ def load_library() -> ctypes.CDLL:
         )
     lib = ctypes.CDLL(LIB_PATH)
     for table in (C_ENTRIES, TREE_ENTRIES, MLA_ENTRIES, MLA_KV8_ENTRIES, MLA_PREFILL_ENTRIES, MLA_SPARSE_ENTRIES,
-                  MLA_INDEXER_ENTRIES, MLA_SPARSE_KV8_ENTRIES):
+                  MLA_INDEXER_ENTRIES, MLA_SPARSE_KV8_ENTRIES, MLA_APPEND_ENTRIES):
         for name, (restype, argtypes) in table.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
@@ -1423,6 +1438,215 @@ def flash_attention_mla_indexer(q, k, weights, ks, ke, *, topk, max_len, k_scale
                                                 stream=stream)
     return flash_attention_mla_indexer_topk(logits, ks, ke, topk, num_rows=k.numel() // MLA_INDEXER_DIM,
                                             max_len=max_len, stream=stream)
+
+
+def _mla_append_seqs(where, t, block_table, cache, kv_lens, cu_seqlens):
+    """The sequences of the MLA cache writers: kv_lens int32 [B] (required),
+    cu_seqlens int32 [B + 1] or None (uniform: B divides the T tokens), the
+    block table int32 [B, max_pages]; returns (batch, seqlen_new, the cache
+    group of the C entries)."""
+    import torch
+
+    if kv_lens is None or kv_lens.dtype != torch.int32 or kv_lens.dim() != 1 or not kv_lens.is_contiguous():
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: kv_lens must be a contiguous int32 [B] tensor")
+    b = kv_lens.shape[0]
+    if cache.dim() != 3 or not cache.is_contiguous():
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: the cache must be a contiguous 3-D tensor")
+    if block_table is None:
+        if cache.shape[0] != b:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: the cache holds {cache.shape[0]} sequences, "
+                                                        f"kv_lens {b}")
+        group = (cache.shape[1],)
+    else:
+        _check_table_type(block_table)
+        if block_table.dim() != 2 or block_table.shape[0] != b or not block_table.is_contiguous():
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: block_table must be a contiguous [{b}, "
+                                                        "max_pages_per_seq] tensor")
+        if cache.shape[0] == 0 or cache.shape[1] == 0 or cache.shape[1] % 64 != 0:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: the pool must hold pages of a positive multiple "
+                                                        "of 64 rows")
+        group = (cache.shape[0], cache.shape[1], block_table.data_ptr(), block_table.shape[1])
+    if cu_seqlens is None:
+        if b and t % b != 0:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: without cu_seqlens the {t} tokens must be "
+                                                        f"{b} sequences of one length")
+        sn = t // b if b else 0
+    else:
+        if cu_seqlens.dtype != torch.int32 or tuple(cu_seqlens.shape) != (b + 1,) or not cu_seqlens.is_contiguous():
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: cu_seqlens must be a contiguous int32 [{b + 1}] "
+                                                        "tensor")
+        sn = 0
+    return b, sn, group
+
+
+def _mla_on_device(where, first, **tensors):
+    """Every tensor given (None: absent) lives on the GPU of the first: checked last, after types and shapes."""
+    name0, x0 = first
+    if not x0.is_cuda:
+        raise FlashAttentionError(FA_ERR_NULL_POINTER, f"{where}: {name0} must be a device tensor")
+    for name, x in tensors.items():
+        if x is not None and (not x.is_cuda or x.device != x0.device):
+            raise FlashAttentionError(FA_ERR_NULL_POINTER, f"{where}: {name} must be a tensor on {x0.device}")
+
+
+def _mla_rows(where, name, x, dtype, shape):
+    """x: a view of `shape` (None: any size there) and `dtype` with a
+    unit inner stride, outer strides that are multiples of 8 elements and a
+    16-byte aligned start -- a slice, read or written in place; never copied."""
+    if x.dtype != dtype:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: {name} must be {dtype}, got {x.dtype}")
+    if x.dim() != len(shape) or any(s is not None and s != d for s, d in zip(shape, x.shape)):
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: {name} must be {list(shape)}, got {list(x.shape)}")
+    inner = x.shape[-1]
+    if x.stride(-1) != 1 or any(st % 8 != 0 or st < inner for st, d in zip(x.stride()[:-1], x.shape[:-1]) if d > 1):
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: {name} must be a slice with unit inner stride and "
+                                                    "outer strides in multiples of 8 elements (nothing is copied)")
+    if x.data_ptr() % 16 != 0:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: {name} must start at a multiple of 16 bytes")
+
+
+def _mla_stride(x, dim):
+    """x's stride over `dim`, or its row width where the extent is 1 (any stride serves)."""
+    return x.stride(dim) if x.shape[dim] > 1 else max(x.stride(dim), x.shape[-1])
+
+
+def _mla_append(where, ckv_new, kpe_new, cache, block_table, kv_lens, cu_seqlens, q_pe, q_out, cos, sin,
+                interleaved, ckv_scale, stream):
+    import torch
+
+    dt, dev = ckv_new.dtype, ckv_new.device
+    if dt not in (torch.float16, torch.bfloat16):
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: ckv_new must be float16 or bfloat16, got {dt}")
+    kv8 = cache.dtype in (torch.float8_e4m3fn, torch.uint8)
+    if not kv8 and cache.dtype != dt:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: the cache must be {dt}, torch.float8_e4m3fn or "
+                                                    f"torch.uint8, got {cache.dtype}")
+    if ckv_scale is not None:
+        if not kv8:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: ckv_scale goes with an FP8 cache")
+        if ckv_scale.dtype != torch.float32 or ckv_scale.numel() != 1 or not ckv_scale.is_contiguous():
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: ckv_scale must be a contiguous float32 tensor of "
+                                                        "one element")
+    if cache.dim() != 3 or cache.shape[2] != MLA_DQK:
+        raise FlashAttentionError(FA_ERR_UNSUPPORTED_HEAD_DIM, f"{where}: the cache must have rows of {MLA_DQK}")
+    t = ckv_new.shape[0] if ckv_new.dim() == 2 else -1
+    _mla_rows(where, "ckv_new", ckv_new, dt, (None, MLA_DV))
+    _mla_rows(where, "kpe_new", kpe_new, dt, (t, MLA_DQK - MLA_DV))
+    b, sn, group = _mla_append_seqs(where, t, block_table, cache, kv_lens, cu_seqlens)
+    if (cos is None) != (sin is None) or (q_pe is None) != (q_out is None):
+        raise FlashAttentionError(FA_ERR_NULL_POINTER, f"{where}: cos and sin, q_pe and q_out come in pairs")
+    rope_len = 0
+    if cos is not None:
+        for name, x in (("cos", cos), ("sin", sin)):
+            if (x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != 32 or x.shape != cos.shape
+                    or not x.is_contiguous() or x.data_ptr() % 16 != 0):
+                raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: {name} must be a contiguous float32 "
+                                                            "[rope_len, 32] table at a multiple of 16 bytes")
+        rope_len = cos.shape[0]
+        if not 1 <= rope_len <= 0x7fffffff:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: the tables must hold at least one row")
+    hq, qargs = 0, (None, None, 0, 0, 0, 0, 0)
+    if q_pe is not None:
+        if cos is None:
+            raise FlashAttentionError(FA_ERR_NULL_POINTER, f"{where}: q_pe needs the cos and sin tables")
+        if q_pe.dim() != 3:
+            raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: q_pe must be [T, Hq, 64]")
+        hq = q_pe.shape[1]
+        _mla_rows(where, "q_pe", q_pe, dt, (t, None, MLA_DQK - MLA_DV))
+        if q_out.dim() == 4:  # the decode layout [B, Hq, Sq, 576]: at Sq = 1 the memory of [B, Hq, 576]
+            if q_out.shape[2] != 1:
+                raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: q_out in the decode layout [B, Hq, Sq, 576] "
+                                                            "is written at Sq = 1 only")
+            q_out = q_out[:, :, 0]
+        _mla_rows(where, "q_out", q_out, dt, (t, hq, MLA_DQK))
+        qargs = (q_pe.data_ptr(), q_out.data_ptr(), hq, _mla_stride(q_pe, 0), _mla_stride(q_pe, 1),
+                 _mla_stride(q_out, 0), _mla_stride(q_out, 1))
+    _mla_on_device(where, ("ckv_new", ckv_new), kpe_new=kpe_new, cache=cache, kv_lens=kv_lens, cu_seqlens=cu_seqlens,
+                   block_table=block_table, q_pe=q_pe, q_out=q_out, cos=cos, sin=sin, ckv_scale=ckv_scale)
+    _launch("fa_mla_append" + ("_paged" if block_table is not None else "") + ("_kv8" if kv8 else "")
+            + ("_bf16" if dt is torch.bfloat16 else "_f16"), dev.index, stream,
+            (ckv_new.data_ptr(), kpe_new.data_ptr(), cache.data_ptr(), _mla_stride(ckv_new, 0),
+             _mla_stride(kpe_new, 0), b, t, sn, *group, cu_seqlens.data_ptr() if cu_seqlens is not None else None,
+             kv_lens.data_ptr(), *qargs, cos.data_ptr() if cos is not None else None,
+             sin.data_ptr() if sin is not None else None, rope_len, int(bool(interleaved))),
+            ((ckv_scale.data_ptr() if ckv_scale is not None else None,) if kv8 else ()))
+
+
+def flash_attention_mla_append(ckv_new, kpe_new, ckv_cache, kv_lens, cu_seqlens=None, q_pe=None, q_out=None,
+                               cos=None, sin=None, interleaved: bool = False, ckv_scale=None, *, stream=None):
+    """The MLA latent-cache append with fused RoPE (fa_mla_append[_kv8]_{f16,bf16}
+    of include/fa_mi355x_mla_append.h): one launch writes, for every new token,
+    row pos = kv_lens[b] - n_b + t of ckv_cache [B, cap, 576] with [ckv_new row
+    | rope(kpe_new row)], and rope(q_pe) of every head into q_out[..., 512:576].
+
+    ckv_new: [T, 512], kpe_new: [T, 64], q_pe: [T, Hq, 64] -- token-major views
+    of one 16-bit dtype, read in place: slices (kv_a[:, 512:], q[..., 128:]) with
+    unit inner stride; anything else raises, nothing is copied.  q_out: a view
+    [T, Hq, 576] (or the decode layout [B, Hq, 1, 576]) whose dims [0, 512) the
+    caller fills with q_nope @ W_UK; only [512, 576) is written; q_pe may be
+    q_out[..., 512:] itself.  q_pe and q_out None: append only.  cos, sin:
+    float32 [rope_len, 32]; both None (append only): k_pe is a bit copy.
+    interleaved: GPT-J pairs instead of NeoX.  cu_seqlens: int32 [B + 1], or
+    None for B sequences of T / B tokens; kv_lens: int32 [B], the lengths after
+    the append.  The cache's dtype chooses the form: the sources' dtype, or
+    torch.float8_e4m3fn / torch.uint8 with ckv_scale (a float32 device tensor of
+    one element, None: 1.0), stored as E4M3(clamp(y / ckv_scale, +-448)) by the
+    reciprocal contract.  Rows that do not exist (pos outside the capacity or
+    the tables) are dropped.  Enqueued on ``stream`` (default: torch's current
+    stream); no sync, no workspace, graph-capturable."""
+    _mla_append("mla_append", ckv_new, kpe_new, ckv_cache, None, kv_lens, cu_seqlens, q_pe, q_out, cos, sin,
+                interleaved, ckv_scale, stream)
+
+
+def flash_attention_mla_append_paged(ckv_new, kpe_new, ckv_pages, block_table, kv_lens, cu_seqlens=None, q_pe=None,
+                                     q_out=None, cos=None, sin=None, interleaved: bool = False, ckv_scale=None, *,
+                                     stream=None):
+    """:func:`flash_attention_mla_append` into a paged latent cache
+    (fa_mla_append_paged[_kv8]_{f16,bf16}): ckv_pages is the pool [num_pages,
+    page_size, 576] (page_size % 64 == 0) and block_table int32 [B,
+    max_pages_per_seq]; a row whose page id lies outside the pool is dropped."""
+    if block_table is None:
+        raise FlashAttentionError(FA_ERR_NULL_POINTER, "block_table must be a tensor")
+    _mla_append("mla_append_paged", ckv_new, kpe_new, ckv_pages, block_table, kv_lens, cu_seqlens, q_pe, q_out, cos,
+                sin, interleaved, ckv_scale, stream)
+
+
+def flash_attention_mla_indexer_append(k_new, k_pool, kv_lens, k_scale, cu_seqlens=None, block_table=None,
+                                       scale_pow2: bool = False, *, stream=None):
+    """The writer of the indexer's FP8 key pool
+    (fa_mla_indexer_append_k8[_paged]_{f16,bf16}): per new token, the row of
+    k_pool (E4M3 bytes, torch.float8_e4m3fn or uint8, [B, cap, 128] or with
+    ``block_table`` [num_pages, page_size, 128]) that the latent append
+    addresses receives k_new's row quantised by DeepSeek-V3.2's act_quant --
+    s = max(amax, 1e-4) / 448, rounded up to a power of two when ``scale_pow2``
+    -- and ``k_scale`` (float32, one per pool row, an output) its s.  k_new:
+    [T, 128] fp16 or bf16, a token-major view with unit inner stride.  The
+    sequences are :func:`flash_attention_mla_append`'s.  The key's RoPE and
+    Hadamard transform stay the caller's.  No sync, graph-capturable."""
+    import torch
+
+    where = "mla_indexer_append"
+    dt, dev = k_new.dtype, k_new.device
+    if dt not in (torch.float16, torch.bfloat16):
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: k_new must be float16 or bfloat16, got {dt}")
+    if k_pool.dtype not in (torch.float8_e4m3fn, torch.uint8):
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: k_pool must be torch.float8_e4m3fn or torch.uint8, "
+                                                    f"got {k_pool.dtype}")
+    if k_pool.dim() != 3 or k_pool.shape[2] != MLA_INDEXER_DIM:
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: k_pool must have rows of {MLA_INDEXER_DIM}")
+    _mla_rows(where, "k_new", k_new, dt, (None, MLA_INDEXER_DIM))
+    b, sn, group = _mla_append_seqs(where, k_new.shape[0], block_table, k_pool, kv_lens, cu_seqlens)
+    if (k_scale is None or k_scale.dtype != torch.float32 or k_scale.numel() != k_pool.numel() // MLA_INDEXER_DIM
+            or not k_scale.is_contiguous()):
+        raise FlashAttentionError(FA_ERR_BAD_SHAPE, f"{where}: k_scale must be a contiguous float32 tensor with one "
+                                                    "scale per pool row")
+    _mla_on_device(where, ("k_new", k_new), k_pool=k_pool, k_scale=k_scale, kv_lens=kv_lens, cu_seqlens=cu_seqlens,
+                   block_table=block_table)
+    _launch("fa_mla_indexer_append_k8" + ("_paged" if block_table is not None else "")
+            + ("_bf16" if dt is torch.bfloat16 else "_f16"), dev.index, stream,
+            (k_new.data_ptr(), k_pool.data_ptr(), k_scale.data_ptr(), _mla_stride(k_new, 0), b, k_new.shape[0], sn,
+             *group, cu_seqlens.data_ptr() if cu_seqlens is not None else None, kv_lens.data_ptr(),
+             int(bool(scale_pow2))))
 
 
 def _prefill_call(family, kv8, q, k, v, out, batch, seqlen_q, block_table, kv_lens, q_lens, causal,
